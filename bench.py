@@ -13,6 +13,8 @@ never here).  N = 1: the 8192^3 problem.  N > 1: weak scaling -- every rank owns
 (8192 N) x 8192 x 8192 problem (configs[4] at N = 8), row panels dealt block-cyclically, C
 all-gathered over RCCL/xGMI inside the timed region (laser_amd/distributed.py).
 
+--dump-outputs DIR writes C of the last timed step (float32 .npy, a fixed row sample for large C) for comparing two builds.
+
 Prints ONE JSON line on rank 0.  `roofline` prices the GEMM kernel alone against the dense fp32
 MFMA peak (157.3 TFLOP/s, /opt/skills/guides/MI355X_MICROARCH.md); `cpu_baseline` is the CPU
 oracle's OpenMP restatement of Laser's algorithm timed on this host's cores on a bounded sample of
@@ -65,10 +67,30 @@ def last_kernel_name(laser_amd):
 
 
 SIZE = 8192
+DUMP_BYTES = 32 << 20   # --dump-outputs: all files of one run together (well under 64 MB)
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: what the timed path computed in its last step, one DIR/<name>.npy (float32) per output array.  An
+    output larger than its share of DUMP_BYTES is written as a fixed sample of its rows (seeded, sorted; the same rows for the
+    same arguments), so two builds can be compared output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, a in arrays.items():
+        rows, cols = a.shape
+        keep = max(1, min(rows, share // (a.element_size() * cols)))
+        if keep < rows:
+            idx = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+            a = a.index_select(0, torch.as_tensor(idx, device=a.device))
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a.to(torch.float32).cpu().numpy())
+        log(f"[dump-outputs] {path}: {keep} of {rows} rows x {cols}")
 
 
 def host_info():
@@ -415,6 +437,8 @@ def single_process_primary(args):
     for d in set(devices):
         torch.cuda.synchronize(d)
     wall = time.perf_counter() - t0
+    if args.dump_outputs:                  # before the transport legs below run the product again
+        dump_outputs(args.dump_outputs, {("C" if g == 0 else f"C_slot{g}"): Cs[g][:M] for g in range(ndev)})
     # self-check on every device: a few rows owned by EVERY slot (only right if the gather delivered them), vs fp64
     err = 0.0
     for g in range(ndev):
@@ -646,7 +670,12 @@ def main():
     ap.add_argument("--single-process", type=int, default=0, metavar="NDEV",
                     help="run ONLY the single-process sharded entry point of the C-ABI over NDEV GPUs and print its JSON")
     ap.add_argument("--no-single-process", action="store_true", help="skip the single-process sharded side measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write C of the last timed step as DIR/<name>.npy (float32; a fixed, seeded row "
+                         "sample when C is larger than the dump budget)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.single_process > 0:
         import torch
@@ -798,6 +827,8 @@ def main():
     ref = hashed(check_rows, K, 1).double() @ B.double()
     err = (C[check_rows].double() - ref).abs().max().item()
     assert err < 1e-4, f"bench self-check failed on rank {rank}: max abs err {err}"
+    if args.dump_outputs and rank == 0:    # before the other mode / compute-only legs below run the product again
+        dump_outputs(args.dump_outputs, {"C": C[:M_total]})
 
     # N > 1: (i) the same panels WITHOUT the exchange (compute-only: what the step would cost if the gather were free), max over
     # ranks; (ii) the roofline object prices the GEMM kernel alone -- this rank's row share as ONE launch under the same tile pin

@@ -194,6 +194,30 @@ def test_committed_traffic_figure_matches_the_shipped_kernels():
         assert bench.pmc_traffic(mode, dict(d["plans"][mode], wgs=1)) is None      # another launch plan: the figure is not quoted
 
 
+def test_bench_dump_outputs_is_a_fixed_sample_within_budget(tmp_path):
+    """bench.py --dump-outputs: a small C is written whole, a large one as the same seeded row sample on every call, float32,
+    and every file of one run together stays under 64 MB (eight device slots of the 8192^2 C share the budget)."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    small = torch.arange(64 * 48, dtype=torch.float32).reshape(64, 48)
+    bench.dump_outputs(str(tmp_path / "small"), {"C": small})
+    assert np.array_equal(np.load(tmp_path / "small" / "C.npy"), small.numpy())
+    big = torch.rand((8192, 8192), generator=torch.Generator().manual_seed(0))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {("C" if g == 0 else f"C_slot{g}"): big for g in range(8)})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["C.npy"] + [f"C_slot{g}.npy" for g in range(1, 8)]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64 << 20
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and a.shape[1] == 8192 and 0 < a.shape[0] < 8192 and np.array_equal(a, b)
+        rows = {float(v): i for i, v in enumerate(big.numpy()[:, 0])}
+        assert all(np.array_equal(r, big.numpy()[rows[float(r[0])]]) for r in a)   # rows of C itself, not a reduction of it
+
+
 def test_launch_plans_scale_with_the_device_cu_count():
     """VERDICT r5 missing #4: 256 CUs / 8 XCDs were compile-time constants and a partitioned MI355X (CPX 32 / QPX 64 / DPX 128 CUs)
     stepped off every assembly kernel.  The launcher now plans with the device's own CU count; laser_hip_plan_f32 shows the choice
