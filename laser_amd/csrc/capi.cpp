@@ -467,49 +467,37 @@ hipError_t int_gemm_k_chunks(const GemmArgs<T> &a, void *ws, hipStream_t s, FA a
   return e;
 }
 
-template <>
-hipError_t run_gemm<int32_t>(const GemmArgs<int32_t> &a, hipStream_t s) {
-  // Large single problems go to the int8 matrix cores (limb decomposition, gemm_i32_mfma.hip); the
-  // limb planes live in stream-ordered scratch so concurrent streams never share a buffer.
+// Integer GEMMs mod 2^32 / 2^64.  Large single problems go to the int8 matrix cores (limb decomposition: four limbs,
+// gemm_i32_mfma.hip; eight, gemm_i64_mfma.hip); the limb planes live in stream-ordered scratch so concurrent streams never share a
+// buffer.  The hand-scheduled kernels (laser_amd/asmgen/i8_kernel.py) take what they can, K > 8192 in chunks.
+template <typename T>
+hipError_t run_gemm_int(const GemmArgs<T> &a, hipStream_t s) {
+  constexpr bool i32 = std::is_same<T, int32_t>::value;
   if (g_ctx.skinny) {
-    const hipError_t e = launch_gemm_skinny<int32_t>(a, false, 512, s);
+    const hipError_t e = launch_gemm_skinny<T>(a, false, i32 ? 512 : 256, s);
     if (e != hipErrorNotSupported) return e;
   }
   const double work = (double)a.M * (double)a.N * (double)a.K;
-  if (g_ctx.i32_mfma && a.batch == 1 && work >= 64.0 * 64.0 * 64.0 * 8.0) {
+  if ((i32 ? g_ctx.i32_mfma : g_ctx.i64_mfma) && a.batch == 1 && work >= 64.0 * 64.0 * 64.0 * 8.0) {
+    using Launch = hipError_t (*)(const GemmArgs<T> &, void *, hipStream_t);
+    Launch asm_launch, mfma_launch;     // the hand-scheduled kernel; the compiler-scheduled one where it does not apply
+    if constexpr (i32) asm_launch = launch_gemm_i32_asm, mfma_launch = launch_gemm_i32_mfma;
+    else asm_launch = launch_gemm_i64_asm, mfma_launch = launch_gemm_i64_mfma;
     void *ws = nullptr;
-    hipError_t e = scratch_alloc_async(&ws, gemm_i32_mfma_workspace_bytes(a.M, a.N, a.K), s);
+    hipError_t e = scratch_alloc_async(&ws, (i32 ? gemm_i32_mfma_workspace_bytes : gemm_i64_mfma_workspace_bytes)(a.M, a.N, a.K), s);
     if (e != hipSuccess) return e;
     g_last_i32_asm = 0;
-    // the hand-scheduled kernel (laser_amd/asmgen/i8_kernel.py) when eligible, K > 8192 in chunks
-    e = a.K > 8192 ? int_gemm_k_chunks<int32_t>(a, ws, s, launch_gemm_i32_asm, launch_gemm_i32_mfma) : launch_gemm_i32_asm(a, ws, s);
-    if (e == hipErrorNotSupported) e = launch_gemm_i32_mfma(a, ws, s);
+    e = a.K > 8192 ? int_gemm_k_chunks<T>(a, ws, s, asm_launch, mfma_launch) : asm_launch(a, ws, s);
+    if (e == hipErrorNotSupported) e = mfma_launch(a, ws, s);
     hipError_t e2 = hipFreeAsync(ws, s);
     return e != hipSuccess ? e : e2;
   }
-  return launch_gemm_valu<int32_t>(a, false, s);
+  return launch_gemm_valu<T>(a, false, s);
 }
 template <>
-hipError_t run_gemm<int64_t>(const GemmArgs<int64_t> &a, hipStream_t s) {
-  if (g_ctx.skinny) {
-    const hipError_t e = launch_gemm_skinny<int64_t>(a, false, 256, s);
-    if (e != hipErrorNotSupported) return e;
-  }
-  // Large single problems: eight int8 limbs on the matrix cores (gemm_i64_mfma.hip), planes in stream-ordered scratch
-  const double work = (double)a.M * (double)a.N * (double)a.K;
-  if (g_ctx.i64_mfma && a.batch == 1 && work >= 64.0 * 64.0 * 64.0 * 8.0) {
-    void *ws = nullptr;
-    hipError_t e = scratch_alloc_async(&ws, gemm_i64_mfma_workspace_bytes(a.M, a.N, a.K), s);
-    if (e != hipSuccess) return e;
-    g_last_i32_asm = 0;
-    // the hand-scheduled kernel (i8_kernel.py "i64_64x64x32") when eligible, K > 8192 in chunks
-    e = a.K > 8192 ? int_gemm_k_chunks<int64_t>(a, ws, s, launch_gemm_i64_asm, launch_gemm_i64_mfma) : launch_gemm_i64_asm(a, ws, s);
-    if (e == hipErrorNotSupported) e = launch_gemm_i64_mfma(a, ws, s);
-    hipError_t e2 = hipFreeAsync(ws, s);
-    return e != hipSuccess ? e : e2;
-  }
-  return launch_gemm_valu<int64_t>(a, false, s);
-}
+hipError_t run_gemm<int32_t>(const GemmArgs<int32_t> &a, hipStream_t s) { return run_gemm_int(a, s); }
+template <>
+hipError_t run_gemm<int64_t>(const GemmArgs<int64_t> &a, hipStream_t s) { return run_gemm_int(a, s); }
 
 // the small-matrix kernel on operands that live in host memory mapped into the device (gemm_host's zero-copy staging)
 template <typename T>

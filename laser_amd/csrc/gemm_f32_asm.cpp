@@ -47,8 +47,25 @@ int asm_tile_pin_now() { return tl_asm_tile >= -1 ? tl_asm_tile : (int)g_asm_til
 
 namespace {
 
+// What a kernel is: the choosers look rows up by these attributes (find_kernel), never by position
+enum Family : uint8_t {
+  kF32,        // float32 GEMM on 32x32 blocks (laser_amd/asmgen/f32_kernel.py)
+  kF32x16,     // float32 GEMM on 16x16 blocks (v_mfma_f32_16x16x4_f32; asmgen/f32x16_kernel.py)
+  kF64,        // float64 GEMM (v_mfma_f64_16x16x4_f64; asmgen/f64_kernel.py)
+  kI32,        // int32 GEMM via four int8 limb planes (asmgen/i8_kernel.py)
+  kI64,        // int64 GEMM via eight int8 limb planes (i8_kernel.py "i64_64x64x32")
+  kConv,       // implicit-GEMM convolution, any kernel size / stride / zero padding (f32_kernel.py)
+  kConvWalk,   // the same as unit walkers (f32_kernel.py Cfg.cpers): a workgroup runs units (image, tile) g, g + G, g + 2G ... and goes
+               // from one to the next inside its K loop (the next unit's first gathers before the old tile's last K-tiles are
+               // multiplied, the old tile's C stores from the gaps of the new tile's first K-tile body)
+};
 struct KernelInfo {
   const char *symbol;
+  Family fam;
+  bool exact;   // laser-order: the chain restarts every kc (gemm.nim:150-158); false: one chain over the whole K
+  bool nt;      // B passed transposed (unit ROW stride: k-contiguous like A, BASELINE configs[2])
+  bool pre;     // fused prologue: relu on A's and / or B's elements in the staging registers; one tile per workgroup
+  int cls;      // tile class of option "asm_tile" (the f32 GEMM families; -1 for the others)
   int bm, bn, bk;
   // tile-choice model (round 4: refitted to profiles/r04/plan_sweep_f32_mid_v2.jsonl, every candidate x plan forced; round 6: the 128x128x16 tile's
   // alone-on-its-CU figure 0.935 -> 0.92 -- 2048^3, one round of 256 tiles: 128.4 us against the 32-deep variant's 126.6, x16_ab_mid_j.jsonl): fraction of the matrix peak a CU reaches on this tile when
@@ -56,96 +73,156 @@ struct KernelInfo {
   // loads, epilogue of the last round) in microseconds
   double eff, eff_alone, fixed_us;
   int occ;   // workgroups of this kernel a CU holds (registers / LDS)
+  // Kernels whose persistent workgroups go from one whole tile to the next without leaving the K loop (asmgen/f32_kernel.py Cfg.pipe:
+  // the next tile's first K-tiles are fetched by the last bodies of this one, its first body stores this one's C): what one such
+  // transition saves against a fresh workgroup per tile, in microseconds (0: the kernel has no pipelined transition).  Measured:
+  // profiles/r06/pipe_*.jsonl.  256x128x32 (one workgroup per CU): pipe_ab_{big,mid}_b.jsonl (plain vs strided, interleaved, same
+  // bits): +0.2 ... +0.5 % at 4096^3 ... 8192^3, +1.6 % at 5120^3, +1.3 ... +2.3 % on the convolution's GEMM twin (8192x3072x1152:
+  // three tiles of 36 K-tiles per workgroup).  128x128x32: +0.3 ... +3 %, a tile the model rarely picks.  The 16x16-block tiles
+  // (f32x16_kernel.py trans_after) and float64 128x128x16 (f64_kernel.py trans_after): one workgroup per CU too.  256x256x16: -1.8 ...
+  // +1.1 % (sixteen blocks' stores in the first sixteen gaps of a 16-deep body): left alone.  Two or three workgroups per CU
+  // (128x128x16, 64x64) cover each other's transitions already, and a static share of the tiles quantises in workgroup slots where
+  // the plain launch quantises in CUs: -0.3 ... -14 %
+  double pipe_us;
+  // what tells a row from the others of its family with the same exact / nt / pre: the tile class, or the tile's rows
+  constexpr int tile() const { return cls >= 0 ? cls : bm; }
 };
-// [0] laser-order, large tile  [1] one chain, large tile  [2] laser-order, 128x128  [3] one chain, 128x128;
-// [4..7] the same with B passed transposed (unit ROW stride: k-contiguous like A, BASELINE configs[2])
-// [8] / [9]: one chain on the 256x128x32 tile (plain / B transposed): finer tile quantisation for the fast mode
-// [10] / [11]: implicit-GEMM convolution, 3x3 kernel, stride 1, any zero padding (laser-order / one chain)
-// [12..15]: 64x64 tiles, three workgroups per CU (laser-order / one chain, plain / B transposed): problems of few tiles
-// (1024^3 = 32 tiles of 256x128 for 256 CUs) and the tile quantisation of mid-size ones (3072^3 = 1.125 rounds of 256x128)
-// [16..19]: float64 (v_mfma_f64_16x16x4_f64; laser_amd/asmgen/f64_kernel.py): 128x128x16 laser-order / one chain, 64x64x16 same
-// [20]: int32 via int8 limb planes (laser_amd/asmgen/i8_kernel.py)
-// [21..24]: convolution with fewer output channels: 128x128x32 (laser-order / one chain), 64x128x32 (same)
-// [25..28]: float64 with B passed transposed: 128x128x16 (laser-order / one chain), 64x64x16 (same)
-// [29]: int64 via eight int8 limb planes (i8_kernel.py "i64_64x64x32")
-// [30..33]: 128x128 tiles with a 32-deep K-tile, one workgroup per CU (laser-order / one chain, plain / B transposed): one round of
-// 129 .. 256 tiles, where a workgroup has its CU to itself
-// [34..45]: fused prologue (relu on A's and / or B's elements in the staging registers): `_pre` variants of [0] [4] [1] [5] [2] [6] [3]
-// [7] [12] [14] [13] [15], one tile per workgroup
-// [46..53]: float32 on 16x16 blocks (v_mfma_f32_16x16x4_f32; laser_amd/asmgen/f32x16_kernel.py): tiles whose sides are multiples of 32
-// -- 96x96 (laser-order / one chain, plain / B transposed) and 160x96 (same) -- for the problems the 32x32-block tiles quantise badly:
-// the reference's own benchmark shape 1920^3 (gemm_bench_float32.nim:383-410) is 240 tiles of 160x96 against 225 of 128x128 on 256
-// CUs; 1536^3 is 256 tiles of 96x96 against 144 of 128x128
-// [54..65]: the same family's 128x96, 192x96 and 160x160 tiles (four variants each, in that order)
-// [66..71]: the convolution kernels [10] [11] [21..24] as unit walkers (f32_kernel.py Cfg.cpers): a workgroup runs units (image, tile)
-// g, g + G, g + 2G ... and goes from one to the next inside its K loop (the next unit's first gathers before the old tile's last
-// K-tiles are multiplied, the old tile's C stores from the gaps of the new tile's first K-tile body)
+// One row per kernel.  The position is visible outside this file -- last_f32_asm / last_f64_asm / last_i32_asm = 1 + index, option
+// "asm_kernel", laser_hip_plan_f32, bench.py's ASM_KERNEL_SYMBOLS -- so rows are appended, never moved.
+// Tile classes: 0 = the large tile (laser-order 256x128x32, one chain 256x256x16), 1 = 256x128x32 one chain (finer tile quantisation
+// for the fast mode), 2 = 128x128x16, 3 = 128x128x32 (one workgroup per CU: one round of 129 .. 256 tiles, where a workgroup has its
+// CU to itself), 4 = 64x64x32 (three workgroups per CU: problems of few tiles -- 1024^3 = 32 tiles of 256x128 for 256 CUs -- and the
+// tile quantisation of mid-size ones -- 3072^3 = 1.125 rounds of 256x128); on 16x16 blocks, tiles whose sides are multiples of 32 for
+// the problems the 32x32-block tiles quantise badly: 5 = 96x96, 6 = 160x96, 7 = 128x96, 8 = 192x96, 9 = 160x160 (the reference's own
+// benchmark shape 1920^3, gemm_bench_float32.nim:383-410, is 240 tiles of 160x96 against 225 of 128x128 on 256 CUs; 1536^3 is 256
+// tiles of 96x96 against 144 of 128x128).  The convolution tiles: 256x128 (up to 31 taps), 128x128 and 64x128 (fewer output channels).
 constexpr int kNumKernels = 72;
-const KernelInfo kKernels[kNumKernels] = {
-    {"lh_f32_exact_256x128x32", 256, 128, 32, 0.965, 0.965, 10.0, 1},    {"lh_f32_fast_256x256x16", 256, 256, 16, 0.98, 0.98, 12.0, 1},
-    {"lh_f32_exact_128x128x16", 128, 128, 16, 0.95, 0.92, 6.0, 2},       {"lh_f32_fast_128x128x16", 128, 128, 16, 0.96, 0.93, 6.0, 2},
-    {"lh_f32_exact_256x128x32_nt", 256, 128, 32, 0.965, 0.965, 10.0, 1}, {"lh_f32_fast_256x256x16_nt", 256, 256, 16, 0.98, 0.98, 12.0, 1},
-    {"lh_f32_exact_128x128x16_nt", 128, 128, 16, 0.95, 0.92, 6.0, 2},    {"lh_f32_fast_128x128x16_nt", 128, 128, 16, 0.96, 0.93, 6.0, 2},
-    {"lh_f32_fast_256x128x32", 256, 128, 32, 0.97, 0.97, 10.0, 1},       {"lh_f32_fast_256x128x32_nt", 256, 128, 32, 0.97, 0.97, 10.0, 1},
-    {"lh_f32_conv_exact_256x128x32", 256, 128, 32, 0.88, 0.88, 15.0, 1}, {"lh_f32_conv_fast_256x128x32", 256, 128, 32, 0.88, 0.88, 15.0, 1},
-    {"lh_f32_exact_64x64x32", 64, 64, 32, 0.90, 0.84, 6.0, 3},           {"lh_f32_fast_64x64x32", 64, 64, 32, 0.91, 0.85, 6.0, 3},
-    {"lh_f32_exact_64x64x32_nt", 64, 64, 32, 0.90, 0.84, 6.0, 3},        {"lh_f32_fast_64x64x32_nt", 64, 64, 32, 0.91, 0.85, 6.0, 3},
-    {"lh_f64_exact_128x128x16", 128, 128, 16, 0.937, 0.945, 8.0, 1},     {"lh_f64_fast_128x128x16", 128, 128, 16, 0.965, 0.97, 8.0, 1},
-    {"lh_f64_exact_64x64x16", 64, 64, 16, 0.915, 0.815, 3.0, 2},         {"lh_f64_fast_64x64x16", 64, 64, 16, 0.93, 0.83, 3.0, 2},
-    {"lh_i32_128x128x32", 128, 128, 32, 0.8, 0.8, 10.0, 1},
-    {"lh_f32_conv_exact_128x128x32", 128, 128, 32, 0.8, 0.8, 12.0, 1}, {"lh_f32_conv_fast_128x128x32", 128, 128, 32, 0.8, 0.8, 12.0, 1},
-    {"lh_f32_conv_exact_64x128x32", 64, 128, 32, 0.72, 0.72, 8.0, 2},  {"lh_f32_conv_fast_64x128x32", 64, 128, 32, 0.72, 0.72, 8.0, 2},
-    {"lh_f64_exact_128x128x16_nt", 128, 128, 16, 0.937, 0.945, 8.0, 1},   {"lh_f64_fast_128x128x16_nt", 128, 128, 16, 0.965, 0.97, 8.0, 1},
-    {"lh_f64_exact_64x64x16_nt", 64, 64, 16, 0.915, 0.815, 3.0, 2},       {"lh_f64_fast_64x64x16_nt", 64, 64, 16, 0.93, 0.83, 3.0, 2},
-    {"lh_i64_64x64x32", 64, 64, 32, 0.7, 0.7, 10.0, 1},
-    {"lh_f32_exact_128x128x32", 128, 128, 32, 0.95, 0.95, 7.0, 1},       {"lh_f32_fast_128x128x32", 128, 128, 32, 0.96, 0.96, 7.0, 1},
-    {"lh_f32_exact_128x128x32_nt", 128, 128, 32, 0.95, 0.95, 7.0, 1},    {"lh_f32_fast_128x128x32_nt", 128, 128, 32, 0.96, 0.96, 7.0, 1},
-    {"lh_f32_exact_256x128x32_pre", 256, 128, 32, 0.92, 0.92, 10.0, 1},  {"lh_f32_exact_256x128x32_pre_nt", 256, 128, 32, 0.92, 0.92, 10.0, 1},
-    {"lh_f32_fast_256x256x16_pre", 256, 256, 16, 0.93, 0.93, 12.0, 1},   {"lh_f32_fast_256x256x16_pre_nt", 256, 256, 16, 0.93, 0.93, 12.0, 1},
-    {"lh_f32_exact_128x128x16_pre", 128, 128, 16, 0.90, 0.86, 6.0, 2},   {"lh_f32_exact_128x128x16_pre_nt", 128, 128, 16, 0.90, 0.86, 6.0, 2},
-    {"lh_f32_fast_128x128x16_pre", 128, 128, 16, 0.91, 0.87, 6.0, 2},    {"lh_f32_fast_128x128x16_pre_nt", 128, 128, 16, 0.91, 0.87, 6.0, 2},
-    {"lh_f32_exact_64x64x32_pre", 64, 64, 32, 0.84, 0.74, 3.0, 3},       {"lh_f32_exact_64x64x32_pre_nt", 64, 64, 32, 0.84, 0.74, 3.0, 3},
-    {"lh_f32_fast_64x64x32_pre", 64, 64, 32, 0.85, 0.76, 3.0, 3},        {"lh_f32_fast_64x64x32_pre_nt", 64, 64, 32, 0.85, 0.76, 3.0, 3},
+constexpr KernelInfo kKernels[kNumKernels] = {
+    // symbol                          family     exact nt pre  cls   bm   bn  bk eff    alone  fixed occ pipe_us
+    {"lh_f32_exact_256x128x32",        kF32,      1,    0, 0,    0, 256, 128, 32, 0.965, 0.965, 10.0,  1, 2.5}, // 0
+    {"lh_f32_fast_256x256x16",         kF32,      0,    0, 0,    0, 256, 256, 16, 0.98,  0.98,  12.0,  1, 0},   // 1
+    {"lh_f32_exact_128x128x16",        kF32,      1,    0, 0,    2, 128, 128, 16, 0.95,  0.92,   6.0,  2, 0},   // 2
+    {"lh_f32_fast_128x128x16",         kF32,      0,    0, 0,    2, 128, 128, 16, 0.96,  0.93,   6.0,  2, 0},   // 3
+    {"lh_f32_exact_256x128x32_nt",     kF32,      1,    1, 0,    0, 256, 128, 32, 0.965, 0.965, 10.0,  1, 2.5}, // 4
+    {"lh_f32_fast_256x256x16_nt",      kF32,      0,    1, 0,    0, 256, 256, 16, 0.98,  0.98,  12.0,  1, 0},   // 5
+    {"lh_f32_exact_128x128x16_nt",     kF32,      1,    1, 0,    2, 128, 128, 16, 0.95,  0.92,   6.0,  2, 0},   // 6
+    {"lh_f32_fast_128x128x16_nt",      kF32,      0,    1, 0,    2, 128, 128, 16, 0.96,  0.93,   6.0,  2, 0},   // 7
+    {"lh_f32_fast_256x128x32",         kF32,      0,    0, 0,    1, 256, 128, 32, 0.97,  0.97,  10.0,  1, 2.5}, // 8
+    {"lh_f32_fast_256x128x32_nt",      kF32,      0,    1, 0,    1, 256, 128, 32, 0.97,  0.97,  10.0,  1, 2.5}, // 9
+    {"lh_f32_conv_exact_256x128x32",   kConv,     1,    0, 0,   -1, 256, 128, 32, 0.88,  0.88,  15.0,  1, 0},   // 10
+    {"lh_f32_conv_fast_256x128x32",    kConv,     0,    0, 0,   -1, 256, 128, 32, 0.88,  0.88,  15.0,  1, 0},   // 11
+    {"lh_f32_exact_64x64x32",          kF32,      1,    0, 0,    4,  64,  64, 32, 0.90,  0.84,   6.0,  3, 0},   // 12
+    {"lh_f32_fast_64x64x32",           kF32,      0,    0, 0,    4,  64,  64, 32, 0.91,  0.85,   6.0,  3, 0},   // 13
+    {"lh_f32_exact_64x64x32_nt",       kF32,      1,    1, 0,    4,  64,  64, 32, 0.90,  0.84,   6.0,  3, 0},   // 14
+    {"lh_f32_fast_64x64x32_nt",        kF32,      0,    1, 0,    4,  64,  64, 32, 0.91,  0.85,   6.0,  3, 0},   // 15
+    {"lh_f64_exact_128x128x16",        kF64,      1,    0, 0,   -1, 128, 128, 16, 0.937, 0.945,  8.0,  1, 3.0}, // 16
+    {"lh_f64_fast_128x128x16",         kF64,      0,    0, 0,   -1, 128, 128, 16, 0.965, 0.97,   8.0,  1, 3.0}, // 17
+    {"lh_f64_exact_64x64x16",          kF64,      1,    0, 0,   -1,  64,  64, 16, 0.915, 0.815,  3.0,  2, 0},   // 18
+    {"lh_f64_fast_64x64x16",           kF64,      0,    0, 0,   -1,  64,  64, 16, 0.93,  0.83,   3.0,  2, 0},   // 19
+    {"lh_i32_128x128x32",              kI32,      0,    0, 0,   -1, 128, 128, 32, 0.8,   0.8,   10.0,  1, 0},   // 20
+    {"lh_f32_conv_exact_128x128x32",   kConv,     1,    0, 0,   -1, 128, 128, 32, 0.8,   0.8,   12.0,  1, 0},   // 21
+    {"lh_f32_conv_fast_128x128x32",    kConv,     0,    0, 0,   -1, 128, 128, 32, 0.8,   0.8,   12.0,  1, 0},   // 22
+    {"lh_f32_conv_exact_64x128x32",    kConv,     1,    0, 0,   -1,  64, 128, 32, 0.72,  0.72,   8.0,  2, 0},   // 23
+    {"lh_f32_conv_fast_64x128x32",     kConv,     0,    0, 0,   -1,  64, 128, 32, 0.72,  0.72,   8.0,  2, 0},   // 24
+    {"lh_f64_exact_128x128x16_nt",     kF64,      1,    1, 0,   -1, 128, 128, 16, 0.937, 0.945,  8.0,  1, 3.0}, // 25
+    {"lh_f64_fast_128x128x16_nt",      kF64,      0,    1, 0,   -1, 128, 128, 16, 0.965, 0.97,   8.0,  1, 3.0}, // 26
+    {"lh_f64_exact_64x64x16_nt",       kF64,      1,    1, 0,   -1,  64,  64, 16, 0.915, 0.815,  3.0,  2, 0},   // 27
+    {"lh_f64_fast_64x64x16_nt",        kF64,      0,    1, 0,   -1,  64,  64, 16, 0.93,  0.83,   3.0,  2, 0},   // 28
+    {"lh_i64_64x64x32",                kI64,      0,    0, 0,   -1,  64,  64, 32, 0.7,   0.7,   10.0,  1, 0},   // 29
+    {"lh_f32_exact_128x128x32",        kF32,      1,    0, 0,    3, 128, 128, 32, 0.95,  0.95,   7.0,  1, 1.0}, // 30
+    {"lh_f32_fast_128x128x32",         kF32,      0,    0, 0,    3, 128, 128, 32, 0.96,  0.96,   7.0,  1, 1.0}, // 31
+    {"lh_f32_exact_128x128x32_nt",     kF32,      1,    1, 0,    3, 128, 128, 32, 0.95,  0.95,   7.0,  1, 1.0}, // 32
+    {"lh_f32_fast_128x128x32_nt",      kF32,      0,    1, 0,    3, 128, 128, 32, 0.96,  0.96,   7.0,  1, 1.0}, // 33
+    {"lh_f32_exact_256x128x32_pre",    kF32,      1,    0, 1,    0, 256, 128, 32, 0.92,  0.92,  10.0,  1, 0},   // 34
+    {"lh_f32_exact_256x128x32_pre_nt", kF32,      1,    1, 1,    0, 256, 128, 32, 0.92,  0.92,  10.0,  1, 0},   // 35
+    {"lh_f32_fast_256x256x16_pre",     kF32,      0,    0, 1,    0, 256, 256, 16, 0.93,  0.93,  12.0,  1, 0},   // 36
+    {"lh_f32_fast_256x256x16_pre_nt",  kF32,      0,    1, 1,    0, 256, 256, 16, 0.93,  0.93,  12.0,  1, 0},   // 37
+    {"lh_f32_exact_128x128x16_pre",    kF32,      1,    0, 1,    2, 128, 128, 16, 0.90,  0.86,   6.0,  2, 0},   // 38
+    {"lh_f32_exact_128x128x16_pre_nt", kF32,      1,    1, 1,    2, 128, 128, 16, 0.90,  0.86,   6.0,  2, 0},   // 39
+    {"lh_f32_fast_128x128x16_pre",     kF32,      0,    0, 1,    2, 128, 128, 16, 0.91,  0.87,   6.0,  2, 0},   // 40
+    {"lh_f32_fast_128x128x16_pre_nt",  kF32,      0,    1, 1,    2, 128, 128, 16, 0.91,  0.87,   6.0,  2, 0},   // 41
+    {"lh_f32_exact_64x64x32_pre",      kF32,      1,    0, 1,    4,  64,  64, 32, 0.84,  0.74,   3.0,  3, 0},   // 42
+    {"lh_f32_exact_64x64x32_pre_nt",   kF32,      1,    1, 1,    4,  64,  64, 32, 0.84,  0.74,   3.0,  3, 0},   // 43
+    {"lh_f32_fast_64x64x32_pre",       kF32,      0,    0, 1,    4,  64,  64, 32, 0.85,  0.76,   3.0,  3, 0},   // 44
+    {"lh_f32_fast_64x64x32_pre_nt",    kF32,      0,    1, 1,    4,  64,  64, 32, 0.85,  0.76,   3.0,  3, 0},   // 45
     // (fitted to profiles/r06/x16_ab_{ref,mid}_g.jsonl, x16_ab_more_i.jsonl; the laser-order entries + 0.007 with the running sum in VGPRs, x16_ab_big2_n.jsonl; the many-round figures of pipe_ab_x16_p.jsonl at 7680^3 -- 0.963 / 0.972 on 160x160, 0.934 / 0.952 on 96x96 --: plain launches at 1536^3 .. 5120^3, 1000x3000x2000; the 64x64 tiles'
     // fixed cost 3 -> 6 us from the same runs: 1664^3 and 1000x3000x2000 took 84 / 98 us where the table said 80 / 92)
-    {"lh_f32x16_exact_96x96x32", 96, 96, 32, 0.925, 0.925, 5.0, 1},        {"lh_f32x16_fast_96x96x32", 96, 96, 32, 0.943, 0.93, 5.0, 1},
-    {"lh_f32x16_exact_96x96x32_nt", 96, 96, 32, 0.925, 0.925, 5.0, 1},     {"lh_f32x16_fast_96x96x32_nt", 96, 96, 32, 0.943, 0.93, 5.0, 1},
-    {"lh_f32x16_exact_160x96x32", 160, 96, 32, 0.952, 0.958, 6.0, 1},    {"lh_f32x16_fast_160x96x32", 160, 96, 32, 0.96, 0.963, 6.0, 1},
-    {"lh_f32x16_exact_160x96x32_nt", 160, 96, 32, 0.952, 0.958, 6.0, 1}, {"lh_f32x16_fast_160x96x32_nt", 160, 96, 32, 0.96, 0.963, 6.0, 1},
-    {"lh_f32x16_exact_128x96x32", 128, 96, 32, 0.938, 0.922, 5.5, 1},    {"lh_f32x16_fast_128x96x32", 128, 96, 32, 0.935, 0.94, 5.5, 1},
-    {"lh_f32x16_exact_128x96x32_nt", 128, 96, 32, 0.938, 0.922, 5.5, 1}, {"lh_f32x16_fast_128x96x32_nt", 128, 96, 32, 0.935, 0.94, 5.5, 1},
-    {"lh_f32x16_exact_192x96x32", 192, 96, 32, 0.95, 0.952, 6.5, 1},    {"lh_f32x16_fast_192x96x32", 192, 96, 32, 0.962, 0.965, 6.5, 1},
-    {"lh_f32x16_exact_192x96x32_nt", 192, 96, 32, 0.95, 0.952, 6.5, 1}, {"lh_f32x16_fast_192x96x32_nt", 192, 96, 32, 0.962, 0.965, 6.5, 1},
-    {"lh_f32x16_exact_160x160x32", 160, 160, 32, 0.959, 0.945, 8.0, 1},  {"lh_f32x16_fast_160x160x32", 160, 160, 32, 0.968, 0.956, 8.0, 1},
-    {"lh_f32x16_exact_160x160x32_nt", 160, 160, 32, 0.959, 0.945, 8.0, 1}, {"lh_f32x16_fast_160x160x32_nt", 160, 160, 32, 0.968, 0.956, 8.0, 1},
-    {"lh_f32_conv_exact_256x128x32_p", 256, 128, 32, 0.90, 0.90, 15.0, 1}, {"lh_f32_conv_fast_256x128x32_p", 256, 128, 32, 0.90, 0.90, 15.0, 1},
-    {"lh_f32_conv_exact_128x128x32_p", 128, 128, 32, 0.82, 0.82, 12.0, 1}, {"lh_f32_conv_fast_128x128x32_p", 128, 128, 32, 0.82, 0.82, 12.0, 1},
-    {"lh_f32_conv_exact_64x128x32_p", 64, 128, 32, 0.74, 0.74, 8.0, 2},    {"lh_f32_conv_fast_64x128x32_p", 64, 128, 32, 0.74, 0.74, 8.0, 2}};
-// plain kernel -> its `_pre` variant (-1: none)
-int pre_variant(int k) {
-  switch (k) {
-    case 0: return 34; case 4: return 35; case 1: return 36; case 5: return 37; case 2: return 38; case 6: return 39;
-    case 3: return 40; case 7: return 41; case 12: return 42; case 14: return 43; case 13: return 44; case 15: return 45;
-    default: return -1;
+    {"lh_f32x16_exact_96x96x32",       kF32x16,   1,    0, 0,    5,  96,  96, 32, 0.925, 0.925,  5.0,  1, 1.5}, // 46
+    {"lh_f32x16_fast_96x96x32",        kF32x16,   0,    0, 0,    5,  96,  96, 32, 0.943, 0.93,   5.0,  1, 1.5}, // 47
+    {"lh_f32x16_exact_96x96x32_nt",    kF32x16,   1,    1, 0,    5,  96,  96, 32, 0.925, 0.925,  5.0,  1, 1.5}, // 48
+    {"lh_f32x16_fast_96x96x32_nt",     kF32x16,   0,    1, 0,    5,  96,  96, 32, 0.943, 0.93,   5.0,  1, 1.5}, // 49
+    {"lh_f32x16_exact_160x96x32",      kF32x16,   1,    0, 0,    6, 160,  96, 32, 0.952, 0.958,  6.0,  1, 1.5}, // 50
+    {"lh_f32x16_fast_160x96x32",       kF32x16,   0,    0, 0,    6, 160,  96, 32, 0.96,  0.963,  6.0,  1, 1.5}, // 51
+    {"lh_f32x16_exact_160x96x32_nt",   kF32x16,   1,    1, 0,    6, 160,  96, 32, 0.952, 0.958,  6.0,  1, 1.5}, // 52
+    {"lh_f32x16_fast_160x96x32_nt",    kF32x16,   0,    1, 0,    6, 160,  96, 32, 0.96,  0.963,  6.0,  1, 1.5}, // 53
+    {"lh_f32x16_exact_128x96x32",      kF32x16,   1,    0, 0,    7, 128,  96, 32, 0.938, 0.922,  5.5,  1, 1.5}, // 54
+    {"lh_f32x16_fast_128x96x32",       kF32x16,   0,    0, 0,    7, 128,  96, 32, 0.935, 0.94,   5.5,  1, 1.5}, // 55
+    {"lh_f32x16_exact_128x96x32_nt",   kF32x16,   1,    1, 0,    7, 128,  96, 32, 0.938, 0.922,  5.5,  1, 1.5}, // 56
+    {"lh_f32x16_fast_128x96x32_nt",    kF32x16,   0,    1, 0,    7, 128,  96, 32, 0.935, 0.94,   5.5,  1, 1.5}, // 57
+    {"lh_f32x16_exact_192x96x32",      kF32x16,   1,    0, 0,    8, 192,  96, 32, 0.95,  0.952,  6.5,  1, 1.5}, // 58
+    {"lh_f32x16_fast_192x96x32",       kF32x16,   0,    0, 0,    8, 192,  96, 32, 0.962, 0.965,  6.5,  1, 1.5}, // 59
+    {"lh_f32x16_exact_192x96x32_nt",   kF32x16,   1,    1, 0,    8, 192,  96, 32, 0.95,  0.952,  6.5,  1, 1.5}, // 60
+    {"lh_f32x16_fast_192x96x32_nt",    kF32x16,   0,    1, 0,    8, 192,  96, 32, 0.962, 0.965,  6.5,  1, 1.5}, // 61
+    {"lh_f32x16_exact_160x160x32",     kF32x16,   1,    0, 0,    9, 160, 160, 32, 0.959, 0.945,  8.0,  1, 1.5}, // 62
+    {"lh_f32x16_fast_160x160x32",      kF32x16,   0,    0, 0,    9, 160, 160, 32, 0.968, 0.956,  8.0,  1, 1.5}, // 63
+    {"lh_f32x16_exact_160x160x32_nt",  kF32x16,   1,    1, 0,    9, 160, 160, 32, 0.959, 0.945,  8.0,  1, 1.5}, // 64
+    {"lh_f32x16_fast_160x160x32_nt",   kF32x16,   0,    1, 0,    9, 160, 160, 32, 0.968, 0.956,  8.0,  1, 1.5}, // 65
+    {"lh_f32_conv_exact_256x128x32_p", kConvWalk, 1,    0, 0,   -1, 256, 128, 32, 0.90,  0.90,  15.0,  1, 0},   // 66
+    {"lh_f32_conv_fast_256x128x32_p",  kConvWalk, 0,    0, 0,   -1, 256, 128, 32, 0.90,  0.90,  15.0,  1, 0},   // 67
+    {"lh_f32_conv_exact_128x128x32_p", kConvWalk, 1,    0, 0,   -1, 128, 128, 32, 0.82,  0.82,  12.0,  1, 0},   // 68
+    {"lh_f32_conv_fast_128x128x32_p",  kConvWalk, 0,    0, 0,   -1, 128, 128, 32, 0.82,  0.82,  12.0,  1, 0},   // 69
+    {"lh_f32_conv_exact_64x128x32_p",  kConvWalk, 1,    0, 0,   -1,  64, 128, 32, 0.74,  0.74,   8.0,  2, 0},   // 70
+    {"lh_f32_conv_fast_64x128x32_p",   kConvWalk, 0,    0, 0,   -1,  64, 128, 32, 0.74,  0.74,   8.0,  2, 0}    // 71
+};
+// The row of the kernel with these attributes, -1 if there is none.  tile: the tile class of the f32 GEMM families, the tile's rows
+// (bm) for the others.
+constexpr int find_kernel(Family fam, int tile, bool exact, bool nt = false, bool pre = false) {
+  for (int k = 0; k < kNumKernels; k++) {
+    const KernelInfo &r = kKernels[k];
+    if (r.fam == fam && r.tile() == tile && r.exact == exact && r.nt == nt && r.pre == pre) return k;
   }
+  return -1;
 }
+constexpr bool kernel_attributes_unique() {
+  for (int k = 0; k < kNumKernels; k++)
+    if (find_kernel(kKernels[k].fam, kKernels[k].tile(), kKernels[k].exact, kKernels[k].nt, kKernels[k].pre) != k) return false;
+  return true;
+}
+static_assert(kernel_attributes_unique(), "two rows of kKernels with the same attributes: find_kernel sees the first only");
+
+// The choosers' rows, resolved at compile time.  f32 GEMMs: [tile class][laser-order][B transposed][fused prologue]
+struct F32Rows { int k[10][2][2][2]; };
+constexpr F32Rows kF32Rows = [] {
+  F32Rows t{};
+  for (int c = 0; c < 10; c++)
+    for (int e = 0; e < 2; e++)
+      for (int n = 0; n < 2; n++)
+        for (int p = 0; p < 2; p++) t.k[c][e][n][p] = find_kernel(c < 5 ? kF32 : kF32x16, c, e, n, p);   // (5..9: 16x16 blocks)
+  return t;
+}();
+// f64 GEMMs: [128x128x16, 64x64x16][laser-order][B transposed]
+struct F64Rows { int k[2][2][2]; };
+constexpr F64Rows kF64Rows = [] {
+  F64Rows t{};
+  for (int i = 0; i < 2; i++)
+    for (int e = 0; e < 2; e++)
+      for (int n = 0; n < 2; n++) t.k[i][e][n] = find_kernel(kF64, i == 0 ? 128 : 64, e, n);
+  return t;
+}();
+// convolutions by tile rows: [256, 128, 64][laser-order], and the unit walker of each
+struct ConvRows { int k[3][2], walker[3][2]; };
+constexpr ConvRows kConvRows = [] {
+  ConvRows t{};
+  for (int i = 0; i < 3; i++)
+    for (int e = 0; e < 2; e++) {
+      t.k[i][e] = find_kernel(kConv, 256 >> i, e);
+      t.walker[i][e] = find_kernel(kConvWalk, 256 >> i, e);
+    }
+  return t;
+}();
+constexpr int kI32Row = find_kernel(kI32, 128, false), kI64Row = find_kernel(kI64, 64, false);
+static_assert(kI32Row >= 0 && kI64Row >= 0, "the integer limb kernels");
 constexpr int kFullCUs = 256;      // the unpartitioned MI355X (SPX): what the efficiency table was measured on
-// Kernels whose persistent workgroups go from one whole tile to the next without leaving the K loop (asmgen/f32_kernel.py Cfg.pipe:
-// the next tile's first K-tiles are fetched by the last bodies of this one, its first body stores this one's C): what one such
-// transition saves against a fresh workgroup per tile, in microseconds (0: the kernel has no pipelined transition).  Measured:
-// profiles/r06/pipe_*.jsonl.
-double pipe_gain_us(int k) {
-  // profiles/r06/pipe_ab_{big,mid}_b.jsonl (plain vs strided, interleaved, same bits): 256x128x32 +0.2 ... +0.5 % at 4096^3 ... 8192^3,
-  // +1.6 % at 5120^3, +1.3 ... +2.3 % on the convolution's GEMM twin (8192x3072x1152: three tiles of 36 K-tiles per workgroup)
-  if (k == 0 || k == 4 || k == 8 || k == 9) return 2.5;       // 256x128x32 (laser-order / one chain, B plain / transposed): one workgroup per CU
-  if (k >= 30 && k <= 33) return 1.0;                         // 128x128x32 (one workgroup per CU): +0.3 ... +3 %, a tile the model rarely picks
-  if (k >= 46 && k <= 65) return 1.5;                         // the 16x16-block tiles (one workgroup per CU; f32x16_kernel.py trans_after)
-  if (k == 16 || k == 17 || k == 25 || k == 26) return 3.0;   // float64 128x128x16 (one workgroup per CU; f64_kernel.py trans_after)
-  // 256x256x16: -1.8 ... +1.1 % (sixteen blocks' stores in the first sixteen gaps of a 16-deep body): left alone.  Two or three
-  // workgroups per CU (128x128x16, 64x64) cover each other's transitions already, and a static share of the tiles quantises in
-  // workgroup slots where the plain launch quantises in CUs: -0.3 ... -14 %
-  return 0.0;
-}
 // Workspace of the cut launches of ONE stream on one device: partial tiles + their flags (all flags are zero between launches: the
 // workgroup that consumes a partial clears its flag).  Launches on a stream run in order, so they can share it.
 struct StreamWs {
@@ -226,7 +303,11 @@ bool fill_sched(SchedArgs &sc, int64_t tiles_m, int64_t tiles_n, int group_m, in
   return true;
 }
 
-hipError_t get_module(int dev, DeviceModule **out) {
+// the current device's module: code object loaded, CU count read, on first use
+hipError_t current_module(DeviceModule **out) {
+  int dev = 0;
+  const hipError_t de = hipGetDevice(&dev);
+  if (de != hipSuccess) return de;
   if (dev < 0 || dev >= kMaxDev) return hipErrorInvalidDevice;
   DeviceModule &m = g_mods[dev];
   std::lock_guard<std::mutex> lk(m.mu);
@@ -252,14 +333,6 @@ hipError_t get_module(int dev, DeviceModule **out) {
   }
   *out = &m;
   return hipSuccess;
-}
-
-// compute units of the current device (cached by get_module); kFullCUs when it cannot be asked (the callers fail later, loudly)
-int current_cus() {
-  int dev = 0;
-  DeviceModule *m = nullptr;
-  if (hipGetDevice(&dev) != hipSuccess || get_module(dev, &m) != hipSuccess) return kFullCUs;
-  return m->cus;
 }
 
 // The stream's workspace, grown when needed (rare: an allocation + a clear on the launch stream).  Addresses handed out stay valid
@@ -572,6 +645,21 @@ hipError_t launch_planned(DeviceModule *m, int kern, const Plan &plan_in, KernAr
   return e;
 }
 
+// C^T = B^T A^T: the same product with the operands exchanged, C (and the bias view) read along its other direction -- every element
+// is the same k-ascending chain, so the bits are the same
+template <typename T>
+GemmArgs<T> transposed_problem(const GemmArgs<T> &a) {
+  GemmArgs<T> t = a;
+  std::swap(t.M, t.N);
+  std::swap(t.Mext, t.Next);
+  t.A = a.B; t.rsA = a.csB; t.csA = a.rsB;
+  t.B = a.A; t.rsB = a.csA; t.csB = a.rsA;
+  std::swap(t.rsC, t.csC);
+  std::swap(t.rsBias, t.csBias);
+  std::swap(t.preA, t.preB);
+  return t;
+}
+
 void zero_conv_fields(KernArgs &ka) {
   ka.unused_ = nullptr;
   ka.dbg = nullptr;
@@ -669,7 +757,7 @@ hipError_t choose_gemm_f32_asm(const GemmArgs<float> &a, bool laser_order, int c
   // laser-order results need the kc = 512 slices only when K > 512; one chain otherwise (the laser-order kernels are
   // plain single-chain kernels then: their fold tile is never reached)
   const bool exact = laser_order && a.K > 512;
-  const int big = (exact ? 0 : (a.K > 512 ? 1 : 0)) + (nt ? 4 : 0), small = (exact ? 2 : (a.K > 512 ? 3 : 2)) + (nt ? 4 : 0);
+  const bool lo_row = exact || a.K <= 512;   // the rows taken: laser-order ones (with K <= 512 in either mode), else one-chain ones
   // 32-bit byte offsets inside the descriptors
   if ((double)a.rsA * 4.0 * 256 >= 4.0e9) return hipErrorNotSupported;
   if ((nt ? (double)ldb * 4.0 * 256 : (double)a.K * (double)ldb * 4.0) >= 4.0e9) return hipErrorNotSupported;
@@ -682,44 +770,39 @@ hipError_t choose_gemm_f32_asm(const GemmArgs<float> &a, bool laser_order, int c
   // quantisation to one K slice.  3072^3: 288 tiles of 256x128 = 2 rounds for 1.125 rounds of work, or 6.75 slices per CU.
   int pick = -1;
   Plan plan;
-  const int mid = (!exact && a.K > 512) ? (nt ? 9 : 8) : -1;   // one chain over a long K: also the 256x128 tile
-  const int tiny = 12 + ((exact || a.K <= 512) ? 0 : 1) + (nt ? 2 : 0);
-  const int deep = 30 + ((exact || a.K <= 512) ? 0 : 1) + (nt ? 2 : 0);    // 128x128 with the 32-deep K-tile: one workgroup per CU
   const double cu_flops_per_us = 157.3e6 / 256.0;
-  // the one-chain kernels' fused epilogue has no C read: beta != 0 with a bias / activation only on the laser-order kernels
-  const auto lo_kernel = [](int k) { return k == 0 || k == 2 || k == 4 || k == 6 || k == 12 || k == 14 || k == 30 || k == 32 || (k >= 46 && k <= 65 && (k - 46) % 2 == 0); };
   const bool pre = a.preA != 0 || a.preB != 0;
   // A pinned tile class (option "asm_tile" / the sharded entry point's LASER_HIP_SHARD_PIN_TILE on its worker threads): the local
   // products of a multi-GPU run that shares the CUs with RCCL's kernels.  One tile per workgroup then -- a persistent plan counts on
-  // every workgroup slot of the chip -- and no lower bound on the tile count (the caller asked for THIS kernel family).
-  const int tile_pin = asm_tile_pin_now();
-  // 16x16-block tiles (f32x16_kernel.py): 16-byte pieces are all-or-nothing (K % 4 == 0), no fused prologue (the fused epilogue --
-  // bias view + relu -- and a column stride on C are theirs too)
-  const bool x16_ok = a.K % 4 == 0 && !pre;
-  const int x96 = x16_ok ? 46 + ((exact || a.K <= 512) ? 0 : 1) + (nt ? 2 : 0) : -1, x160 = x16_ok ? x96 + 4 : -1;
-  const int x128 = x16_ok ? x96 + 8 : -1, x192 = x16_ok ? x96 + 12 : -1, x160s = x16_ok ? x96 + 16 : -1;
-  const int classes[10] = {big, mid, small, deep, tiny, x96, x160, x128, x192, x160s};      // (index = the tile class of option "asm_tile")
+  // every workgroup slot of the chip -- and no lower bound on the tile count (the caller asked for THIS kernel family).  Class 1 has
+  // no laser-order row: where the row is laser-order it is class 0's 256x128 tile.
+  int tile_pin = asm_tile_pin_now();
+  if (tile_pin == 1 && kF32Rows.k[1][lo_row][nt][0] < 0) tile_pin = 0;
   // near ties go to the class asked first: within a block family, the larger tile (less L2 traffic, fewer workgroups)
   const int order[10] = {0, 1, 2, 3, 4, 9, 8, 6, 7, 5};
   for (int oi = 0; oi < 10; oi++) {
     const int ci = order[oi];
-    const int k0 = classes[ci];
-    if (tile_pin >= 0 && ci != (tile_pin == 1 && mid < 0 ? 0 : tile_pin)) continue;
+    const int k0 = kF32Rows.k[ci][lo_row][nt][0];
+    if (tile_pin >= 0 && ci != tile_pin) continue;
     if (k0 < 0 || (g_asm_kernel >= 0 && k0 != g_asm_kernel)) continue;
-    if (fused && !lo_kernel(k0) && a.beta != 0.0f) continue;
-    const int k = pre ? pre_variant(k0) : k0;       // fused prologue: the variants that apply it in the staging registers
+    // 16x16-block tiles (f32x16_kernel.py): 16-byte pieces are all-or-nothing (K % 4 == 0); they have no `_pre` variants (the fused
+    // epilogue -- bias view + relu -- and a column stride on C are theirs too)
+    if (kKernels[k0].fam == kF32x16 && a.K % 4 != 0) continue;
+    // the one-chain kernels' fused epilogue has no C read: beta != 0 with a bias / activation only on the laser-order kernels
+    if (fused && !kKernels[k0].exact && a.beta != 0.0f) continue;
+    const int k = kF32Rows.k[ci][lo_row][nt][pre];       // fused prologue: the variants that apply it in the staging registers
     if (k < 0) continue;
     const KernelInfo &ki_ = kKernels[k];
     const int64_t tm = (a.M + ki_.bm - 1) / ki_.bm, tn = (a.N + ki_.bn - 1) / ki_.bn, t = tm * tn;
     if ((double)t * 8.0 * (double)tn >= 4.0e9) continue;    // the in-kernel tile arithmetic's range (fill_sched)
     // below ~5/8 of a round of the larger tiles (3/8 of the 64x64 ones) the compiler-scheduled kernels' slice-parallel and
     // small-problem forms do better
-    if (g_f32_asm < 2 && tile_pin < 0 && t * a.batch < (k0 == tiny ? 3 : 5) * (int64_t)cus / 8) continue;
+    if (g_f32_asm < 2 && tile_pin < 0 && t * a.batch < (ki_.bm == 64 ? 3 : 5) * (int64_t)cus / 8) continue;
     // (laser-order with K <= kc is ONE chain that must stay one chain: cuts only at kc boundaries, or anywhere in one-chain mode;
     // the `_pre` variants run one tile per workgroup)
     const bool may_pipe = !fused && a.beta == 0.0f && a.K % ki_.bk == 0 && a.K >= 3 * ki_.bk && tile_pin < 0 && !pre;
     const Plan p = plan_launch(ki_, t, a.K, a.batch, exact, 512, cu_flops_per_us, (exact || !laser_order) && !pre && tile_pin < 0,
-                               may_pipe ? pipe_gain_us(k) : -1.0, cus);
+                               may_pipe ? ki_.pipe_us : -1.0, cus);
     if (p.time_us < 0.99 * plan.time_us) plan = p, pick = k;   // (near ties go to the larger tile: less L2 traffic)
   }
   if (pick < 0) return hipErrorNotSupported;
@@ -730,11 +813,8 @@ hipError_t choose_gemm_f32_asm(const GemmArgs<float> &a, bool laser_order, int c
 
 hipError_t launch_gemm_f32_asm_core(const GemmArgs<float> &a, bool laser_order, hipStream_t s) {
   if (!g_f32_asm) return hipErrorNotSupported;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
   DeviceModule *m = nullptr;
-  e = get_module(dev, &m);
+  hipError_t e = current_module(&m);
   if (e != hipSuccess) return e;
   int pick = -1;
   Plan plan;
@@ -825,18 +905,8 @@ int asm_plan_f32(int64_t M, int64_t N, int64_t K, int laser_order, int cus, int6
 // hipErrorNotSupported: not this kernel family's class of problem -- the caller takes the compiler-scheduled kernels.
 hipError_t launch_gemm_f32_asm(const GemmArgs<float> &a_in, bool laser_order, hipStream_t s) {
   if (!g_f32_asm) return hipErrorNotSupported;
-  GemmArgs<float> a = a_in;
-  if (a.csC > a.rsC && a.rsC >= 1 && a.batch == 1) {     // columns are the slow direction of C (column-major, with or without a row stride)
-    std::swap(a.M, a.N);
-    std::swap(a.Mext, a.Next);
-    const float *pa = a.A;
-    const int64_t rsa = a.rsA, csa = a.csA;
-    a.A = a.B; a.rsA = a.csB; a.csA = a.rsB;
-    a.B = pa;  a.rsB = csa;   a.csB = rsa;
-    std::swap(a.rsC, a.csC);
-    std::swap(a.rsBias, a.csBias);
-    std::swap(a.preA, a.preB);
-  }
+  // columns are the slow direction of C (column-major, with or without a row stride)
+  GemmArgs<float> a = a_in.csC > a_in.rsC && a_in.rsC >= 1 && a_in.batch == 1 ? transposed_problem(a_in) : a_in;
   const bool packA = a.csA != 1, packB = a.csB != 1 && a.rsB != 1;
   if (!packA && !packB) return launch_gemm_f32_asm_core(a, laser_order, s);
   // packing pays for itself only on products that keep the chip busy for a while; plain / fused-epilogue single problems
@@ -872,89 +942,62 @@ hipError_t launch_gemm_f32_asm(const GemmArgs<float> &a_in, bool laser_order, hi
 }
 
 
-// int32 GEMM mod 2^32 on the int8 matrix cores (gemm_i32_mfma.hip's arithmetic; kernel of laser_amd/asmgen/i8_kernel.py): the
-// packing pass writes tile-major digit planes into `ws` (>= 4 * (rup(M,128) + rup(N,128)) * rup(K,32) bytes), then one launch.
-// Any int32 alpha / beta, unit column stride on C, K <= 8192 (the accumulator groups are never folded).
-hipError_t launch_gemm_i32_asm(const GemmArgs<int32_t> &a, void *ws, hipStream_t s) {
+namespace {
+// int32 / int64 GEMM mod 2^32 / 2^64 on the int8 matrix cores (the arithmetic of gemm_i32_mfma.hip / gemm_i64_mfma.hip; kernels
+// "i32_128x128x32" / "i64_64x64x32" of laser_amd/asmgen/i8_kernel.py): the packing pass writes sizeof(T) tile-major digit planes of
+// each operand into `ws` (>= sizeof(T) * (rup(M, tile) + rup(N, tile)) * rup(K, 32) bytes), then one launch.  Any alpha / beta
+// (wrapping), unit column stride on C, K <= 8192 (the accumulator groups are never folded).
+template <typename T>
+hipError_t launch_gemm_int_asm(const GemmArgs<T> &a, void *ws, hipStream_t s) {
+  constexpr int kern = sizeof(T) == 4 ? kI32Row : kI64Row;
+  constexpr int64_t tile = kKernels[kern].bm, bk = kKernels[kern].bk, limbs = sizeof(T);
+  static_assert(kKernels[kern].bn == tile, "square tiles: one padding of M and N");
   if (!g_i32_asm) return hipErrorNotSupported;
   if (a.batch != 1 || a.csC != 1 || a.rsC < a.N) return hipErrorNotSupported;
   if (a.M < 1 || a.N < 1 || a.K < 1 || a.K > 8192) return hipErrorNotSupported;
-  const int64_t Mpad = (a.M + 127) / 128 * 128, Npad = (a.N + 127) / 128 * 128, Kpad = (a.K + 31) / 32 * 32;
-  const int64_t tiles = (Mpad / 128) * (Npad / 128);
-  if (g_i32_asm < 2 && tiles < current_cus() / 2) return hipErrorNotSupported;      // few tiles: the 8-wave compiler kernel's two workgroups per CU
-  if (((double)(a.M - 1) * (double)a.rsC + (double)a.N) * 4.0 > 2147483648.0 || (double)tiles * 8.0 * (double)(Npad / 128) >= 4.0e9)
-    return hipErrorNotSupported;
-  int8_t *Ap = (int8_t *)ws, *Bp = Ap + 4 * Mpad * Kpad;
-  hipError_t e = launch_limb_planes<int32_t>(Ap, a.A, a.M, a.K, a.rsA, a.csA, Mpad, Kpad, s, 128);
-  if (e != hipSuccess) return e;
-  e = launch_limb_planes<int32_t>(Bp, a.B, a.N, a.K, a.csB, a.rsB, Npad, Kpad, s, 128);
-  if (e != hipSuccess) return e;
-  int dev = 0;
-  e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
   DeviceModule *m = nullptr;
-  e = get_module(dev, &m);
+  hipError_t e = current_module(&m);
   if (e != hipSuccess) return e;
-  const int tiles_m = (int)(Mpad / 128), tiles_n = (int)(Npad / 128), group_m = g_int_group_m;
+  const int64_t Mpad = (a.M + tile - 1) / tile * tile, Npad = (a.N + tile - 1) / tile * tile, Kpad = (a.K + bk - 1) / bk * bk;
+  const int64_t tiles = (Mpad / tile) * (Npad / tile);
+  if (g_i32_asm < 2 && tiles < m->cus / 2) return hipErrorNotSupported;      // few tiles: the 8-wave compiler kernel's two workgroups per CU
+  if (((double)(a.M - 1) * (double)a.rsC + (double)a.N) * (double)limbs > 2147483648.0 || (double)tiles * 8.0 * (double)(Npad / tile) >= 4.0e9)
+    return hipErrorNotSupported;
+  int8_t *Ap = (int8_t *)ws, *Bp = Ap + limbs * Mpad * Kpad;
+  e = launch_limb_planes<T>(Ap, a.A, a.M, a.K, a.rsA, a.csA, Mpad, Kpad, s, (int)tile);
+  if (e != hipSuccess) return e;
+  e = launch_limb_planes<T>(Bp, a.B, a.N, a.K, a.csB, a.rsB, Npad, Kpad, s, (int)tile);
+  if (e != hipSuccess) return e;
+  const int tiles_m = (int)(Mpad / tile), tiles_n = (int)(Npad / tile), group_m = g_int_group_m;
   KernArgs ka;
   zero_conv_fields(ka);
   ka.A = Ap; ka.B = Bp; ka.C = a.C;
   ka.lda = (uint32_t)(Kpad / 32); ka.ldb = 0; ka.ldc = (uint32_t)a.rsC;
   ka.M = (uint32_t)a.M; ka.N = (uint32_t)a.N; ka.K = (uint32_t)Kpad;
-  static_assert(sizeof(float) == sizeof(int32_t), "");
-  std::memcpy(&ka.alpha, &a.alpha, 4);   // int32 alpha / beta travel in the float slots (i8_kernel.py)
-  std::memcpy(&ka.beta, &a.beta, 4);
+  if constexpr (sizeof(T) == 4) {      // int32 alpha / beta travel in the float slots (i8_kernel.py)
+    std::memcpy(&ka.alpha, &a.alpha, 4);
+    std::memcpy(&ka.beta, &a.beta, 4);
+  } else {                             // int64 alpha / beta in the H, W / oW, pH slots (i8_kernel.py KA_ALPHA64 = 72: where the f64 kernels take their doubles)
+    static_assert(offsetof(KernArgs, H) == 72 && offsetof(KernArgs, oW) == 80, "KA_ALPHA64");
+    ka.alpha = 0.0f; ka.beta = 0.0f;
+    std::memcpy(&ka.H, &a.alpha, 8);
+    std::memcpy(&ka.oW, &a.beta, 8);
+  }
   Plan plain;      // one tile per workgroup (the limb kernels are never cut along K: integer sums need no order, K <= 8192 per launch)
   plain.G = tiles;
-  e = launch_planned(m, 20, plain, ka, tiles_m, tiles_n, group_m, 1, 0, s);
-  if (e == hipSuccess) g_last_i32_asm = 21;
+  e = launch_planned(m, kern, plain, ka, tiles_m, tiles_n, group_m, 1, 0, s);
+  if (e == hipSuccess) g_last_i32_asm = 1 + kern;
   return e;
 }
+}  // namespace
 
-// int64 GEMM mod 2^64 (gemm_i64_mfma.hip's arithmetic; kernel "i64_64x64x32" of laser_amd/asmgen/i8_kernel.py): eight tile-major
-// digit planes in `ws` (>= 8 * (rup(M,64) + rup(N,64)) * rup(K,32) bytes), one launch.  Any int64 alpha / beta (wrapping), K <= 8192.
-hipError_t launch_gemm_i64_asm(const GemmArgs<int64_t> &a, void *ws, hipStream_t s) {
-  if (!g_i32_asm) return hipErrorNotSupported;
-  if (a.batch != 1 || a.csC != 1 || a.rsC < a.N) return hipErrorNotSupported;
-  if (a.M < 1 || a.N < 1 || a.K < 1 || a.K > 8192) return hipErrorNotSupported;
-  const int64_t Mpad = (a.M + 63) / 64 * 64, Npad = (a.N + 63) / 64 * 64, Kpad = (a.K + 31) / 32 * 32;
-  const int64_t tiles = (Mpad / 64) * (Npad / 64);
-  if (g_i32_asm < 2 && tiles < current_cus() / 2) return hipErrorNotSupported;
-  if (((double)(a.M - 1) * (double)a.rsC + (double)a.N) * 8.0 > 2147483648.0 || (double)tiles * 8.0 * (double)(Npad / 64) >= 4.0e9)
-    return hipErrorNotSupported;
-  int8_t *Ap = (int8_t *)ws, *Bp = Ap + 8 * Mpad * Kpad;
-  hipError_t e = launch_limb_planes<int64_t>(Ap, a.A, a.M, a.K, a.rsA, a.csA, Mpad, Kpad, s, 64);
-  if (e != hipSuccess) return e;
-  e = launch_limb_planes<int64_t>(Bp, a.B, a.N, a.K, a.csB, a.rsB, Npad, Kpad, s, 64);
-  if (e != hipSuccess) return e;
-  int dev = 0;
-  e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  DeviceModule *m = nullptr;
-  e = get_module(dev, &m);
-  if (e != hipSuccess) return e;
-  const int tiles_m = (int)(Mpad / 64), tiles_n = (int)(Npad / 64), group_m = g_int_group_m;
-  KernArgs ka;
-  zero_conv_fields(ka);
-  ka.A = Ap; ka.B = Bp; ka.C = a.C;
-  ka.lda = (uint32_t)(Kpad / 32); ka.ldb = 0; ka.ldc = (uint32_t)a.rsC;
-  ka.M = (uint32_t)a.M; ka.N = (uint32_t)a.N; ka.K = (uint32_t)Kpad;
-  ka.alpha = 0.0f; ka.beta = 0.0f;
-  // int64 alpha / beta in the H, W / oW, pH slots (i8_kernel.py KA_ALPHA64 = 72: where the f64 kernels take their doubles)
-  static_assert(offsetof(KernArgs, H) == 72 && offsetof(KernArgs, oW) == 80, "KA_ALPHA64");
-  std::memcpy(&ka.H, &a.alpha, 8);
-  std::memcpy(&ka.oW, &a.beta, 8);
-  Plan plain;
-  plain.G = tiles;
-  e = launch_planned(m, 29, plain, ka, tiles_m, tiles_n, group_m, 1, 0, s);
-  if (e == hipSuccess) g_last_i32_asm = 30;
-  return e;
-}
+hipError_t launch_gemm_i32_asm(const GemmArgs<int32_t> &a, void *ws, hipStream_t s) { return launch_gemm_int_asm(a, ws, s); }
+hipError_t launch_gemm_i64_asm(const GemmArgs<int64_t> &a, void *ws, hipStream_t s) { return launch_gemm_int_asm(a, ws, s); }
 
 namespace {
-// float64 twin of launch_gemm_f32_asm_core (kernels of laser_amd/asmgen/f64_kernel.py): row-major A and C, B row-major or passed
-// transposed, any alpha / beta, K even, batches as grid y.
-hipError_t launch_gemm_f64_asm_core(const GemmArgs<double> &a, bool laser_order, hipStream_t s) {
+// float64 twin of choose_gemm_f32_asm (kernels of laser_amd/asmgen/f64_kernel.py): row-major A and C, B row-major or passed
+// transposed, any alpha / beta, K even, batches as grid y.  No device is touched.
+hipError_t choose_gemm_f64_asm(const GemmArgs<double> &a, bool laser_order, int cus, int *pick_out, Plan *plan_out) {
   if (!g_f64_asm) return hipErrorNotSupported;
   if (a.batch < 1 || a.batch > 65535 || a.bias != nullptr || a.act != 0 || a.col0 != 0 || a.done_flags != nullptr) return hipErrorNotSupported;
   if (a.batch > 1 && (a.bsA < 0 || a.bsB < 0 || a.bsC < 0)) return hipErrorNotSupported;
@@ -968,33 +1011,45 @@ hipError_t launch_gemm_f64_asm_core(const GemmArgs<double> &a, bool laser_order,
   if (a.rsA < a.K || ldb < (nt ? a.K : a.N) || a.rsC < a.N || a.K < 2 || a.K % 2 != 0) return hipErrorNotSupported;   // 16-byte pieces = 2 k
   if ((double)a.rsA * 8.0 * 128 >= 4.0e9 || (nt ? (double)ldb * 8.0 * 128 : (double)a.K * (double)ldb * 8.0) >= 4.0e9) return hipErrorNotSupported;
   if (((double)(a.M - 1) * (double)a.rsC + (double)a.N) * 8.0 > 2147483648.0) return hipErrorNotSupported;
-  const bool exact = laser_order && a.K > 256;   // kc = 256 doubles (gemm_tiling.nim:310)
-  const int big = (nt ? 25 : 16) + (exact ? 0 : 1), tiny = (nt ? 27 : 18) + (exact ? 0 : 1);
+  // laser-order: kc = 256 doubles (gemm_tiling.nim:310), and the laser-order rows only where that cuts the chain
+  const bool exact = laser_order && a.K > 256;
   int pick = -1;
   Plan plan;
   const double cu_flops_per_us = 78.6e6 / 256.0;
-  const int cus = current_cus();
-  for (int k : {big, tiny}) {
+  for (const auto &tile_rows : kF64Rows.k) {     // 128x128x16, then 64x64x16
+    const int k = tile_rows[exact][nt];
     if (g_asm_kernel >= 0 && k != g_asm_kernel) continue;
     const KernelInfo &ki_ = kKernels[k];
     const int64_t tm = (a.M + ki_.bm - 1) / ki_.bm, tn = (a.N + ki_.bn - 1) / ki_.bn, t = tm * tn;   // (batches are grid y)
     if ((double)t * 8.0 * (double)tn >= 4.0e9) continue;
-    if (g_f64_asm < 2 && t * a.batch < (k == tiny ? 3 : 5) * (int64_t)cus / 8) continue;
+    if (g_f64_asm < 2 && t * a.batch < (ki_.bm == 64 ? 3 : 5) * (int64_t)cus / 8) continue;
     // (pipelined tile transitions, round 6: beta == 0, whole K-tiles, three or more of them -- f64_kernel.py once())
     const bool may_pipe = a.beta == 0.0 && a.K % ki_.bk == 0 && a.K >= 3 * ki_.bk && a.batch == 1;
     // (the hybrid plan is fitted and tested on the f32 kernels only: not offered here)
-    const Plan p = plan_launch(ki_, t, a.K, a.batch, exact, 256, cu_flops_per_us, exact || !laser_order, may_pipe ? pipe_gain_us(k) : -1.0, cus, false);
+    const Plan p = plan_launch(ki_, t, a.K, a.batch, exact, 256, cu_flops_per_us, exact || !laser_order, may_pipe ? ki_.pipe_us : -1.0, cus, false);
     if (p.time_us < 0.99 * plan.time_us) plan = p, pick = k;
   }
   if (pick < 0) return hipErrorNotSupported;
+  *pick_out = pick;
+  *plan_out = plan;
+  return hipSuccess;
+}
+
+hipError_t launch_gemm_f64_asm_core(const GemmArgs<double> &a, bool laser_order, hipStream_t s) {
+  if (!g_f64_asm) return hipErrorNotSupported;
+  DeviceModule *m = nullptr;
+  hipError_t e = current_module(&m);
+  if (e != hipSuccess) return e;
+  int pick = -1;
+  Plan plan;
+  e = choose_gemm_f64_asm(a, laser_order, m->cus, &pick, &plan);
+  if (e != hipSuccess) return e;
   const KernelInfo &ki = kKernels[pick];
   const int tiles_m = (int)((a.M + ki.bm - 1) / ki.bm), tiles_n = (int)((a.N + ki.bn - 1) / ki.bn);
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  DeviceModule *m = nullptr;
-  e = get_module(dev, &m);
-  if (e != hipSuccess) return e;
+  const bool nt = a.csB != 1 && a.rsB == 1;
+  const int64_t ldb = nt ? a.csB : a.rsB;
+  const bool exact = laser_order && a.K > 256;
+  const double cu_flops_per_us = 78.6e6 / 256.0;
   const int group_m = 8;
   KernArgs ka;
   zero_conv_fields(ka);
@@ -1017,7 +1072,7 @@ hipError_t launch_gemm_f64_asm_core(const GemmArgs<double> &a, bool laser_order,
   ka.bsC_bytes = a.batch > 1 ? (uint64_t)a.bsC * 8 : 0;
   e = launch_planned(m, pick, plan, ka, tiles_m, tiles_n, group_m, a.batch, (size_t)ki.bm * ki.bn * 8, s);
   if (e == hipErrorNotSupported && plan.persistent) {
-    Plan plain = plan_launch(ki, (int64_t)tiles_m * tiles_n, a.K, a.batch, exact, 256, cu_flops_per_us, false, -1.0, cus);
+    Plan plain = plan_launch(ki, (int64_t)tiles_m * tiles_n, a.K, a.batch, exact, 256, cu_flops_per_us, false, -1.0, m->cus);
     e = launch_planned(m, pick, plain, ka, tiles_m, tiles_n, group_m, a.batch, (size_t)ki.bm * ki.bn * 8, s);
   }
   if (e == hipSuccess) g_last_f64_asm = 1 + pick;
@@ -1029,16 +1084,7 @@ hipError_t launch_gemm_f64_asm_core(const GemmArgs<double> &a, bool laser_order,
 // launch_gemm_f32_asm; other strides (a column stride on C, gathers) stay on the compiler-scheduled kernels.
 hipError_t launch_gemm_f64_asm(const GemmArgs<double> &a_in, bool laser_order, hipStream_t s) {
   if (!g_f64_asm) return hipErrorNotSupported;
-  GemmArgs<double> a = a_in;
-  if (a.csC != 1 && a.rsC == 1 && a.batch == 1 && a.bias == nullptr) {
-    std::swap(a.M, a.N);
-    std::swap(a.Mext, a.Next);
-    const double *pa = a.A;
-    const int64_t rsa = a.rsA, csa = a.csA;
-    a.A = a.B; a.rsA = a.csB; a.csA = a.rsB;
-    a.B = pa;  a.rsB = csa;   a.csB = rsa;
-    std::swap(a.rsC, a.csC);
-  }
+  GemmArgs<double> a = a_in.csC != 1 && a_in.rsC == 1 && a_in.batch == 1 && a_in.bias == nullptr ? transposed_problem(a_in) : a_in;
   if (a.csA == 1) return launch_gemm_f64_asm_core(a, laser_order, s);
   if (a.rsA != 1 || a.batch != 1 || a.Mext != a.M || a.Next != a.N || a.Kext != a.K || a.col0 != 0 || a.done_flags != nullptr || a.csA < a.M) return hipErrorNotSupported;
   if ((double)a.M * (double)a.N * (double)a.K < 1024.0 * 1024.0 * 1024.0 || a.K < 64 || a.K % 2 != 0) return hipErrorNotSupported;
@@ -1056,14 +1102,15 @@ hipError_t launch_gemm_f64_asm(const GemmArgs<double> &a_in, bool laser_order, h
 }
 
 namespace {
-// what the assembly convolution launcher makes of a call: the kernel (kKernels index), the padded K, the geometry and the tile grid
+// what the assembly convolution launcher makes of a call: the kernel (kKernels index) and its unit walker, the padded K, the geometry
+// and the tile grid
 struct ConvClass {
-  int pick = -1, tiles_m = 0, tiles_n = 0;
+  int pick = -1, walker = -1, tiles_m = 0, tiles_n = 0;
   int64_t kH = 0, kW = 0, sH = 0, sW = 0, taps = 0, oW = 0, oH = 0, npix = 0, Cin = 0, Kp = 0, tiles = 0;
   bool exact = false;
 };
-// hipErrorNotSupported: not this launcher's class (launch_conv_f32_asm's comment); no device work
-hipError_t conv_asm_classify(const GemmArgs<float> &a, bool laser_order, ConvClass &cc) {
+// hipErrorNotSupported: not this launcher's class (launch_conv_f32_asm's comment) on a device of `cus` compute units; no device work
+hipError_t conv_asm_classify(const GemmArgs<float> &a, bool laser_order, int cus, ConvClass &cc) {
   if (!g_f32_asm) return hipErrorNotSupported;
   if (a.col0 != 0 || a.cs_imgs != 0) return hipErrorNotSupported;
   if (a.alpha != 1.0f || a.beta != 0.0f) return hipErrorNotSupported;
@@ -1087,22 +1134,22 @@ hipError_t conv_asm_classify(const GemmArgs<float> &a, bool laser_order, ConvCla
       (double)Kp * (double)taps >= 4.0e9)      // (the in-kernel k / taps: x * d < 2^32)
     return hipErrorNotSupported;
   const bool exact = laser_order && a.K > 512;
+  const bool lo_row = exact || a.K <= 512;   // (as in choose_gemm_f32_asm)
   // rows of the tile by the number of output channels: the smallest padded row count, weighted by what each tile reaches (the
   // 256-row tile's tap table ends at 31 taps)
-  int pick = -1;
+  int pick = -1, walker = -1;
   double best_cost = 1e300;
-  for (int base : {10, 21, 23}) {
-    if (base == 10 && taps > 31) continue;
-    const KernelInfo &kc = kKernels[base];
+  for (int i = 0; i < 3; i++) {     // 256, 128, 64 rows
+    const KernelInfo &kc = kKernels[kConvRows.k[i][lo_row]];
+    if (kc.bm == 256 && taps > 31) continue;
     const double cost = (double)((a.M + kc.bm - 1) / kc.bm * kc.bm) / kc.eff;
-    if (cost < 0.99 * best_cost) best_cost = cost, pick = base;
+    if (cost < 0.99 * best_cost) best_cost = cost, pick = kConvRows.k[i][lo_row], walker = kConvRows.walker[i][lo_row];
   }
-  pick += (exact || a.K <= 512 ? 0 : 1);
   const KernelInfo &ki = kKernels[pick];
   const int tiles_m = (int)((a.M + ki.bm - 1) / ki.bm), tiles_n = (int)((a.N + ki.bn - 1) / ki.bn);
   const int64_t tiles = (int64_t)tiles_m * tiles_n;
   if ((double)tiles * (double)tiles >= 4.0e9) return hipErrorNotSupported;   // the in-kernel tile arithmetic's range (fill_sched)
-  if (g_f32_asm < 2 && tiles * a.batch < 5 * (int64_t)current_cus() / 8) return hipErrorNotSupported;
+  if (g_f32_asm < 2 && tiles * a.batch < 5 * (int64_t)cus / 8) return hipErrorNotSupported;
   // a 256-row tile that is mostly padding (few output channels) loses to the compiler-scheduled 128 / 64-row tiles
   if (g_f32_asm < 2 && (double)a.M * (double)a.N < 0.75 * (double)tiles * ki.bm * ki.bn) return hipErrorNotSupported;
   if ((double)npix * (double)oW >= 4.0e9) return hipErrorNotSupported;
@@ -1110,10 +1157,10 @@ hipError_t conv_asm_classify(const GemmArgs<float> &a, bool laser_order, ConvCla
   // whatever the count; where that leaves a fifth of the chip idle the compiler-scheduled kernels' smaller tiles are ahead by 6 - 10 %
   // (profiles/r06/conv_m64_ab_w.jsonl: 800 units = 3.125 per CU, 320 units = 1.25 per CU), elsewhere behind by 4 - 25 %
   if (g_f32_asm < 2 && ki.bm == 64) {
-    const int64_t cus = current_cus(), units_ = tiles * a.batch, per_cu = (units_ + cus - 1) / cus;
+    const int64_t units_ = tiles * a.batch, per_cu = (units_ + cus - 1) / cus;
     if ((double)units_ < 0.8 * (double)(per_cu * cus)) return hipErrorNotSupported;
   }
-  cc.pick = pick; cc.tiles_m = tiles_m; cc.tiles_n = tiles_n; cc.tiles = tiles;
+  cc.pick = pick; cc.walker = walker; cc.tiles_m = tiles_m; cc.tiles_n = tiles_n; cc.tiles = tiles;
   cc.kH = kH; cc.kW = kW; cc.sH = sH; cc.sW = sW; cc.taps = taps; cc.oW = oW; cc.oH = oH; cc.npix = npix; cc.Cin = Cin; cc.Kp = Kp;
   cc.exact = exact;
   return hipSuccess;
@@ -1129,8 +1176,9 @@ hipError_t conv_asm_classify(const GemmArgs<float> &a, bool laser_order, ConvCla
 // Returns -1: not the assembly launcher's class (the caller keeps its own plan), 0: one launch, > 0: the cut.
 int64_t conv_asm_plan_cut(const GemmArgs<float> &a_in, bool laser_order) {
   GemmArgs<float> a = a_in;
-  const int cus = current_cus();
-  if (cus < 8) return -1;
+  DeviceModule *m = nullptr;
+  if (current_module(&m) != hipSuccess) return -1;
+  const int cus = m->cus;
   const double cu_rate = 157.3e12 / 256.0;
   const auto main_us = [&](const ConvClass &cc) {
     const KernelInfo &ki = kKernels[cc.pick];
@@ -1141,12 +1189,12 @@ int64_t conv_asm_plan_cut(const GemmArgs<float> &a_in, bool laser_order) {
   double best = 1e300;
   int64_t best_cut = -1;
   ConvClass cc;
-  if (conv_asm_classify(a, laser_order, cc) == hipSuccess) best = main_us(cc), best_cut = 0;
+  if (conv_asm_classify(a, laser_order, cus, cc) == hipSuccess) best = main_us(cc), best_cut = 0;
   const int64_t npix = a.N, kfull = npix / 128;
   for (int64_t k = kfull; k >= 1 && k >= kfull - 12; k--) {
     if (k * 128 == npix) continue;
     a.N = k * 128;
-    if (conv_asm_classify(a, laser_order, cc) != hipSuccess) continue;
+    if (conv_asm_classify(a, laser_order, cus, cc) != hipSuccess) continue;
     // (the 64-row tile with a short reduction: a cut launch loses 5 - 10 % to one launch of the compiler-scheduled kernels, K = 288 / 864;
     // from K = 1152 on it is 5 - 9 % ahead: profiles/r06/conv_m64_ab_x.jsonl)
     if (kKernels[cc.pick].bm == 64 && cc.Kp < 1024) continue;
@@ -1166,18 +1214,16 @@ int64_t conv_asm_plan_cut(const GemmArgs<float> &a_in, bool laser_order) {
 // this kernel's class.
 hipError_t launch_conv_f32_asm(const GemmArgs<float> &a_in, bool laser_order, hipStream_t s) {
   GemmArgs<float> a = a_in;
+  DeviceModule *m = nullptr;
+  hipError_t e = current_module(&m);
+  if (e != hipSuccess) return e;
   ConvClass cc;
-  if (const hipError_t ce = conv_asm_classify(a, laser_order, cc); ce != hipSuccess) return ce;
+  e = conv_asm_classify(a, laser_order, m->cus, cc);
+  if (e != hipSuccess) return e;
   int pick = cc.pick;
   const KernelInfo &ki = kKernels[pick];
   const int tiles_m = cc.tiles_m, tiles_n = cc.tiles_n;
   const int64_t kH = cc.kH, kW = cc.kW, sH = cc.sH, sW = cc.sW, taps = cc.taps, oW = cc.oW, npix = cc.npix, Cin = cc.Cin, Kp = cc.Kp, tiles = cc.tiles;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  DeviceModule *m = nullptr;
-  e = get_module(dev, &m);
-  if (e != hipSuccess) return e;
   // the filter matrix as dense rows of Kp elements: as given when it already is (the usual case: K % 4 == 0, contiguous), else one
   // small packing pass into stream-ordered scratch (C_out x K floats: the first layer of a network has C_in = 3)
   float *packed = nullptr;
@@ -1236,7 +1282,7 @@ hipError_t launch_conv_f32_asm(const GemmArgs<float> &a_in, bool laser_order, hi
   if (can_walk && ((g_conv_walk == 1 && units > slots) || (g_conv_walk >= 2 && units >= 2))) {
     walk_G = std::min(slots, units);
     if (g_conv_walk >= 3) walk_G = std::min<int64_t>(g_conv_walk, units - 1);       // (tests: a forced workgroup count)
-    pick = (pick == 10 || pick == 11 ? 66 + (pick - 10) : 68 + (pick - 21));
+    pick = cc.walker;
   }
   e = launch_planned(m, pick, plain, ka, tiles_m, tiles_n, group_m, a.batch, 0, s, walk_G);
   if (packed) {

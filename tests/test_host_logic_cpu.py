@@ -154,7 +154,7 @@ def test_dma_fed_lds_layouts_are_bank_conflict_free_in_the_model():
         assert _b128_extra_cycles(swz) == 0, ks
 
 
-def test_bench_kernel_names_match_the_launcher_table():
+def test_bench_kernel_names_match_the_kernel_table():
     """bench.py names the kernel of its `roofline` object from laser_hip_get_option("last_f32_asm") = 1 + index into kKernels
     (gemm_f32_asm.cpp): the two tables must list the same symbols in the same order, and every symbol must be one the Makefile
     assembles into the embedded code object."""
@@ -162,7 +162,8 @@ def test_bench_kernel_names_match_the_launcher_table():
     import importlib.util
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = open(os.path.join(root, "laser_amd", "csrc", "gemm_f32_asm.cpp")).read()
-    table = src[src.index("const KernelInfo kKernels[kNumKernels] = {"):src.index("// plain kernel -> its `_pre` variant")]
+    start = src.index("KernelInfo kKernels[kNumKernels] = {")
+    table = src[start:src.index("\n};", start)]
     symbols = re.findall(r'\{"(lh_[a-z0-9_x]+)"', table)
     assert len(symbols) == int(re.search(r"constexpr int kNumKernels = (\d+);", src).group(1))
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
@@ -247,3 +248,39 @@ def test_launch_plans_scale_with_the_device_cu_count():
     assert la.plan_f32(512, 512, 512, True, 32)["kernel"] != 0
     with pytest.raises(la.LaserHipError):
         la.plan_f32(0, 4, 4)
+
+
+def test_tile_class_option_picks_the_class_rows():
+    """Option asm_tile pins a tile class of the f32 GEMM kernels; the launcher finds the class's row in kKernels by its attributes
+    (tile class, laser-order, B transposed, fused prologue).  The class -> kernel map, per shape and mode, as the launcher has always
+    made it: a row is laser-order where laser-order mode cuts the chain (K > 512) or where there is one chain anyway (K <= 512);
+    class 1 (256x128 one chain) has no laser-order row and gives way to class 0."""
+    import importlib.util
+    import laser_amd as la
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    shapes = [(2048, 2048, 2048), (1920, 1920, 300), (4096, 4096, 4096)]
+    # class -> (laser-order row, one-chain row)
+    rows = {0: ("lh_f32_exact_256x128x32", "lh_f32_fast_256x256x16"),
+            1: ("lh_f32_exact_256x128x32", "lh_f32_fast_256x128x32"),
+            2: ("lh_f32_exact_128x128x16", "lh_f32_fast_128x128x16"),
+            3: ("lh_f32_exact_128x128x32", "lh_f32_fast_128x128x32"),
+            4: ("lh_f32_exact_64x64x32", "lh_f32_fast_64x64x32"),
+            5: ("lh_f32x16_exact_96x96x32", "lh_f32x16_fast_96x96x32"),
+            6: ("lh_f32x16_exact_160x96x32", "lh_f32x16_fast_160x96x32"),
+            7: ("lh_f32x16_exact_128x96x32", "lh_f32x16_fast_128x96x32"),
+            8: ("lh_f32x16_exact_192x96x32", "lh_f32x16_fast_192x96x32"),
+            9: ("lh_f32x16_exact_160x160x32", "lh_f32x16_fast_160x160x32")}
+    try:
+        for cls, (lo_row, fast_row) in rows.items():
+            la.set_option("asm_tile", cls)
+            for M, N, K in shapes:
+                for laser in (True, False):
+                    k = la.plan_f32(M, N, K, laser, 256)["kernel"]
+                    assert k != 0, (cls, M, N, K, laser)
+                    want = lo_row if laser or K <= 512 else fast_row
+                    assert bench.ASM_KERNEL_SYMBOLS[k - 1] == want, (cls, M, N, K, laser)
+    finally:
+        la.set_option("asm_tile", -1)
