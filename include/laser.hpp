@@ -36,25 +36,41 @@ struct Strides { int64_t h, w; };
   else if constexpr (std::is_same_v<T, int32_t>) { CALL_I32; }                            \
   else { static_assert(std::is_same_v<T, int64_t>, "float, double, int32_t or int64_t"); CALL_I64; }
 
+// The GEMM entry points take every integer type of 1, 2, 4 or 8 bytes, signed or not (gemm.nim:184-248: every SomeNumber):
+// arithmetic mod 2^n, so each is the signed entry point of its width on the same bits.  CALL(SFX, E, S) is expanded with the
+// suffix, the element type the pointers are cast to and the scalar type alpha / beta are passed as (int32_t for i8 / i16).
+#define LASER_GEMM_DISPATCH(T, CALL)                                                                                    \
+  if constexpr (std::is_same_v<T, float>) { CALL(f32, float, float); }                                                 \
+  else if constexpr (std::is_same_v<T, double>) { CALL(f64, double, double); }                                         \
+  else {                                                                                                                \
+    static_assert(std::is_integral_v<T> && !std::is_same_v<T, bool>, "float, double or an integer type");             \
+    if constexpr (sizeof(T) == 1) { CALL(i8, int8_t, int32_t); }                                                       \
+    else if constexpr (sizeof(T) == 2) { CALL(i16, int16_t, int32_t); }                                                \
+    else if constexpr (sizeof(T) == 4) { CALL(i32, int32_t, int32_t); }                                                \
+    else { CALL(i64, int64_t, int64_t); }                                                                               \
+  }
+
 // gemm.nim:184-193
 template <typename T>
 void gemm_strided(int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rowStrideA, int64_t colStrideA,
                   const T *B, int64_t rowStrideB, int64_t colStrideB, T beta, T *C, int64_t rowStrideC,
                   int64_t colStrideC) {
-#define LASER_ARGS M, N, K, alpha, A, rowStrideA, colStrideA, B, rowStrideB, colStrideB, beta, C, rowStrideC, colStrideC
-  LASER_DISPATCH(T, check(laser_hip_gemm_strided_f32(LASER_ARGS)), check(laser_hip_gemm_strided_f64(LASER_ARGS)),
-                 check(laser_hip_gemm_strided_i32(LASER_ARGS)), check(laser_hip_gemm_strided_i64(LASER_ARGS)))
-#undef LASER_ARGS
+#define LASER_CALL(SFX, E, S)                                                                                             \
+  check(laser_hip_gemm_strided_##SFX(M, N, K, (S)(E)alpha, (const E *)A, rowStrideA, colStrideA, (const E *)B, rowStrideB, \
+                                     colStrideB, (S)(E)beta, (E *)C, rowStrideC, colStrideC))
+  LASER_GEMM_DISPATCH(T, LASER_CALL)
+#undef LASER_CALL
 }
 
 // device-resident flavour (device pointers, hipStream_t as void*)
 template <typename T>
 void gemm_strided_dev(int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA, int64_t csA, const T *B,
                       int64_t rsB, int64_t csB, T beta, T *C, int64_t rsC, int64_t csC, void *stream = nullptr) {
-#define LASER_ARGS M, N, K, alpha, A, rsA, csA, B, rsB, csB, beta, C, rsC, csC, stream
-  LASER_DISPATCH(T, check(laser_hip_gemm_strided_f32_dev(LASER_ARGS)), check(laser_hip_gemm_strided_f64_dev(LASER_ARGS)),
-                 check(laser_hip_gemm_strided_i32_dev(LASER_ARGS)), check(laser_hip_gemm_strided_i64_dev(LASER_ARGS)))
-#undef LASER_ARGS
+#define LASER_CALL(SFX, E, S)                                                                                     \
+  check(laser_hip_gemm_strided_##SFX##_dev(M, N, K, (S)(E)alpha, (const E *)A, rsA, csA, (const E *)B, rsB, csB, (S)(E)beta, \
+                                           (E *)C, rsC, csC, stream))
+  LASER_GEMM_DISPATCH(T, LASER_CALL)
+#undef LASER_CALL
 }
 
 // Fused epilogue -- planned by the reference (README.md:238-242; TODO gemm.nim:196), not present in it:
@@ -77,37 +93,37 @@ void gemm_strided_fused(int64_t M, int64_t N, int64_t K, T alpha, const T *A, in
 // gemm_prepacked.nim:76-85, :157-167
 template <typename T>
 int64_t gemm_prepackB_mem_required(int64_t M, int64_t N, int64_t K) {
-  LASER_DISPATCH(T, return laser_hip_gemm_prepackB_mem_required_f32(M, N, K), return laser_hip_gemm_prepackB_mem_required_f64(M, N, K),
-                 return laser_hip_gemm_prepackB_mem_required_i32(M, N, K), return laser_hip_gemm_prepackB_mem_required_i64(M, N, K))
+#define LASER_CALL(SFX, E, S) return laser_hip_gemm_prepackB_mem_required_##SFX(M, N, K)
+  LASER_GEMM_DISPATCH(T, LASER_CALL)
+#undef LASER_CALL
 }
 template <typename T>
 int64_t gemm_prepackA_mem_required(int64_t M, int64_t N, int64_t K) {
-  LASER_DISPATCH(T, return laser_hip_gemm_prepackA_mem_required_f32(M, N, K), return laser_hip_gemm_prepackA_mem_required_f64(M, N, K),
-                 return laser_hip_gemm_prepackA_mem_required_i32(M, N, K), return laser_hip_gemm_prepackA_mem_required_i64(M, N, K))
+#define LASER_CALL(SFX, E, S) return laser_hip_gemm_prepackA_mem_required_##SFX(M, N, K)
+  LASER_GEMM_DISPATCH(T, LASER_CALL)
+#undef LASER_CALL
 }
 // gemm_prepacked.nim:111-135, :193-218 (dst must be 64-byte aligned, like the reference's doAssert)
 template <typename T>
 void gemm_prepackB(void *dst_packedB, int64_t M, int64_t N, int64_t K, const T *src_B, int64_t rowStrideB, int64_t colStrideB) {
-  LASER_DISPATCH(T, check(laser_hip_gemm_prepackB_f32(dst_packedB, M, N, K, src_B, rowStrideB, colStrideB)),
-                 check(laser_hip_gemm_prepackB_f64(dst_packedB, M, N, K, src_B, rowStrideB, colStrideB)),
-                 check(laser_hip_gemm_prepackB_i32(dst_packedB, M, N, K, src_B, rowStrideB, colStrideB)),
-                 check(laser_hip_gemm_prepackB_i64(dst_packedB, M, N, K, src_B, rowStrideB, colStrideB)))
+#define LASER_CALL(SFX, E, S) check(laser_hip_gemm_prepackB_##SFX(dst_packedB, M, N, K, (const E *)src_B, rowStrideB, colStrideB))
+  LASER_GEMM_DISPATCH(T, LASER_CALL)
+#undef LASER_CALL
 }
 template <typename T>
 void gemm_prepackA(void *dst_packedA, int64_t M, int64_t N, int64_t K, const T *src_A, int64_t rowStrideA, int64_t colStrideA) {
-  LASER_DISPATCH(T, check(laser_hip_gemm_prepackA_f32(dst_packedA, M, N, K, src_A, rowStrideA, colStrideA)),
-                 check(laser_hip_gemm_prepackA_f64(dst_packedA, M, N, K, src_A, rowStrideA, colStrideA)),
-                 check(laser_hip_gemm_prepackA_i32(dst_packedA, M, N, K, src_A, rowStrideA, colStrideA)),
-                 check(laser_hip_gemm_prepackA_i64(dst_packedA, M, N, K, src_A, rowStrideA, colStrideA)))
+#define LASER_CALL(SFX, E, S) check(laser_hip_gemm_prepackA_##SFX(dst_packedA, M, N, K, (const E *)src_A, rowStrideA, colStrideA))
+  LASER_GEMM_DISPATCH(T, LASER_CALL)
+#undef LASER_CALL
 }
 // gemm_prepacked.nim:275-292
 template <typename T>
 void gemm_packed(int64_t M, int64_t N, int64_t K, T alpha, const void *packedA, const void *packedB, T beta, T *C,
                  int64_t rowStrideC, int64_t colStrideC) {
-  LASER_DISPATCH(T, check(laser_hip_gemm_packed_f32(M, N, K, alpha, packedA, packedB, beta, C, rowStrideC, colStrideC)),
-                 check(laser_hip_gemm_packed_f64(M, N, K, alpha, packedA, packedB, beta, C, rowStrideC, colStrideC)),
-                 check(laser_hip_gemm_packed_i32(M, N, K, alpha, packedA, packedB, beta, C, rowStrideC, colStrideC)),
-                 check(laser_hip_gemm_packed_i64(M, N, K, alpha, packedA, packedB, beta, C, rowStrideC, colStrideC)))
+#define LASER_CALL(SFX, E, S) \
+  check(laser_hip_gemm_packed_##SFX(M, N, K, (S)(E)alpha, packedA, packedB, (S)(E)beta, (E *)C, rowStrideC, colStrideC))
+  LASER_GEMM_DISPATCH(T, LASER_CALL)
+#undef LASER_CALL
 }
 inline void gemm_prepack_release(void *packed) { check(laser_hip_gemm_prepack_release(packed)); }
 
@@ -345,4 +361,5 @@ void gemm(T alpha, const Tensor<T> &A, const Tensor<T> &B, T beta, Tensor<T> &C)
 }
 
 #undef LASER_DISPATCH
+#undef LASER_GEMM_DISPATCH
 }  // namespace laser

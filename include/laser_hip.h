@@ -55,7 +55,7 @@ const char *laser_hip_version(void);
 /* Incremented whenever an exported prototype, an option name or an operation code changes incompatibly (round 3 changed the
  * alpha / beta types of map_strided and collapsed the setters into laser_hip_set_option: 2; round 4 only added names: still 2).
  * A caller built against another header should refuse to run. */
-#define LASER_HIP_ABI_VERSION 2
+#define LASER_HIP_ABI_VERSION 3
 int laser_hip_abi_version(void);
 int laser_hip_device_count(void);
 /* Diagnostics (touches no device): the kernel and launch plan the float32 launcher takes for a dense row-major M x N x K product on a
@@ -92,6 +92,7 @@ int laser_hip_f32_config_count(void);
  *   "int_group_m"      [4] tile rows per raster group of those kernels' workgroup -> tile map (1 .. 64; a scheduling knob: same results)
  *   "f64_mfma" "i32_mfma" "i64_mfma"  [1] matrix-core kernels (f64 MFMA; int8-limb decomposition for the integers, the
  *                          reference's integer micro-kernels: gemm_ukernel_avx512.nim:40-74); 0 = the VALU kernels
+ *   "narrow_mfma"      [1] int8 / int16 GEMMs on the int8 matrix cores (one / two digit planes); 0 = the VALU / streaming kernels
  *   "conv_implicit"    [1] im2col fused into the GEMM's B loader; 0 = explicit im2col workspace + batched GEMM, the
  *                          reference's literal structure (conv2d_im2col.nim:126-166)
  *   "conv_patch"       [1] implicit conv reads B from an LDS-resident input patch when it fits; 0 = per-element gather
@@ -149,6 +150,7 @@ int laser_hip_f32_config_count(void);
  * laser_hip_get_option reads any of them back, plus the read-only diagnostics of the last launch:
  *   "last_f32_config"  tile configuration index (-1 none yet, -2 small-matrix kernel, -3 direct small-channel conv kernel)
  *   "last_f32_asm" / "last_f64_asm" / "last_i32_asm"  0 = compiler-scheduled kernel, else 1 + index of the assembly kernel (gemm_f32_asm.cpp)
+ *   "last_narrow_mfma" 1 = the last int8 / int16 GEMM ran on the matrix cores, 0 = a VALU / streaming kernel
  *   "last_asm_wgs" / "last_asm_slices"  workgroups and K slices per tile of the last assembly launch (slices 1 = tiles never cut)
  *   "last_asm_rem"     tiles the last assembly launch left to the K-cut launch of a hybrid plan (0: one launch)
  *   "last_asm_group_m"  its raster group height in tile rows (which tiles share an XCD's L2), + 65536 when the workgroup ids were
@@ -230,6 +232,48 @@ LASER_HIP_DECL_PACK(f64, double)
 LASER_HIP_DECL_PACK(i32, int32_t)
 LASER_HIP_DECL_PACK(i64, int64_t)
 #undef LASER_HIP_DECL_PACK
+
+/* ---- gemm_strided / pre-packed GEMM for int8 and int16 (gemm.nim:184-248: every SomeNumber) -----------------
+ * The same entry points as above for the narrow integer types, uint8 / uint16 on the same bits (two's-complement
+ * wrap-around mod 2^8 / 2^16, the reference's gemm.nim:239 treatment of int32 / uint32).  alpha and beta travel as
+ * int32_t and are reduced mod 2^8 / 2^16.  No _sharded and no fused-epilogue (_ex) form. */
+#define LASER_HIP_DECL_GEMM_NARROW(SFX, T)                                                        \
+  int laser_hip_gemm_strided_##SFX(int64_t M, int64_t N, int64_t K, int32_t alpha, const T *A,    \
+                                   int64_t rowStrideA, int64_t colStrideA, const T *B,            \
+                                   int64_t rowStrideB, int64_t colStrideB, int32_t beta, T *C,    \
+                                   int64_t rowStrideC, int64_t colStrideC);                       \
+  int laser_hip_gemm_strided_##SFX##_dev(int64_t M, int64_t N, int64_t K, int32_t alpha,          \
+                                         const T *dA, int64_t rowStrideA, int64_t colStrideA,     \
+                                         const T *dB, int64_t rowStrideB, int64_t colStrideB,     \
+                                         int32_t beta, T *dC, int64_t rowStrideC,                 \
+                                         int64_t colStrideC, void *stream);                       \
+  int laser_hip_gemm_strided_batched_##SFX##_dev(                                                 \
+      int64_t batch, int64_t M, int64_t N, int64_t K, int32_t alpha, const T *dA,                 \
+      int64_t rowStrideA, int64_t colStrideA, int64_t batchStrideA, const T *dB,                  \
+      int64_t rowStrideB, int64_t colStrideB, int64_t batchStrideB, int32_t beta, T *dC,          \
+      int64_t rowStrideC, int64_t colStrideC, int64_t batchStrideC, void *stream);                \
+  int64_t laser_hip_gemm_prepackA_mem_required_##SFX(int64_t M, int64_t N, int64_t K);            \
+  int64_t laser_hip_gemm_prepackB_mem_required_##SFX(int64_t M, int64_t N, int64_t K);            \
+  int laser_hip_gemm_prepackA_##SFX(void *dst_packedA, int64_t M, int64_t N, int64_t K,           \
+                                    const T *src_A, int64_t rowStrideA, int64_t colStrideA);      \
+  int laser_hip_gemm_prepackB_##SFX(void *dst_packedB, int64_t M, int64_t N, int64_t K,           \
+                                    const T *src_B, int64_t rowStrideB, int64_t colStrideB);      \
+  int laser_hip_gemm_packed_##SFX(int64_t M, int64_t N, int64_t K, int32_t alpha,                 \
+                                  const void *packedA, const void *packedB, int32_t beta, T *C,   \
+                                  int64_t rowStrideC, int64_t colStrideC);                        \
+  int laser_hip_gemm_prepackA_##SFX##_dev(void *d_dst, int64_t M, int64_t N, int64_t K,           \
+                                          const T *dA, int64_t rowStrideA, int64_t colStrideA,    \
+                                          void *stream);                                          \
+  int laser_hip_gemm_prepackB_##SFX##_dev(void *d_dst, int64_t M, int64_t N, int64_t K,           \
+                                          const T *dB, int64_t rowStrideB, int64_t colStrideB,    \
+                                          void *stream);                                          \
+  int laser_hip_gemm_packed_##SFX##_dev(int64_t M, int64_t N, int64_t K, int32_t alpha,           \
+                                        const void *d_packedA, const void *d_packedB,             \
+                                        int32_t beta, T *dC, int64_t rowStrideC,                  \
+                                        int64_t colStrideC, void *stream);
+LASER_HIP_DECL_GEMM_NARROW(i8, int8_t)
+LASER_HIP_DECL_GEMM_NARROW(i16, int16_t)
+#undef LASER_HIP_DECL_GEMM_NARROW
 int laser_hip_gemm_prepack_release(void *packed);
 
 /* ---- physical transposes -- laser/primitives/swapaxes.nim:16-112 --------------------------------

@@ -5,7 +5,7 @@ There is NO fallback: if the shared library is missing or the GPU is not a gfx95
 import ctypes as C
 import os
 
-ABI_VERSION = 2   # include/laser_hip.h LASER_HIP_ABI_VERSION this mirror was written against
+ABI_VERSION = 3   # include/laser_hip.h LASER_HIP_ABI_VERSION this mirror was written against
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "liblaser_hip.so")
@@ -14,6 +14,8 @@ OK, E_INVALID, E_HIP, E_NODEVICE, E_HANDLE = 0, 1, 2, 3, 4
 F32_LASER_ORDER, F32_FAST = 0, 1
 
 _CT = {"f32": C.c_float, "f64": C.c_double, "i32": C.c_int32, "i64": C.c_int64}
+# int8 / int16 GEMM entry points (no _sharded or map_strided form): alpha and beta travel as int32_t
+_NARROW = ("i8", "i16")
 
 
 class LaserHipError(RuntimeError):
@@ -49,7 +51,7 @@ def lib():
     L.laser_hip_get_option.argtypes = [C.c_char_p, C.POINTER(i64)]
     L.laser_hip_f32_config_name.argtypes = [ci]
     L.laser_hip_f32_config_name.restype = C.c_char_p
-    for sfx, ct in _CT.items():
+    for sfx, ct in list(_CT.items()) + [(n, C.c_int32) for n in _NARROW]:
         g = [i64, i64, i64, ct, vp, i64, i64, vp, i64, i64, ct, vp, i64, i64]
         getattr(L, f"laser_hip_gemm_strided_{sfx}").argtypes = g
         getattr(L, f"laser_hip_gemm_strided_{sfx}_dev").argtypes = g + [vp]
@@ -63,6 +65,8 @@ def lib():
             getattr(L, f"laser_hip_gemm_prepack{ab}_{sfx}_dev").argtypes = [vp, i64, i64, i64, vp, i64, i64, vp]
         getattr(L, f"laser_hip_gemm_packed_{sfx}").argtypes = [i64, i64, i64, ct, vp, vp, ct, vp, i64, i64]
         getattr(L, f"laser_hip_gemm_packed_{sfx}_dev").argtypes = [i64, i64, i64, ct, vp, vp, ct, vp, i64, i64, vp]
+        if sfx in _NARROW:
+            continue
         pp = C.POINTER(vp)  # table of per-device pointers
         getattr(L, f"laser_hip_gemm_strided_{sfx}_sharded").argtypes = [ci, C.POINTER(ci)] + g
         getattr(L, f"laser_hip_gemm_strided_{sfx}_sharded_dev").argtypes = [
@@ -122,7 +126,7 @@ def check(rc):
 
 
 def ctype_of(sfx):
-    return _CT[sfx]
+    return C.c_int32 if sfx in _NARROW else _CT[sfx]
 
 
 # Every symbol include/laser_hip.h declares (tests check the .so exports each of them).
@@ -148,6 +152,13 @@ def declared_symbols():
                   f"laser_hip_gemm_strided_batched_{s}_dev", f"laser_hip_gemm_packed_{s}",
                   f"laser_hip_gemm_strided_{s}_sharded", f"laser_hip_gemm_strided_{s}_sharded_dev",
                   f"laser_hip_map_strided_unary_{s}_dev", f"laser_hip_map_strided_binary_{s}_dev",
+                  f"laser_hip_gemm_packed_{s}_dev"]
+        for ab in "AB":
+            names += [f"laser_hip_gemm_prepack{ab}_mem_required_{s}", f"laser_hip_gemm_prepack{ab}_{s}",
+                      f"laser_hip_gemm_prepack{ab}_{s}_dev"]
+    for s in _NARROW:
+        names += [f"laser_hip_gemm_strided_{s}", f"laser_hip_gemm_strided_{s}_dev",
+                  f"laser_hip_gemm_strided_batched_{s}_dev", f"laser_hip_gemm_packed_{s}",
                   f"laser_hip_gemm_packed_{s}_dev"]
         for ab in "AB":
             names += [f"laser_hip_gemm_prepack{ab}_mem_required_{s}", f"laser_hip_gemm_prepack{ab}_{s}",

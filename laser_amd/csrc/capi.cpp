@@ -66,6 +66,7 @@ struct Context {
   std::atomic<bool> f64_mfma{true};       // float64 GEMM on the f64 matrix cores (false: VALU kernel)
   std::atomic<bool> i32_mfma{true};       // int32 GEMM on the int8 matrix cores (false: VALU kernel)
   std::atomic<bool> i64_mfma{true};       // int64 GEMM on the int8 matrix cores (false: VALU kernel)
+  std::atomic<bool> narrow_mfma{true};    // int8 / int16 GEMM on the int8 matrix cores (false: VALU / skinny kernels)
   std::atomic<bool> zc_poll{true};           // small host-pointer calls: poll completion flags in mapped memory (false: synchronise the stream)
   std::atomic<bool> host_pipeline_2d{true};  // large row-major host-pointer calls: row panels x column panels (false: row panels only)
   std::atomic<int> slice_parallel_min{2};        // (tuning override only) fewest kc slices worth splitting
@@ -447,8 +448,7 @@ hipError_t run_gemm_core<double>(const GemmArgs<double> &a, hipStream_t s) {
 // associative, so C = alpha * sum_chunks(A_c B_c) + beta * C0 is computed chunk by chunk -- the first with (alpha, beta), the
 // rest with (alpha, 1) -- bit for bit the single product.  hipErrorNotSupported (nothing launched): not the kernels' class.
 template <typename T, typename FA, typename FC>
-hipError_t int_gemm_k_chunks(const GemmArgs<T> &a, void *ws, hipStream_t s, FA asm_launch, FC compiler_launch) {
-  constexpr int64_t kChunk = 8192;
+hipError_t int_gemm_k_chunks(const GemmArgs<T> &a, void *ws, hipStream_t s, FA asm_launch, FC compiler_launch, int64_t kChunk = 8192) {
   hipError_t e = hipErrorNotSupported;
   for (int64_t k0 = 0; k0 < a.K; k0 += kChunk) {
     GemmArgs<T> c = a;
@@ -498,6 +498,35 @@ template <>
 hipError_t run_gemm<int32_t>(const GemmArgs<int32_t> &a, hipStream_t s) { return run_gemm_int(a, s); }
 template <>
 hipError_t run_gemm<int64_t>(const GemmArgs<int64_t> &a, hipStream_t s) { return run_gemm_int(a, s); }
+
+// Integer GEMMs mod 2^8 / 2^16 (uint8 / uint16 on the same bits), in the shape of run_gemm_int: the streaming kernel for M or
+// N <= 8, the int8 matrix cores (gemm_narrow_mfma.hip) for single problems with enough work -- K beyond NARROW_MAX_K in chunks
+// --, the VALU kernel otherwise (batches included).
+std::atomic<int> g_last_narrow_mfma{0};
+template <typename T>
+hipError_t run_gemm_narrow(const GemmArgs<T> &a, hipStream_t s) {
+  g_last_narrow_mfma = 0;
+  if (g_ctx.skinny) {
+    const hipError_t e = launch_gemm_skinny<T>(a, false, 0, s);
+    if (e != hipErrorNotSupported) return e;
+  }
+  const double work = (double)a.M * (double)a.N * (double)a.K;
+  if (g_ctx.narrow_mfma && a.batch == 1 && work >= 64.0 * 64.0 * 64.0 * 8.0) {
+    void *ws = nullptr;
+    hipError_t e = scratch_alloc_async(&ws, gemm_narrow_mfma_workspace_bytes<T>(a.M, a.N, a.K), s);
+    if (e != hipSuccess) return e;
+    e = a.K > NARROW_MAX_K ? int_gemm_k_chunks<T>(a, ws, s, launch_gemm_narrow_mfma<T>, launch_gemm_narrow_mfma<T>, NARROW_MAX_K)
+                           : launch_gemm_narrow_mfma<T>(a, ws, s);
+    if (e == hipSuccess) g_last_narrow_mfma = 1;
+    hipError_t e2 = hipFreeAsync(ws, s);
+    return e != hipSuccess ? e : e2;
+  }
+  return launch_gemm_valu<T>(a, false, s);
+}
+template <>
+hipError_t run_gemm<int8_t>(const GemmArgs<int8_t> &a, hipStream_t s) { return run_gemm_narrow(a, s); }
+template <>
+hipError_t run_gemm<int16_t>(const GemmArgs<int16_t> &a, hipStream_t s) { return run_gemm_narrow(a, s); }
 
 // the small-matrix kernel on operands that live in host memory mapped into the device (gemm_host's zero-copy staging)
 template <typename T>
@@ -819,7 +848,7 @@ int gemm_host(int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA,
   // laser_hip_set_shard_devices(n != 1): a large plain gemm_strided call is cut into row ranges over n GPUs (rows of
   // C are independent, gemm.nim:160-176, so the arithmetic is unchanged).  Not for calls that already ARE a shard
   // (tl_device set by the sharded entry point's worker thread) and not worth it below ~4 tile rows per GPU.
-  if (g_ctx.shard_devices != 1 && tl_device < 0 && !(hepi && hepi->on())) {
+  if (sizeof(T) >= 4 && g_ctx.shard_devices != 1 && tl_device < 0 && !(hepi && hepi->on())) {   // (no sharded form for int8 / int16)
     int ndev = g_ctx.shard_devices;
     if (ndev <= 0 && hipGetDeviceCount(&ndev) != hipSuccess) ndev = 1;
     if (ndev > 1 && M >= (int64_t)1024 * ndev && (double)M * (double)N * (double)K >= 64.0 * 1024 * 1024 * 1024)
@@ -1549,6 +1578,7 @@ int laser_hip_set_option(const char *name, int value) {
   else if (n == "int_group_m") g_int_group_m = value < 1 ? 1 : value > 64 ? 64 : value;
   else if (n == "f64_mfma") g_ctx.f64_mfma = on;
   else if (n == "i32_mfma") g_ctx.i32_mfma = on;
+  else if (n == "narrow_mfma") g_ctx.narrow_mfma = on;
   else if (n == "i64_mfma") g_ctx.i64_mfma = on;
   else if (n == "conv_implicit") g_ctx.conv_implicit = on;
   else if (n == "conv_patch") g_conv_patch = on;
@@ -1591,6 +1621,8 @@ int laser_hip_get_option(const char *name, int64_t *value) {
   else if (n == "f64_mfma") *value = g_ctx.f64_mfma;
   else if (n == "i32_mfma") *value = g_ctx.i32_mfma;
   else if (n == "i64_mfma") *value = g_ctx.i64_mfma;
+  else if (n == "narrow_mfma") *value = g_ctx.narrow_mfma;
+  else if (n == "last_narrow_mfma") *value = g_last_narrow_mfma;
   else if (n == "conv_implicit") *value = g_ctx.conv_implicit;
   else if (n == "conv_patch") *value = g_conv_patch;
   else if (n == "conv_direct") *value = g_conv_direct;
@@ -1693,6 +1725,60 @@ LH_DEF_GEMM(f64, double)
 LH_DEF_GEMM(i32, int32_t)
 LH_DEF_GEMM(i64, int64_t)
 #undef LH_DEF_GEMM
+
+// int8 / int16 (uint8 / uint16 on the same bits): alpha and beta travel as int32_t and are reduced mod 2^8 / 2^16
+#define LH_DEF_GEMM_NARROW(SFX, T)                                                                            \
+  int laser_hip_gemm_strided_##SFX(int64_t M, int64_t N, int64_t K, int32_t alpha, const T *A, int64_t rsA,   \
+                                   int64_t csA, const T *B, int64_t rsB, int64_t csB, int32_t beta, T *C,     \
+                                   int64_t rsC, int64_t csC) {                                                \
+    return gemm_host<T>(M, N, K, (T)alpha, A, rsA, csA, B, rsB, csB, (T)beta, C, rsC, csC);                   \
+  }                                                                                                           \
+  int laser_hip_gemm_strided_##SFX##_dev(int64_t M, int64_t N, int64_t K, int32_t alpha, const T *A,          \
+                                         int64_t rsA, int64_t csA, const T *B, int64_t rsB, int64_t csB,      \
+                                         int32_t beta, T *C, int64_t rsC, int64_t csC, void *stream) {        \
+    return gemm_dev<T>(1, M, N, K, (T)alpha, A, rsA, csA, 0, B, rsB, csB, 0, (T)beta, C, rsC, csC, 0, stream); \
+  }                                                                                                           \
+  int laser_hip_gemm_strided_batched_##SFX##_dev(                                                             \
+      int64_t batch, int64_t M, int64_t N, int64_t K, int32_t alpha, const T *A, int64_t rsA, int64_t csA,    \
+      int64_t bsA, const T *B, int64_t rsB, int64_t csB, int64_t bsB, int32_t beta, T *C, int64_t rsC,        \
+      int64_t csC, int64_t bsC, void *stream) {                                                               \
+    return gemm_dev<T>(batch, M, N, K, (T)alpha, A, rsA, csA, bsA, B, rsB, csB, bsB, (T)beta, C, rsC, csC,    \
+                       bsC, stream);                                                                          \
+  }                                                                                                           \
+  int64_t laser_hip_gemm_prepackA_mem_required_##SFX(int64_t M, int64_t N, int64_t K) {                       \
+    return prepack_bytes<T>(true, M, N, K);                                                                   \
+  }                                                                                                           \
+  int64_t laser_hip_gemm_prepackB_mem_required_##SFX(int64_t M, int64_t N, int64_t K) {                       \
+    return prepack_bytes<T>(false, M, N, K);                                                                  \
+  }                                                                                                           \
+  int laser_hip_gemm_prepackA_##SFX(void *dst, int64_t M, int64_t N, int64_t K, const T *A, int64_t rs,       \
+                                    int64_t cs) {                                                             \
+    return prepack_host<T>(true, dst, M, N, K, A, rs, cs);                                                    \
+  }                                                                                                           \
+  int laser_hip_gemm_prepackB_##SFX(void *dst, int64_t M, int64_t N, int64_t K, const T *B, int64_t rs,       \
+                                    int64_t cs) {                                                             \
+    return prepack_host<T>(false, dst, M, N, K, B, rs, cs);                                                   \
+  }                                                                                                           \
+  int laser_hip_gemm_packed_##SFX(int64_t M, int64_t N, int64_t K, int32_t alpha, const void *pA,             \
+                                  const void *pB, int32_t beta, T *C, int64_t rsC, int64_t csC) {             \
+    return packed_host<T>(M, N, K, (T)alpha, pA, pB, (T)beta, C, rsC, csC);                                   \
+  }                                                                                                           \
+  int laser_hip_gemm_prepackA_##SFX##_dev(void *d, int64_t M, int64_t N, int64_t K, const T *A, int64_t rs,   \
+                                          int64_t cs, void *stream) {                                         \
+    return prepack_dev<T>(true, d, M, N, K, A, rs, cs, stream);                                               \
+  }                                                                                                           \
+  int laser_hip_gemm_prepackB_##SFX##_dev(void *d, int64_t M, int64_t N, int64_t K, const T *B, int64_t rs,   \
+                                          int64_t cs, void *stream) {                                         \
+    return prepack_dev<T>(false, d, M, N, K, B, rs, cs, stream);                                              \
+  }                                                                                                           \
+  int laser_hip_gemm_packed_##SFX##_dev(int64_t M, int64_t N, int64_t K, int32_t alpha, const void *dA,       \
+                                        const void *dB, int32_t beta, T *dC, int64_t rsC, int64_t csC,        \
+                                        void *stream) {                                                       \
+    return packed_dev<T>(M, N, K, (T)alpha, dA, dB, (T)beta, dC, rsC, csC, stream);                           \
+  }
+LH_DEF_GEMM_NARROW(i8, int8_t)
+LH_DEF_GEMM_NARROW(i16, int16_t)
+#undef LH_DEF_GEMM_NARROW
 
 int laser_hip_gemm_prepack_release(void *packed) {
   if (!packed) return fail(LASER_HIP_E_INVALID, "null packed buffer");

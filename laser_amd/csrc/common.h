@@ -224,6 +224,14 @@ hipError_t launch_gemm_i32_mfma(const GemmArgs<int32_t> &args, void *ws, hipStre
 size_t gemm_i64_mfma_workspace_bytes(int64_t M, int64_t N, int64_t K);
 hipError_t launch_gemm_i64_mfma(const GemmArgs<int64_t> &args, void *ws, hipStream_t s);
 
+// int8 / int16 GEMM (uint8 / uint16 on the same bits) on the int8 matrix cores, bit-exact mod 2^8 / 2^16 (gemm_narrow_mfma.hip):
+// one / two int8 digit planes per operand.  K <= NARROW_MAX_K per launch (the dispatcher chunks longer K);
+// ws = device scratch of gemm_narrow_mfma_workspace_bytes<T>(M, N, K) bytes, valid on stream s.
+constexpr int64_t NARROW_MAX_K = 16384;
+template <typename T>
+size_t gemm_narrow_mfma_workspace_bytes(int64_t M, int64_t N, int64_t K);
+template <typename T>
+hipError_t launch_gemm_narrow_mfma(const GemmArgs<T> &args, void *ws, hipStream_t s);
 extern std::atomic<int> g_conv_direct;        // few output channels x short K: the direct (HBM-streaming) kernel (1, default)
 hipError_t launch_conv_direct_small_f32(const GemmArgs<float> &a, hipStream_t s);
 extern std::atomic<int> g_conv_patch;         // implicit conv: LDS input patch where it fits (1, default) or always the gather (0)

@@ -356,6 +356,8 @@ template hipError_t launch_pack_pad<float>(float *, int64_t, int64_t, const floa
 template hipError_t launch_pack_pad<double>(double *, int64_t, int64_t, const double *, int64_t, int64_t, int64_t, int64_t, hipStream_t, int);
 template hipError_t launch_pack_pad<int32_t>(int32_t *, int64_t, int64_t, const int32_t *, int64_t, int64_t, int64_t, int64_t, hipStream_t, int);
 template hipError_t launch_pack_pad<int64_t>(int64_t *, int64_t, int64_t, const int64_t *, int64_t, int64_t, int64_t, int64_t, hipStream_t, int);
+template hipError_t launch_pack_pad<int8_t>(int8_t *, int64_t, int64_t, const int8_t *, int64_t, int64_t, int64_t, int64_t, hipStream_t, int);
+template hipError_t launch_pack_pad<int16_t>(int16_t *, int64_t, int64_t, const int16_t *, int64_t, int64_t, int64_t, int64_t, hipStream_t, int);
 
 // ---- rank-N strided copy: `forEachStrided d in dst, s in src: d = s` -----------------------------
 // (laser/tensor/initialization.nim:42-110: deepCopy / copyFrom of non-contiguous tensors.)  HBM-bound.

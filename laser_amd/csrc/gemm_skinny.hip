@@ -48,13 +48,18 @@ __device__ __forceinline__ double fma_<double>(double a, double b, double c) { r
 // integers: two's-complement wrap-around c + a*b (gemm_ukernel_avx2.nim:10-11), done on the unsigned type
 template <>
 __device__ __forceinline__ int32_t fma_<int32_t>(int32_t a, int32_t b, int32_t c) { return (int32_t)((uint32_t)a * (uint32_t)b + (uint32_t)c); }
+// int8 / int16: in uint32_t (narrow unsigned operands would promote to int and overflow), truncated = the result mod 2^8 / 2^16
+template <>
+__device__ __forceinline__ int8_t fma_<int8_t>(int8_t a, int8_t b, int8_t c) { return (int8_t)((uint32_t)a * (uint32_t)b + (uint32_t)c); }
+template <>
+__device__ __forceinline__ int16_t fma_<int16_t>(int16_t a, int16_t b, int16_t c) { return (int16_t)((uint32_t)a * (uint32_t)b + (uint32_t)c); }
 template <>
 __device__ __forceinline__ int64_t fma_<int64_t>(int64_t a, int64_t b, int64_t c) { return (int64_t)((uint64_t)a * (uint64_t)b + (uint64_t)c); }
 
 template <typename E>
 __device__ __forceinline__ E mul_(E a, E b) {
   if constexpr (std::is_integral<E>::value) {
-    using U = typename std::make_unsigned<E>::type;
+    using U = std::conditional_t<(sizeof(E) < 4), uint32_t, typename std::make_unsigned<E>::type>;
     return (E)((U)a * (U)b);
   } else {
 #pragma clang fp contract(off)
@@ -64,7 +69,7 @@ __device__ __forceinline__ E mul_(E a, E b) {
 template <typename E>
 __device__ __forceinline__ E add_(E a, E b) {
   if constexpr (std::is_integral<E>::value) {
-    using U = typename std::make_unsigned<E>::type;
+    using U = std::conditional_t<(sizeof(E) < 4), uint32_t, typename std::make_unsigned<E>::type>;
     return (E)((U)a + (U)b);
   } else {
 #pragma clang fp contract(off)
@@ -212,9 +217,16 @@ hipError_t launch_gemm_skinny(const GemmArgs<E> &g, bool laser_order, int kc_ele
   }
   return a.sxk == 1 ? launch_s<E, true>(a, s) : launch_s<E, false>(a, s);
 }
+#ifndef LH_SKINNY_NARROW
 template hipError_t launch_gemm_skinny<float>(const GemmArgs<float> &, bool, int, hipStream_t);
 template hipError_t launch_gemm_skinny<double>(const GemmArgs<double> &, bool, int, hipStream_t);
 template hipError_t launch_gemm_skinny<int32_t>(const GemmArgs<int32_t> &, bool, int, hipStream_t);
 template hipError_t launch_gemm_skinny<int64_t>(const GemmArgs<int64_t> &, bool, int, hipStream_t);
+#else
+// int8 / int16: a translation unit of their own (Makefile: -DLH_SKINNY_NARROW), built without the SLP vectorizer, whose
+// vectors of 1-byte elements crash the gfx950 instruction selector on these kernels
+template hipError_t launch_gemm_skinny<int8_t>(const GemmArgs<int8_t> &, bool, int, hipStream_t);
+template hipError_t launch_gemm_skinny<int16_t>(const GemmArgs<int16_t> &, bool, int, hipStream_t);
+#endif
 
 }  // namespace laser_hip

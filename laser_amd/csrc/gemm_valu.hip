@@ -30,6 +30,16 @@ template <> struct Arith<int32_t> {
   static __device__ __forceinline__ int32_t mul(int32_t a, int32_t b) { return (int32_t)((uint32_t)a * (uint32_t)b); }
   static __device__ __forceinline__ int32_t add(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
 };
+// int8 / int16 (uint8 / uint16 on the same bits): the arithmetic in uint32_t -- (uint16_t)a * (uint16_t)b would promote to int
+// and overflow -- then truncated, which is the product mod 2^8 / 2^16
+template <typename T> struct NarrowArith {
+  static constexpr bool kSliced = false;
+  static __device__ __forceinline__ T madd(T a, T b, T c) { return (T)((uint32_t)c + (uint32_t)a * (uint32_t)b); }
+  static __device__ __forceinline__ T mul(T a, T b) { return (T)((uint32_t)a * (uint32_t)b); }
+  static __device__ __forceinline__ T add(T a, T b) { return (T)((uint32_t)a + (uint32_t)b); }
+};
+template <> struct Arith<int8_t> : NarrowArith<int8_t> {};
+template <> struct Arith<int16_t> : NarrowArith<int16_t> {};
 template <> struct Arith<int64_t> {
   static constexpr bool kSliced = false;
   static __device__ __forceinline__ int64_t madd(int64_t a, int64_t b, int64_t c) {
@@ -171,5 +181,7 @@ template hipError_t launch_gemm_valu<double>(const GemmArgs<double> &, bool, hip
 template hipError_t launch_gemm_valu<float>(const GemmArgs<float> &, bool, hipStream_t);
 template hipError_t launch_gemm_valu<int32_t>(const GemmArgs<int32_t> &, bool, hipStream_t);
 template hipError_t launch_gemm_valu<int64_t>(const GemmArgs<int64_t> &, bool, hipStream_t);
+template hipError_t launch_gemm_valu<int8_t>(const GemmArgs<int8_t> &, bool, hipStream_t);
+template hipError_t launch_gemm_valu<int16_t>(const GemmArgs<int16_t> &, bool, hipStream_t);
 
 }  // namespace laser_hip

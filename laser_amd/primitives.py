@@ -18,6 +18,7 @@ computes: every function forwards to the HIP library and raises LaserHipError on
 """
 import ctypes as C
 import math
+import operator
 
 import numpy as np
 
@@ -28,7 +29,10 @@ try:  # torch is plumbing for device memory / streams only
 except Exception:  # pragma: no cover
     torch = None
 
-_SFX = {"float32": "f32", "float64": "f64", "int32": "i32", "int64": "i64"}
+_SFX = {"float32": "f32", "float64": "f64", "int32": "i32", "int64": "i64",
+        # every other integer type rides on the signed entry point of its width (arithmetic mod 2^n: the same bits)
+        "int8": "i8", "uint8": "i8", "int16": "i16", "uint16": "i16", "uint32": "i32", "uint64": "i64"}
+_IBITS = {"i8": 8, "i16": 16, "i32": 32, "i64": 64}
 
 
 def _is_lt(x):
@@ -43,8 +47,19 @@ def _is_dev(x):
 def _sfx(x):
     name = str(x.dtype).replace("torch.", "")
     if name not in _SFX:
-        raise TypeError(f"unsupported element type {x.dtype} (Laser GEMM: float32/float64/int32/int64)")
+        raise TypeError(f"unsupported element type {x.dtype} (Laser GEMM: float32/float64 and 8- to 64-bit integers)")
     return _SFX[name]
+
+
+def _scalar(s, v):
+    """alpha / beta for the entry point of suffix `s`: integers reduced mod 2^n to the signed representative (what an
+    unsigned scalar is on the same bits; the int8 / int16 entry points take them as int32_t)."""
+    ct = _lib.ctype_of(s)
+    if s not in _IBITS:
+        return ct(v)
+    n = _IBITS[s]
+    v = operator.index(v) & ((1 << n) - 1)
+    return ct(v - (1 << n) if v >> (n - 1) else v)
 
 
 def _ptr(x):
@@ -239,9 +254,8 @@ def gemm_strided(M, N, K, alpha, A, rowStrideA, colStrideA, B, rowStrideB, colSt
     s = _sfx(C_)
     if _sfx(A) != s or _sfx(B) != s:
         raise TypeError("A, B, C must share one element type")
-    ct = _lib.ctype_of(s)
-    args = [M, N, K, ct(alpha), _ptr(A), rowStrideA, colStrideA, _ptr(B), rowStrideB, colStrideB,
-            ct(beta), _ptr(C_), rowStrideC, colStrideC]
+    args = [M, N, K, _scalar(s, alpha), _ptr(A), rowStrideA, colStrideA, _ptr(B), rowStrideB, colStrideB,
+            _scalar(s, beta), _ptr(C_), rowStrideC, colStrideC]
     act = _activation_code(activation) | int(pre)
     if bias is not None or act:
         if s not in ("f32", "f64"):
@@ -267,9 +281,8 @@ def gemm_strided_batched(batch, M, N, K, alpha, A, rsA, csA, bsA, B, rsB, csB, b
     s = _sfx(C_)
     if not _same_side(A, B, C_):
         raise TypeError("batched GEMM is a device-resident entry point")
-    ct = _lib.ctype_of(s)
     _lib.check(getattr(L, f"laser_hip_gemm_strided_batched_{s}_dev")(
-        batch, M, N, K, ct(alpha), _ptr(A), rsA, csA, bsA, _ptr(B), rsB, csB, bsB, ct(beta), _ptr(C_),
+        batch, M, N, K, _scalar(s, alpha), _ptr(A), rsA, csA, bsA, _ptr(B), rsB, csB, bsB, _scalar(s, beta), _ptr(C_),
         rsC, csC, bsC, _stream()))
     return C_
 
@@ -345,13 +358,13 @@ def gemm_prepackB(dst_packedB, M, N, K, src_B, rowStrideB, colStrideB):
 def gemm_packed(M, N, K, alpha, packedA, packedB, beta, C_, rowStrideC, colStrideC):
     L = _lib.lib()
     s = _sfx(C_)
-    ct = _lib.ctype_of(s)
+    alpha, beta = _scalar(s, alpha), _scalar(s, beta)
     if _same_side(packedA, packedB, C_):
-        _lib.check(getattr(L, f"laser_hip_gemm_packed_{s}_dev")(M, N, K, ct(alpha), _ptr(packedA), _ptr(packedB),
-                                                                ct(beta), _ptr(C_), rowStrideC, colStrideC, _stream()))
+        _lib.check(getattr(L, f"laser_hip_gemm_packed_{s}_dev")(M, N, K, alpha, _ptr(packedA), _ptr(packedB),
+                                                                beta, _ptr(C_), rowStrideC, colStrideC, _stream()))
     else:
-        _lib.check(getattr(L, f"laser_hip_gemm_packed_{s}")(M, N, K, ct(alpha), _ptr(packedA), _ptr(packedB),
-                                                            ct(beta), _ptr(C_), rowStrideC, colStrideC))
+        _lib.check(getattr(L, f"laser_hip_gemm_packed_{s}")(M, N, K, alpha, _ptr(packedA), _ptr(packedB),
+                                                            beta, _ptr(C_), rowStrideC, colStrideC))
     return C_
 
 

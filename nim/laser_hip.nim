@@ -23,7 +23,7 @@ const laserHip* = "liblaser_hip.so"
 # ---- C-ABI imports (Nim int == int64 on amd64, float32 == C float) ---------------------------
 proc laser_hip_last_error(): cstring {.lh, importc: "laser_hip_last_error".}
 proc laser_hip_abi_version*(): cint {.lh, importc: "laser_hip_abi_version".}
-const laserHipAbi* = 2                       # include/laser_hip.h LASER_HIP_ABI_VERSION this shim was written against
+const laserHipAbi* = 3                       # include/laser_hip.h LASER_HIP_ABI_VERSION this shim was written against
 proc laser_hip_init*(device: cint): cint {.lh, importc: "laser_hip_init".}
 proc laser_hip_finalize*(): cint {.lh, importc: "laser_hip_finalize".}
 proc laser_hip_device_count*(): cint {.lh, importc: "laser_hip_device_count".}
@@ -53,6 +53,11 @@ proc laser_hip_gemm_strided_f32_dev(M, N, K: int, alpha: float32, A: pointer, rs
 proc laser_hip_gemm_strided_f64_dev(M, N, K: int, alpha: float64, A: pointer, rsA, csA: int, B: pointer, rsB, csB: int, beta: float64, C: pointer, rsC, csC: int, stream: pointer): cint {.lh, importc: "laser_hip_gemm_strided_f64_dev".}
 proc laser_hip_gemm_strided_i32_dev(M, N, K: int, alpha: int32, A: pointer, rsA, csA: int, B: pointer, rsB, csB: int, beta: int32, C: pointer, rsC, csC: int, stream: pointer): cint {.lh, importc: "laser_hip_gemm_strided_i32_dev".}
 proc laser_hip_gemm_strided_i64_dev(M, N, K: int, alpha: int64, A: pointer, rsA, csA: int, B: pointer, rsB, csB: int, beta: int64, C: pointer, rsC, csC: int, stream: pointer): cint {.lh, importc: "laser_hip_gemm_strided_i64_dev".}
+# int8 / int16 (uint8 / uint16 on the same bits): alpha and beta travel as int32 and the library reduces them mod 2^8 / 2^16
+proc laser_hip_gemm_strided_i8(M, N, K: int, alpha: int32, A: ptr int8, rsA, csA: int, B: ptr int8, rsB, csB: int, beta: int32, C: ptr int8, rsC, csC: int): cint {.lh, importc: "laser_hip_gemm_strided_i8".}
+proc laser_hip_gemm_strided_i16(M, N, K: int, alpha: int32, A: ptr int16, rsA, csA: int, B: ptr int16, rsB, csB: int, beta: int32, C: ptr int16, rsC, csC: int): cint {.lh, importc: "laser_hip_gemm_strided_i16".}
+proc laser_hip_gemm_strided_i8_dev(M, N, K: int, alpha: int32, A: pointer, rsA, csA: int, B: pointer, rsB, csB: int, beta: int32, C: pointer, rsC, csC: int, stream: pointer): cint {.lh, importc: "laser_hip_gemm_strided_i8_dev".}
+proc laser_hip_gemm_strided_i16_dev(M, N, K: int, alpha: int32, A: pointer, rsA, csA: int, B: pointer, rsB, csB: int, beta: int32, C: pointer, rsC, csC: int, stream: pointer): cint {.lh, importc: "laser_hip_gemm_strided_i16_dev".}
 
 # pre-packed GEMM
 proc laser_hip_gemm_prepackA_mem_required_f32(M, N, K: int): int {.lh, importc: "laser_hip_gemm_prepackA_mem_required_f32".}
@@ -75,6 +80,16 @@ proc laser_hip_gemm_packed_f32(M, N, K: int, alpha: float32, pA, pB: pointer, be
 proc laser_hip_gemm_packed_f64(M, N, K: int, alpha: float64, pA, pB: pointer, beta: float64, C: ptr float64, rsC, csC: int): cint {.lh, importc: "laser_hip_gemm_packed_f64".}
 proc laser_hip_gemm_packed_i32(M, N, K: int, alpha: int32, pA, pB: pointer, beta: int32, C: ptr int32, rsC, csC: int): cint {.lh, importc: "laser_hip_gemm_packed_i32".}
 proc laser_hip_gemm_packed_i64(M, N, K: int, alpha: int64, pA, pB: pointer, beta: int64, C: ptr int64, rsC, csC: int): cint {.lh, importc: "laser_hip_gemm_packed_i64".}
+proc laser_hip_gemm_prepackA_mem_required_i8(M, N, K: int): int {.lh, importc: "laser_hip_gemm_prepackA_mem_required_i8".}
+proc laser_hip_gemm_prepackA_mem_required_i16(M, N, K: int): int {.lh, importc: "laser_hip_gemm_prepackA_mem_required_i16".}
+proc laser_hip_gemm_prepackB_mem_required_i8(M, N, K: int): int {.lh, importc: "laser_hip_gemm_prepackB_mem_required_i8".}
+proc laser_hip_gemm_prepackB_mem_required_i16(M, N, K: int): int {.lh, importc: "laser_hip_gemm_prepackB_mem_required_i16".}
+proc laser_hip_gemm_prepackA_i8(dst: pointer, M, N, K: int, A: ptr int8, rs, cs: int): cint {.lh, importc: "laser_hip_gemm_prepackA_i8".}
+proc laser_hip_gemm_prepackA_i16(dst: pointer, M, N, K: int, A: ptr int16, rs, cs: int): cint {.lh, importc: "laser_hip_gemm_prepackA_i16".}
+proc laser_hip_gemm_prepackB_i8(dst: pointer, M, N, K: int, B: ptr int8, rs, cs: int): cint {.lh, importc: "laser_hip_gemm_prepackB_i8".}
+proc laser_hip_gemm_prepackB_i16(dst: pointer, M, N, K: int, B: ptr int16, rs, cs: int): cint {.lh, importc: "laser_hip_gemm_prepackB_i16".}
+proc laser_hip_gemm_packed_i8(M, N, K: int, alpha: int32, pA, pB: pointer, beta: int32, C: ptr int8, rsC, csC: int): cint {.lh, importc: "laser_hip_gemm_packed_i8".}
+proc laser_hip_gemm_packed_i16(M, N, K: int, alpha: int32, pA, pB: pointer, beta: int32, C: ptr int16, rsC, csC: int): cint {.lh, importc: "laser_hip_gemm_packed_i16".}
 proc laser_hip_gemm_prepack_release*(packed: pointer): cint {.lh, importc: "laser_hip_gemm_prepack_release".}
 
 # physical transposes
@@ -109,8 +124,8 @@ proc laser_hip_copy_strided_b32_dev(dst: pointer, dstStrides: ptr int, src: poin
 proc laser_hip_copy_strided_b64_dev(dst: pointer, dstStrides: ptr int, src: pointer, srcStrides: ptr int, shape: ptr int, rank: cint, stream: pointer): cint {.lh, importc: "laser_hip_copy_strided_b64_dev".}
 
 # ---- gemm_strided -- laser/primitives/matrix_multiplication/gemm.nim:184-193 --------------------
-# Element types dispatched by the reference: float32, float64, int32 / uint32 (one branch, gemm.nim:239),
-# int64.  Integer arithmetic wraps modulo 2^n, so uint32 is the int32 entry point on the same bits.
+# Element types: every SomeNumber, like the reference (gemm.nim:184-248).  Integer arithmetic wraps modulo 2^n, so each
+# unsigned type is the signed entry point of its width on the same bits (gemm.nim:239 does this for int32 / uint32).
 proc gemm_strided*[T: SomeNumber](
       M, N, K: int,
       alpha: T,
@@ -135,6 +150,18 @@ proc gemm_strided*[T: SomeNumber](
     check laser_hip_gemm_strided_i64(M, N, K, cast[int64](alpha), cast[ptr int64](A), rowStrideA, colStrideA,
                                      cast[ptr int64](B), rowStrideB, colStrideB, cast[int64](beta),
                                      cast[ptr int64](C), rowStrideC, colStrideC)
+  elif T is uint64 or T is uint:
+    check laser_hip_gemm_strided_i64(M, N, K, cast[int64](alpha), cast[ptr int64](A), rowStrideA, colStrideA,
+                                     cast[ptr int64](B), rowStrideB, colStrideB, cast[int64](beta),
+                                     cast[ptr int64](C), rowStrideC, colStrideC)
+  elif T is int8 or T is uint8:
+    check laser_hip_gemm_strided_i8(M, N, K, int32(cast[int8](alpha)), cast[ptr int8](A), rowStrideA, colStrideA,
+                                    cast[ptr int8](B), rowStrideB, colStrideB, int32(cast[int8](beta)),
+                                    cast[ptr int8](C), rowStrideC, colStrideC)
+  elif T is int16 or T is uint16:
+    check laser_hip_gemm_strided_i16(M, N, K, int32(cast[int16](alpha)), cast[ptr int16](A), rowStrideA, colStrideA,
+                                     cast[ptr int16](B), rowStrideB, colStrideB, int32(cast[int16](beta)),
+                                     cast[ptr int16](C), rowStrideC, colStrideC)
   else:
     {.error: "laser_hip: unsupported element type " & $T.}
 
@@ -168,12 +195,16 @@ proc gemm_prepackB_mem_required*(T: type, M, N, K: int): int =
   when T is float32: laser_hip_gemm_prepackB_mem_required_f32(M, N, K)
   elif T is float64: laser_hip_gemm_prepackB_mem_required_f64(M, N, K)
   elif T is int32 or T is uint32: laser_hip_gemm_prepackB_mem_required_i32(M, N, K)
+  elif T is int8 or T is uint8: laser_hip_gemm_prepackB_mem_required_i8(M, N, K)
+  elif T is int16 or T is uint16: laser_hip_gemm_prepackB_mem_required_i16(M, N, K)
   else: laser_hip_gemm_prepackB_mem_required_i64(M, N, K)
 
 proc gemm_prepackA_mem_required*(T: type, M, N, K: int): int =
   when T is float32: laser_hip_gemm_prepackA_mem_required_f32(M, N, K)
   elif T is float64: laser_hip_gemm_prepackA_mem_required_f64(M, N, K)
   elif T is int32 or T is uint32: laser_hip_gemm_prepackA_mem_required_i32(M, N, K)
+  elif T is int8 or T is uint8: laser_hip_gemm_prepackA_mem_required_i8(M, N, K)
+  elif T is int16 or T is uint16: laser_hip_gemm_prepackA_mem_required_i16(M, N, K)
   else: laser_hip_gemm_prepackA_mem_required_i64(M, N, K)
 
 proc gemm_prepackB*[T](dst_packedB: ptr (T or UncheckedArray[T]), M, N, K: int,
@@ -181,6 +212,9 @@ proc gemm_prepackB*[T](dst_packedB: ptr (T or UncheckedArray[T]), M, N, K: int,
   when T is float32: check laser_hip_gemm_prepackB_f32(dst_packedB, M, N, K, src_B, rowStrideB, colStrideB)
   elif T is float64: check laser_hip_gemm_prepackB_f64(dst_packedB, M, N, K, src_B, rowStrideB, colStrideB)
   elif T is int32: check laser_hip_gemm_prepackB_i32(dst_packedB, M, N, K, src_B, rowStrideB, colStrideB)
+  elif T is uint32: check laser_hip_gemm_prepackB_i32(dst_packedB, M, N, K, cast[ptr int32](src_B), rowStrideB, colStrideB)
+  elif T is int8 or T is uint8: check laser_hip_gemm_prepackB_i8(dst_packedB, M, N, K, cast[ptr int8](src_B), rowStrideB, colStrideB)
+  elif T is int16 or T is uint16: check laser_hip_gemm_prepackB_i16(dst_packedB, M, N, K, cast[ptr int16](src_B), rowStrideB, colStrideB)
   else: check laser_hip_gemm_prepackB_i64(dst_packedB, M, N, K, cast[ptr int64](src_B), rowStrideB, colStrideB)
 
 proc gemm_prepackA*[T](dst_packedA: ptr (T or UncheckedArray[T]), M, N, K: int,
@@ -188,6 +222,9 @@ proc gemm_prepackA*[T](dst_packedA: ptr (T or UncheckedArray[T]), M, N, K: int,
   when T is float32: check laser_hip_gemm_prepackA_f32(dst_packedA, M, N, K, src_A, rowStrideA, colStrideA)
   elif T is float64: check laser_hip_gemm_prepackA_f64(dst_packedA, M, N, K, src_A, rowStrideA, colStrideA)
   elif T is int32: check laser_hip_gemm_prepackA_i32(dst_packedA, M, N, K, src_A, rowStrideA, colStrideA)
+  elif T is uint32: check laser_hip_gemm_prepackA_i32(dst_packedA, M, N, K, cast[ptr int32](src_A), rowStrideA, colStrideA)
+  elif T is int8 or T is uint8: check laser_hip_gemm_prepackA_i8(dst_packedA, M, N, K, cast[ptr int8](src_A), rowStrideA, colStrideA)
+  elif T is int16 or T is uint16: check laser_hip_gemm_prepackA_i16(dst_packedA, M, N, K, cast[ptr int16](src_A), rowStrideA, colStrideA)
   else: check laser_hip_gemm_prepackA_i64(dst_packedA, M, N, K, cast[ptr int64](src_A), rowStrideA, colStrideA)
 
 proc gemm_packed*[T: SomeNumber](M, N, K: int, alpha: T,
@@ -196,6 +233,9 @@ proc gemm_packed*[T: SomeNumber](M, N, K: int, alpha: T,
   when T is float32: check laser_hip_gemm_packed_f32(M, N, K, alpha, packedA, packedB, beta, cast[ptr float32](C), rowStrideC, colStrideC)
   elif T is float64: check laser_hip_gemm_packed_f64(M, N, K, alpha, packedA, packedB, beta, cast[ptr float64](C), rowStrideC, colStrideC)
   elif T is int32: check laser_hip_gemm_packed_i32(M, N, K, alpha, packedA, packedB, beta, cast[ptr int32](C), rowStrideC, colStrideC)
+  elif T is uint32: check laser_hip_gemm_packed_i32(M, N, K, cast[int32](alpha), packedA, packedB, cast[int32](beta), cast[ptr int32](C), rowStrideC, colStrideC)
+  elif T is int8 or T is uint8: check laser_hip_gemm_packed_i8(M, N, K, int32(cast[int8](alpha)), packedA, packedB, int32(cast[int8](beta)), cast[ptr int8](C), rowStrideC, colStrideC)
+  elif T is int16 or T is uint16: check laser_hip_gemm_packed_i16(M, N, K, int32(cast[int16](alpha)), packedA, packedB, int32(cast[int16](beta)), cast[ptr int16](C), rowStrideC, colStrideC)
   else: check laser_hip_gemm_packed_i64(M, N, K, cast[int64](alpha), packedA, packedB, cast[int64](beta), cast[ptr int64](C), rowStrideC, colStrideC)
 
 # ---- physical transposes -- laser/primitives/swapaxes.nim:16-112 ---------------------------------
@@ -484,7 +524,11 @@ proc gemm_strided*[T: SomeNumber](
     check laser_hip_gemm_strided_i32_dev(M, N, K, alpha, pointer(A), rowStrideA, colStrideA, pointer(B), rowStrideB, colStrideB, beta, pointer(C), rowStrideC, colStrideC, stream)
   elif T is uint32:
     check laser_hip_gemm_strided_i32_dev(M, N, K, cast[int32](alpha), pointer(A), rowStrideA, colStrideA, pointer(B), rowStrideB, colStrideB, cast[int32](beta), pointer(C), rowStrideC, colStrideC, stream)
-  elif T is int64 or T is int:
+  elif T is int64 or T is int or T is uint64 or T is uint:
     check laser_hip_gemm_strided_i64_dev(M, N, K, cast[int64](alpha), pointer(A), rowStrideA, colStrideA, pointer(B), rowStrideB, colStrideB, cast[int64](beta), pointer(C), rowStrideC, colStrideC, stream)
+  elif T is int8 or T is uint8:
+    check laser_hip_gemm_strided_i8_dev(M, N, K, int32(cast[int8](alpha)), pointer(A), rowStrideA, colStrideA, pointer(B), rowStrideB, colStrideB, int32(cast[int8](beta)), pointer(C), rowStrideC, colStrideC, stream)
+  elif T is int16 or T is uint16:
+    check laser_hip_gemm_strided_i16_dev(M, N, K, int32(cast[int16](alpha)), pointer(A), rowStrideA, colStrideA, pointer(B), rowStrideB, colStrideB, int32(cast[int16](beta)), pointer(C), rowStrideC, colStrideC, stream)
   else:
     {.error: "laser_hip: unsupported element type " & $T.}
