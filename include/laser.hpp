@@ -5,6 +5,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <cstring>
 #include <initializer_list>
 #include <memory>
 #include <stdexcept>
@@ -358,6 +359,80 @@ void gemm(T alpha, const Tensor<T> &A, const Tensor<T> &B, T beta, Tensor<T> &C)
     throw Error(LASER_HIP_E_INVALID, "gemm: shapes do not agree");
   gemm_strided_dev<T>(A.shape[0], B.shape[1], A.shape[1], alpha, A.unsafe_raw_data(), A.strides[0], A.strides[1],
                       B.unsafe_raw_data(), B.strides[0], B.strides[1], beta, C.unsafe_raw_data(), C.strides[0], C.strides[1]);
+}
+
+// ---- forEach with a body (include/laser_hip.h "forEach with a body"): Laser's forEach over device Tensors --------------
+//   laser::forEach("x += y * z", {laser::out("x", tx), laser::in("y", ty), laser::in("z", tz)}, {laser::param("alpha", 0.5f)});
+// The first operand gives the iteration shape; writable operands (out) have exactly that shape, read-only ones (in)
+// broadcast like numpy.  Element types may differ between operands; a parameter keeps the C++ type it is given.
+// Asynchronous on `stream`.  The library compiles a spec once per device and process.
+template <typename T>
+constexpr int dtype_code() {
+  static_assert(std::is_arithmetic<T>::value && !std::is_same<T, bool>::value, "an element type of LASER_HIP_DT_*");
+  if constexpr (std::is_floating_point<T>::value) return sizeof(T) == 4 ? LASER_HIP_DT_F32 : LASER_HIP_DT_F64;
+  else if constexpr (std::is_signed<T>::value)
+    return sizeof(T) == 1 ? LASER_HIP_DT_I8 : sizeof(T) == 2 ? LASER_HIP_DT_I16 : sizeof(T) == 4 ? LASER_HIP_DT_I32 : LASER_HIP_DT_I64;
+  else return sizeof(T) == 1 ? LASER_HIP_DT_U8 : sizeof(T) == 2 ? LASER_HIP_DT_U16 : sizeof(T) == 4 ? LASER_HIP_DT_U32 : LASER_HIP_DT_U64;
+}
+struct ForEachOperand {
+  std::string name;
+  int dtype;
+  bool writable;
+  void *ptr;
+  std::vector<int64_t> shape, strides;
+};
+struct ForEachParam {
+  std::string name;
+  int dtype;
+  uint64_t slot;  // the value in the low bytes
+};
+template <typename T>
+ForEachOperand out(const char *name, Tensor<T> &t) {
+  return {name, dtype_code<T>(), true, t.unsafe_raw_data(), t.shape, t.strides};
+}
+template <typename T>
+ForEachOperand in(const char *name, const Tensor<T> &t) {
+  return {name, dtype_code<T>(), false, const_cast<T *>(t.unsafe_raw_data()), t.shape, t.strides};
+}
+template <typename T>
+ForEachParam param(const char *name, T value) {
+  ForEachParam p{name, dtype_code<T>(), 0};
+  std::memcpy(&p.slot, &value, sizeof(T));
+  return p;
+}
+inline void forEach(const std::string &body, const std::vector<ForEachOperand> &ops, const std::vector<ForEachParam> &params = {},
+                    void *stream = nullptr) {
+  if (ops.empty()) throw Error(LASER_HIP_E_INVALID, "forEach: no operand");
+  std::vector<const char *> names, pnames;
+  std::vector<int> dtypes, writable, pdtypes;
+  std::vector<void *> ptrs;
+  std::vector<uint64_t> slots;
+  std::vector<int64_t> strides;
+  const std::vector<int64_t> &shape = ops[0].shape;
+  const int r = (int)shape.size();
+  for (const ForEachOperand &o : ops) {
+    names.push_back(o.name.c_str());
+    dtypes.push_back(o.dtype);
+    writable.push_back(o.writable);
+    ptrs.push_back(o.ptr);
+    const int pad = r - (int)o.shape.size();
+    if (pad < 0 || (o.writable && o.shape != shape))
+      throw Error(LASER_HIP_E_INVALID, ("forEach: operand " + o.name + " does not fit the iteration shape").c_str());
+    for (int d = 0; d < r; d++) {  // numpy broadcasting: missing / extent-1 dimensions get stride 0
+      const int64_t e = d < pad ? 1 : o.shape[d - pad];
+      if (e != shape[d] && e != 1) throw Error(LASER_HIP_E_INVALID, ("forEach: operand " + o.name + " does not broadcast").c_str());
+      strides.push_back(d < pad || (e == 1 && !o.writable) ? 0 : o.strides[d - pad]);
+    }
+  }
+  for (const ForEachParam &p : params) {
+    pnames.push_back(p.name.c_str());
+    pdtypes.push_back(p.dtype);
+    slots.push_back(p.slot);
+  }
+  int64_t handle = 0;
+  check(laser_hip_foreach_kernel(body.c_str(), (int)ops.size(), names.data(), dtypes.data(), writable.data(), (int)params.size(),
+                                 pnames.data(), pdtypes.data(), &handle));
+  check(laser_hip_foreach_dev(handle, ptrs.data(), strides.data(), shape.data(), r, slots.data(), stream));
 }
 
 #undef LASER_DISPATCH

@@ -45,6 +45,7 @@ extern "C" {
 #define LASER_HIP_E_HIP 2       /* a HIP runtime call failed; see laser_hip_last_error() */
 #define LASER_HIP_E_NODEVICE 3  /* no gfx950 device / library built without device code for this GPU */
 #define LASER_HIP_E_HANDLE 4    /* pre-packed buffer handle is stale or corrupt */
+#define LASER_HIP_E_COMPILE 5   /* a forEach body did not compile, or hiprtc could not be loaded (see "forEach with a body") */
 
 /* ---- lifecycle ----------------------------------------------------------------------------- */
 /* Lazy-initialised on first use; explicit init selects the device (-1 = current device). */
@@ -159,7 +160,9 @@ int laser_hip_f32_config_count(void);
  *                      correct run; reading it synchronises the device, and a stream reported here has its hand-over flags reset)
  *   "last_conv_tail"   how the last convolution's pixel tail ran: 0 no tail, 1 the direct tail kernel, 2 kc slices + combine, 3 one
  *                      compiler-kernel launch
- *   "last_split"       column where the last compiler-scheduled float GEMM / conv launch was cut into main + tail (0 = one launch) */
+ *   "last_split"       column where the last compiler-scheduled float GEMM / conv launch was cut into main + tail (0 = one launch)
+ *   "foreach_compiles" hiprtc compiles of forEach bodies made by this process
+ *   "last_foreach_variant"  kernel of the last laser_hip_foreach_dev launch: 0 contiguous vectorised, 1 contiguous scalar, 2 strided */
 int laser_hip_set_option(const char *name, int value);
 int laser_hip_get_option(const char *name, int64_t *value);
 const char *laser_hip_f32_config_name(int cfg);
@@ -480,6 +483,66 @@ LASER_HIP_DECL_MAP(f64, double)
 LASER_HIP_DECL_MAP(i32, int32_t)
 LASER_HIP_DECL_MAP(i64, int64_t)
 #undef LASER_HIP_DECL_MAP
+
+/* ---- forEach with a body: laser/strided_iteration/foreach.nim:192-264 --------------------------------------------
+ *   forEach x in a, y in b, z in c:  x += y * z
+ * over device views: for every index of `shape`, each named operand is bound to its element, the body runs, and the
+ * writable operands are stored back.  The body is HIP C++ (Laser's statement syntax `x += y * z`, `x = y > 0 ? y : 0` is
+ * valid C++; statements are separated by `;`, a trailing one is optional) and may call the device math library (expf,
+ * logf, sqrtf, fmaxf, ...).  It is compiled at run time with hiprtc (libhiprtc.so is loaded on first use; this library
+ * does not link it) with -O3 -std=c++17 -ffp-contract=off -fwrapv: no fast-math, no denormal flushing, so + - * / on
+ * floats give the bits numpy or a host loop gives, integer arithmetic wraps mod 2^n like numpy, and sqrtf / divisions are
+ * the device library's correctly rounded forms.  Casts are C++'s: float -> int truncates, out-of-range is undefined.
+ *
+ * The spec -- every entry point below takes it, and it identifies one compiled kernel:
+ *   body                          HIP C++ statements
+ *   nops, names[], dtypes[], writable[]
+ *                                 1..8 operands: name, element type (LASER_HIP_DT_*), non-zero = written back.  Read-only
+ *                                 operands are `const` locals: assigning to one is a compile error.
+ *   nparams, param_names[], param_dtypes[]
+ *                                 0..8 scalar parameters (`const` locals of their type); their VALUES are launch
+ *                                 arguments, so changing them does not compile again
+ *   Names are C identifiers, unique, not C++ keywords, not starting with `lh_` (the template's prefix) or `__`; anything
+ *   else (and an unknown dtype code, too many operands or parameters) is LASER_HIP_E_INVALID.
+ *
+ * foreach_source   the generated HIP source (NUL-terminated) into buf; *len = bytes needed including the NUL; buf == NULL
+ *                  asks for the size only; cap < *len is LASER_HIP_E_INVALID.  Host code only, needs no device.
+ * foreach_code     compiles for `arch` (e.g. "gfx950") and returns the code object (an amdgcn ELF, same buffer rules).  Loads
+ *                  nothing, needs no device.  An arch naming xnack+ is LASER_HIP_E_INVALID.
+ * foreach_kernel   compiles for the current device (its gcnArchName as reported), loads the module and returns a handle.
+ *                  Cached per (device, spec) for the life of the process: a second call with the same spec does not
+ *                  compile, and concurrent first calls compile once.  No gfx950 device: LASER_HIP_E_NODEVICE.
+ * foreach_dev      launches, asynchronous on `stream`, on the device the handle was made for (the current device).
+ *                  ptrs[k]: operand k's device address; strides: nops x rank ELEMENT strides (row k = operand k, negative
+ *                  allowed; 0 = broadcast, allowed on read-only operands only -- LASER_HIP_E_INVALID on a writable one);
+ *                  rank <= 6 (LASER_MAXRANK); params: nparams 8-byte slots, parameter j's value in the low bytes of slot j.
+ *                  A writable operand may alias a read operand element for element; partial overlap is undefined.  Size 0
+ *                  is a no-op.  Kernels (get_option "last_foreach_variant"): 0 = every operand C-contiguous and aligned to
+ *                  16 bytes of the widest operand's vector -> 16-byte loads / stores per lane; 1 = contiguous with an
+ *                  unaligned base; 2 = strided (dimensions merged as map_strided does).
+ * Errors: LASER_HIP_E_COMPILE when the body does not compile or hiprtc cannot be loaded -- laser_hip_last_error() holds the
+ * compiler's log.  get_option "foreach_compiles": hiprtc compiles made by this process. */
+#define LASER_HIP_DT_F32 0
+#define LASER_HIP_DT_F64 1
+#define LASER_HIP_DT_I8 2
+#define LASER_HIP_DT_I16 3
+#define LASER_HIP_DT_I32 4
+#define LASER_HIP_DT_I64 5
+#define LASER_HIP_DT_U8 6
+#define LASER_HIP_DT_U16 7
+#define LASER_HIP_DT_U32 8
+#define LASER_HIP_DT_U64 9
+int laser_hip_foreach_source(const char *body, int nops, const char *const *names, const int *dtypes,
+                             const int *writable, int nparams, const char *const *param_names,
+                             const int *param_dtypes, char *buf, int64_t cap, int64_t *len);
+int laser_hip_foreach_code(const char *body, int nops, const char *const *names, const int *dtypes,
+                           const int *writable, int nparams, const char *const *param_names,
+                           const int *param_dtypes, const char *arch, void *buf, int64_t cap, int64_t *len);
+int laser_hip_foreach_kernel(const char *body, int nops, const char *const *names, const int *dtypes,
+                             const int *writable, int nparams, const char *const *param_names,
+                             const int *param_dtypes, int64_t *handle);
+int laser_hip_foreach_dev(int64_t handle, void *const *ptrs, const int64_t *strides, const int64_t *shape, int rank,
+                          const void *params, void *stream);
 
 /* ---- row-panel sharded gemm_strided over the GPUs of one node, ONE process ---------------------------------------
  * Laser partitions M across its OpenMP threads with no cross-thread reduction (gemm.nim:160-176: `omp for` over the

@@ -10,7 +10,7 @@ ABI_VERSION = 3   # include/laser_hip.h LASER_HIP_ABI_VERSION this mirror was wr
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "liblaser_hip.so")
 
-OK, E_INVALID, E_HIP, E_NODEVICE, E_HANDLE = 0, 1, 2, 3, 4
+OK, E_INVALID, E_HIP, E_NODEVICE, E_HANDLE, E_COMPILE = 0, 1, 2, 3, 4, 5
 F32_LASER_ORDER, F32_FAST = 0, 1
 
 _CT = {"f32": C.c_float, "f64": C.c_double, "i32": C.c_int32, "i64": C.c_int64}
@@ -114,6 +114,11 @@ def lib():
     L.laser_hip_storage_download_stream.argtypes = [vp, vp, i64, vp]
     for b in ("b32", "b64"):
         getattr(L, f"laser_hip_copy_strided_{b}_dev").argtypes = [vp, C.POINTER(i64), vp, C.POINTER(i64), C.POINTER(i64), ci, vp]
+    spec = [C.c_char_p, ci, C.POINTER(C.c_char_p), C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(C.c_char_p), C.POINTER(ci)]
+    L.laser_hip_foreach_source.argtypes = spec + [vp, i64, C.POINTER(i64)]
+    L.laser_hip_foreach_code.argtypes = spec + [C.c_char_p, vp, i64, C.POINTER(i64)]
+    L.laser_hip_foreach_kernel.argtypes = spec + [C.POINTER(i64)]
+    L.laser_hip_foreach_dev.argtypes = [i64, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), ci, vp, vp]
     L.laser_hip_cblas_sgemm.argtypes = [ci, ci, ci, i64, i64, i64, C.c_float, vp, i64, vp, i64, C.c_float, vp, i64]
     L.laser_hip_cblas_dgemm.argtypes = [ci, ci, ci, i64, i64, i64, C.c_double, vp, i64, vp, i64, C.c_double, vp, i64]
     _lib = L
@@ -146,7 +151,8 @@ def declared_symbols():
              "laser_hip_storage_alloc_stream", "laser_hip_storage_upload_stream", "laser_hip_storage_download_stream",
              "laser_hip_copy_strided_b32_dev", "laser_hip_copy_strided_b64_dev",
              "laser_hip_host_alloc", "laser_hip_host_free", "laser_hip_host_register", "laser_hip_host_unregister",
-             "laser_hip_shard_plan", "laser_hip_set_shard_devices", "laser_hip_get_shard_devices"]
+             "laser_hip_shard_plan", "laser_hip_set_shard_devices", "laser_hip_get_shard_devices",
+             "laser_hip_foreach_source", "laser_hip_foreach_code", "laser_hip_foreach_kernel", "laser_hip_foreach_dev"]
     for s in _CT:
         names += [f"laser_hip_gemm_strided_{s}", f"laser_hip_gemm_strided_{s}_dev",
                   f"laser_hip_gemm_strided_batched_{s}_dev", f"laser_hip_gemm_packed_{s}",

@@ -1478,6 +1478,10 @@ int api_fail(int code, const char *fmt, ...) {
   g_err = buf;
   return code;
 }
+int api_fail_text(int code, const std::string &text) {
+  g_err = text;
+  return code;
+}
 int api_ensure_init() { return ensure_init(); }
 void api_set_thread_device(int device) { tl_device = device; }
 void api_set_thread_f32_config(int cfg) { tl_f32_cfg = cfg; }
@@ -1623,6 +1627,8 @@ int laser_hip_get_option(const char *name, int64_t *value) {
   else if (n == "i64_mfma") *value = g_ctx.i64_mfma;
   else if (n == "narrow_mfma") *value = g_ctx.narrow_mfma;
   else if (n == "last_narrow_mfma") *value = g_last_narrow_mfma;
+  else if (n == "foreach_compiles") *value = api_foreach_compiles();
+  else if (n == "last_foreach_variant") *value = api_last_foreach_variant();
   else if (n == "conv_implicit") *value = g_ctx.conv_implicit;
   else if (n == "conv_patch") *value = g_conv_patch;
   else if (n == "conv_direct") *value = g_conv_direct;

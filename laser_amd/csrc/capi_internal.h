@@ -3,9 +3,13 @@
 #pragma once
 #include <stdint.h>
 
+#include <string>
+
 namespace laser_hip {
 // set the thread-local error message (printf-style) and return `code`
 int api_fail(int code, const char *fmt, ...);
+// the same with a message of any length (a compiler log)
+int api_fail_text(int code, const std::string &text);
 int api_ensure_init();
 // The device the host-pointer entry points use ON THIS THREAD (-1 = the library's default device).  The sharded
 // host path sets it in its per-GPU worker threads.
@@ -22,4 +26,7 @@ int64_t api_shard_rccl_ranks();
 template <typename T>
 int api_sharded_host(int ndev, int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA, int64_t csA, const T *B,
                      int64_t rsB, int64_t csB, T beta, T *C, int64_t rsC, int64_t csC);
+// foreach.cpp: hiprtc compiles made in this process, and the kernel variant of the last laser_hip_foreach_dev launch
+int64_t api_foreach_compiles();
+int api_last_foreach_variant();
 }  // namespace laser_hip

@@ -532,3 +532,73 @@ proc gemm_strided*[T: SomeNumber](
     check laser_hip_gemm_strided_i16_dev(M, N, K, int32(cast[int16](alpha)), pointer(A), rowStrideA, colStrideA, pointer(B), rowStrideB, colStrideB, int32(cast[int16](beta)), pointer(C), rowStrideC, colStrideC, stream)
   else:
     {.error: "laser_hip: unsupported element type " & $T.}
+
+# ---- forEach with a body (include/laser_hip.h "forEach with a body"): foreach.nim:192-264 on device buffers ----------
+# The body is HIP C++ compiled at run time (Laser's `x += y * z` statements are valid C++).  Translating a Nim AST body
+# to C++ is not done here: the body is a string.
+proc laser_hip_foreach_source(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, buf: pointer, cap: int64, len: ptr int64): cint {.lh, importc: "laser_hip_foreach_source".}
+proc laser_hip_foreach_code(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, arch: cstring, buf: pointer, cap: int64, len: ptr int64): cint {.lh, importc: "laser_hip_foreach_code".}
+proc laser_hip_foreach_kernel(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, handle: ptr int64): cint {.lh, importc: "laser_hip_foreach_kernel".}
+proc laser_hip_foreach_dev(handle: int64, ptrs: ptr pointer, strides: ptr int64, shape: ptr int64, rank: cint, params: pointer, stream: pointer): cint {.lh, importc: "laser_hip_foreach_dev".}
+
+type
+  ForEachOperand* = object
+    name*: string
+    dtype*: cint                 # LASER_HIP_DT_*
+    writable*: bool
+    data*: pointer               # a device address
+    strides*: seq[int]           # element strides over the iteration shape (0 = broadcast, read-only operands only)
+  ForEachParam* = object
+    name*: string
+    dtype*: cint
+    slot*: uint64                # the value in the low bytes
+
+func dtypeCode*(T: typedesc): cint =
+  when T is float32: 0
+  elif T is float64: 1
+  elif T is int8: 2
+  elif T is int16: 3
+  elif T is int32: 4
+  elif T is int64 or T is int: 5
+  elif T is uint8: 6
+  elif T is uint16: 7
+  elif T is uint32: 8
+  elif T is uint64 or T is uint: 9
+  else: {.error: "laser_hip: unsupported element type " & $T.}
+
+func operand*[T](name: string, p: DevicePtr[T], strides: openarray[int], writable = false): ForEachOperand =
+  ForEachOperand(name: name, dtype: dtypeCode(T), writable: writable, data: pointer(p), strides: @strides)
+
+func param*[T: SomeNumber](name: string, value: T): ForEachParam =
+  result = ForEachParam(name: name, dtype: dtypeCode(T))
+  copyMem(result.slot.addr, value.unsafeAddr, sizeof(T))
+
+proc forEachDevice*(body: string, operands: openarray[ForEachOperand], shape: openarray[int],
+                    params: openarray[ForEachParam] = [], stream: pointer = nil) =
+  ## `forEach x in a, y in b: <body>` over device buffers: every operand has one stride per dimension of `shape`.
+  doAssert operands.len >= 1 and shape.len >= 1, "forEachDevice: at least one operand and one dimension"
+  var names, pnames: seq[cstring]
+  var dtypes, writable, pdtypes: seq[cint]
+  var ptrs: seq[pointer]
+  var strides: seq[int64]
+  var slots: seq[uint64]
+  for o in operands:
+    doAssert o.strides.len == shape.len, "forEachDevice: operand " & o.name & " needs one stride per dimension"
+    names.add cstring(o.name)
+    dtypes.add o.dtype
+    writable.add cint(ord(o.writable))
+    ptrs.add o.data
+    for s in o.strides: strides.add int64(s)
+  for p in params:
+    pnames.add cstring(p.name)
+    pdtypes.add p.dtype
+    slots.add p.slot
+  pnames.add nil   # keeps [0] addressable without parameters
+  pdtypes.add 0
+  slots.add 0
+  var handle: int64
+  check laser_hip_foreach_kernel(cstring(body), cint(operands.len), names[0].addr, dtypes[0].addr, writable[0].addr,
+                                 cint(params.len), pnames[0].addr, pdtypes[0].addr, handle.addr)
+  var shp = newSeq[int64](shape.len)
+  for i, s in shape: shp[i] = int64(s)
+  check laser_hip_foreach_dev(handle, ptrs[0].addr, strides[0].addr, shp[0].addr, cint(shape.len), slots[0].addr, stream)
