@@ -62,7 +62,6 @@ struct Context {
   // call is in flight applies to that call or the next, never tears)
   std::atomic<int> float_mode{LASER_HIP_F32_LASER_ORDER};
   std::atomic<int> f32_cfg{-1};
-  hipStream_t s_up = nullptr, s_comp = nullptr;  // host-pointer pipeline: uploads / kernels
   std::atomic<bool> f64_mfma{true};       // float64 GEMM on the f64 matrix cores (false: VALU kernel)
   std::atomic<bool> i32_mfma{true};       // int32 GEMM on the int8 matrix cores (false: VALU kernel)
   std::atomic<bool> i64_mfma{true};       // int64 GEMM on the int8 matrix cores (false: VALU kernel)
@@ -607,140 +606,37 @@ int gemm_dev(int64_t batch, int64_t M, int64_t N, int64_t K, T alpha, const T *A
   return LASER_HIP_OK;
 }
 
-// Row-panel pipelined host path (see gemm_host).  dA0/dB0/dC0 are the device addresses of element
-// (0,0) of each operand inside the cached scratch; Bspan/bn = host span of B; dBbuf = its device copy.
+// Pipelined host path (see gemm_host): row panels of A (R rows) x column panels of B (W columns; W >= N is one column
+// panel).  The uploads grow the computable region as a square -- B_0, A_0, then whichever of the next A row panel / B
+// column panel keeps (rows up)/M ~ (cols up)/N -- so the first tile multiplies after one panel of each.  Every upload
+// releases a row or column STRIP of C as one launch (the new row panel x every column already up, or the new column
+// panel x every row already up: 12 launches at 8192^3, growing with what is on the device -- one launch per TILE left
+// three quarters of the chip idle, 17.7 ms vs 15.5 ms for row panels only), and a helper thread copies every finished
+// strip back while later panels are still arriving (PCIe is full duplex).  Elements of C are independent and each is ONE
+// chain over all of K, so the arithmetic is unchanged.  With one column panel all of B goes first and each A row panel
+// releases a full-width strip.
+// Row panels of A and C and full-width strips are span copies with the caller's strides: the row panels must not
+// overlap, strides may otherwise be negative or non-unit.  More than one column panel needs unit column strides: the
+// column panels of B and the partial-width strips of C are pitched 2-D copies.  dA0/dB0/dC0 are the device addresses of
+// element (0,0) of each operand inside the cached scratch.
 template <typename T>
-int gemm_host_pipelined(int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA, int64_t csA, const T *Bspan,
-                        size_t bn, int64_t rsB, int64_t csB, T beta, T *C, int64_t rsC, int64_t csC, const T *dA0,
-                        const T *dB0, T *dBbuf, T *dC0, bool c_up) {
+int gemm_host_pipelined(int64_t M, int64_t N, int64_t K, int64_t R, int64_t W, T alpha, const T *A, int64_t rsA,
+                        int64_t csA, const T *B, int64_t rsB, int64_t csB, T beta, T *C, int64_t rsC, int64_t csC,
+                        const T *dA0, const T *dB0, T *dC0, bool c_up) {
   if (int rc = pipeline_streams()) return rc;
   DeviceCtx &D = *tl_dev;
-  int64_t R = (M / 8 + 255) / 256 * 256;  // ~8 panels, whole 256-row tiles
-  if (R < 256) R = 256;
-  const int nchunks = (int)((M + R - 1) / R);
-  std::vector<hipEvent_t> ev_up(nchunks), ev_comp(nchunks);
-  for (int i = 0; i < nchunks; i++) {
-    HIP_TRY(hipEventCreateWithFlags(&ev_up[i], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&ev_comp[i], hipEventDisableTiming));
-  }
+  const int nI = (int)((M + R - 1) / R), nJ = (int)((N + W - 1) / W);
   const int64_t ca = (K - 1) * csA, cc = (N - 1) * csC;
-  auto a_span = [&](int64_t r0, int64_t r1, int64_t *lo, int64_t *hi) {
-    *lo = r0 * rsA + std::min<int64_t>(0, ca);
-    *hi = (r1 - 1) * rsA + std::max<int64_t>(0, ca);
+  // rows [r0, r1) of A or C (c = offset of the last column from the first) as one span copy between element-(0,0) pointers
+  auto copy_rows = [](T *dst, const T *src, int64_t r0, int64_t r1, int64_t rs, int64_t c, hipMemcpyKind kind, hipStream_t s) {
+    const int64_t lo = r0 * rs + std::min<int64_t>(0, c), hi = (r1 - 1) * rs + std::max<int64_t>(0, c);
+    return hipMemcpyAsync(dst + lo, src + lo, (size_t)(hi - lo + 1) * sizeof(T), kind, s);
   };
-  auto c_span = [&](int64_t r0, int64_t r1, int64_t *lo, int64_t *hi) {
-    *lo = r0 * rsC + std::min<int64_t>(0, cc);
-    *hi = (r1 - 1) * rsC + std::max<int64_t>(0, cc);
-  };
-
-  // helper thread: copy finished C panels back while the main thread keeps uploading
-  std::mutex qm;
-  std::condition_variable qcv;
-  std::deque<int> queue;
-  bool closed = false;
-  hipError_t down_err = hipSuccess;
-  const int device = D.device;
-  const hipStream_t s_down = D.s_down;
-  std::thread downloader([&]() {
-    (void)hipSetDevice(device);
-    for (;;) {
-      int i;
-      {
-        std::unique_lock<std::mutex> lk(qm);
-        qcv.wait(lk, [&] { return !queue.empty() || closed; });
-        if (queue.empty()) return;
-        i = queue.front();
-        queue.pop_front();
-      }
-      const int64_t r0 = i * R, r1 = std::min<int64_t>(M, r0 + R);
-      int64_t lo, hi;
-      c_span(r0, r1, &lo, &hi);
-      // (asynchronous copy on its own stream + synchronise, not a blocking hipMemcpy: beside the uploads of s_up the
-      // blocking form gets 26 GB/s each way, this one 46 -- scripts/pcie_probe.py, pageable memory)
-      hipError_t e = hipEventSynchronize(ev_comp[i]);
-      if (e == hipSuccess) e = hipMemcpyAsync(C + lo, dC0 + lo, (size_t)(hi - lo + 1) * sizeof(T), hipMemcpyDeviceToHost, s_down);
-      if (e == hipSuccess) e = hipStreamSynchronize(s_down);
-      if (e != hipSuccess && down_err == hipSuccess) down_err = e;
-    }
-  });
-  auto finish = [&]() {
-    {
-      std::lock_guard<std::mutex> lk(qm);
-      closed = true;
-    }
-    qcv.notify_all();
-    downloader.join();
-    for (int i = 0; i < nchunks; i++) {
-      (void)hipEventDestroy(ev_up[i]);
-      (void)hipEventDestroy(ev_comp[i]);
-    }
-  };
-#define PIPE_TRY(expr)                                                                                        \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess) {                                                                                   \
-      finish();                                                                                               \
-      (void)hipDeviceSynchronize();                                                                           \
-      return fail(LASER_HIP_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    }                                                                                                         \
-  } while (0)
-
-  PIPE_TRY(hipMemcpyAsync(dBbuf, Bspan, bn * sizeof(T), hipMemcpyHostToDevice, D.s_up));
-  for (int i = 0; i < nchunks; i++) {
-    const int64_t r0 = i * R, r1 = std::min<int64_t>(M, r0 + R);
-    int64_t lo, hi;
-    a_span(r0, r1, &lo, &hi);
-    PIPE_TRY(hipMemcpyAsync((T *)dA0 + lo, A + lo, (size_t)(hi - lo + 1) * sizeof(T), hipMemcpyHostToDevice, D.s_up));
-    if (c_up) {
-      c_span(r0, r1, &lo, &hi);
-      PIPE_TRY(hipMemcpyAsync(dC0 + lo, C + lo, (size_t)(hi - lo + 1) * sizeof(T), hipMemcpyHostToDevice, D.s_up));
-    }
-    PIPE_TRY(hipEventRecord(ev_up[i], D.s_up));
-    PIPE_TRY(hipStreamWaitEvent(D.s_comp, ev_up[i], 0));
-    GemmArgs<T> a = make_args<T>(1, r1 - r0, N, K, alpha, dA0 + r0 * rsA, rsA, csA, 0, dB0, rsB, csB, 0, beta,
-                                 dC0 + r0 * rsC, rsC, csC, 0);
-    PIPE_TRY(run_gemm<T>(a, D.s_comp));
-    PIPE_TRY(hipEventRecord(ev_comp[i], D.s_comp));
-    {
-      std::lock_guard<std::mutex> lk(qm);
-      queue.push_back(i);
-    }
-    qcv.notify_one();
-  }
-#undef PIPE_TRY
-  finish();
-  if (down_err != hipSuccess) return fail(LASER_HIP_E_HIP, "D2H of a C panel failed: %s", hipGetErrorString(down_err));
-  return LASER_HIP_OK;
-}
-
-// 2-D pipelined host path: row panels of A x column panels of B.  The row-panel pipeline above cannot start a kernel
-// before ALL of B has crossed PCIe (8192^3: 4.7 of its ~14 ms); here B is cut into column panels as well and the
-// uploads grow the computable region as a square -- B_0, A_0, then whichever of the next A row panel / B column panel
-// keeps (rows up)/M ~ (cols up)/N -- so the first tile multiplies after one panel of each, every upload releases a row
-// or column STRIP of C as one launch (the new row panel x every column already up, or the new column panel x every row
-// already up: 12 launches at 8192^3, growing with what is on the device -- one launch per TILE left three quarters of
-// the chip idle, 17.7 ms vs 15.5 ms for the row-panel form), and every finished strip is copied back while later panels
-// are still arriving.  Elements of C are independent and each is ONE chain over all of K, so the arithmetic is unchanged.  Needs row-major-like
-// operands (unit column stride; the column panels of B and the tiles of C are pitched 2-D copies).
-template <typename T>
-int gemm_host_pipelined2d(int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA, const T *B, int64_t rsB, T beta,
-                          T *C, int64_t rsC, const T *dA0, const T *dB0, T *dC0, bool c_up) {
-  if (int rc = pipeline_streams()) return rc;
-  DeviceCtx &D = *tl_dev;
-  int64_t R = (M / 8 + 255) / 256 * 256;  // ~8 row panels of whole 256-row tiles
-  if (R < 256) R = 256;
-  const int nI = (int)((M + R - 1) / R);
-  int64_t W = (N / 4 + 255) / 256 * 256;  // ~4 column panels of whole 256-column tiles
-  if (W < 256) W = 256;
-  const int nJ = (int)((N + W - 1) / W);
-  // one strip of C per upload: the new row panel x every column already up, or the new column panel x every row already up
   struct Strip { int64_t r0, r1, c0, c1; hipEvent_t done; };
-  std::vector<Strip> strips;
-  strips.reserve((size_t)nI + nJ);
-  std::vector<hipEvent_t> ev_up;
+  std::vector<hipEvent_t> events;  // every event made here; finish destroys them
   std::mutex qm;
   std::condition_variable qcv;
-  std::deque<int> queue;
+  std::deque<Strip> queue;
   bool closed = false;
   hipError_t down_err = hipSuccess;
   const int device = D.device;
@@ -753,19 +649,20 @@ int gemm_host_pipelined2d(int64_t M, int64_t N, int64_t K, T alpha, const T *A, 
         std::unique_lock<std::mutex> lk(qm);
         qcv.wait(lk, [&] { return !queue.empty() || closed; });
         if (queue.empty()) return;
-        t = strips[queue.front()];
+        t = queue.front();
         queue.pop_front();
       }
+      // (asynchronous copy on its own stream + synchronise, not a blocking hipMemcpy: beside the uploads of s_up the
+      // blocking form gets 26 GB/s each way, this one 46 -- scripts/pcie_probe.py, pageable memory)
       hipError_t e = hipEventSynchronize(t.done);
       if (e == hipSuccess) {
-        // (asynchronous copies on their own stream + synchronise: see gemm_host_pipelined)
-        if (t.c0 == 0 && t.c1 == N)  // whole rows: one contiguous span
-          e = hipMemcpyAsync(C + t.r0 * rsC, dC0 + t.r0 * rsC, (size_t)((t.r1 - t.r0 - 1) * rsC + N) * sizeof(T), hipMemcpyDeviceToHost, s_down);
+        if (t.c0 == 0 && t.c1 == N)
+          e = copy_rows(C, dC0, t.r0, t.r1, rsC, cc, hipMemcpyDeviceToHost, s_down);
         else
           e = hipMemcpy2DAsync(C + t.r0 * rsC + t.c0, (size_t)rsC * sizeof(T), dC0 + t.r0 * rsC + t.c0, (size_t)rsC * sizeof(T),
                                (size_t)(t.c1 - t.c0) * sizeof(T), (size_t)(t.r1 - t.r0), hipMemcpyDeviceToHost, s_down);
-        if (e == hipSuccess) e = hipStreamSynchronize(s_down);
       }
+      if (e == hipSuccess) e = hipStreamSynchronize(s_down);
       if (e != hipSuccess && down_err == hipSuccess) down_err = e;
     }
   });
@@ -776,8 +673,12 @@ int gemm_host_pipelined2d(int64_t M, int64_t N, int64_t K, T alpha, const T *A, 
     }
     qcv.notify_all();
     downloader.join();
-    for (hipEvent_t e : ev_up) (void)hipEventDestroy(e);
-    for (Strip &t : strips) (void)hipEventDestroy(t.done);
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+  };
+  auto new_event = [&](hipEvent_t *ev) {
+    const hipError_t e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+    if (e == hipSuccess) events.push_back(*ev);
+    return e;
   };
 #define PIPE_TRY(expr)                                                                                        \
   do {                                                                                                        \
@@ -788,47 +689,45 @@ int gemm_host_pipelined2d(int64_t M, int64_t N, int64_t K, T alpha, const T *A, 
       return fail(LASER_HIP_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     }                                                                                                         \
   } while (0)
-  // one upload (row panel of A [+ of C when it is read], or column panel of B), then the strip of C it completes
   int a_up = 0, b_up = 0;
-  auto upload_and_launch = [&](bool is_a) -> int {
-    hipEvent_t ev;
-    PIPE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    ev_up.push_back(ev);
+  while (a_up < nI || b_up < nJ) {
+    // one upload: B first, then keep the uploaded fractions level (ties go to A: its panels are the cheaper, contiguous copies)
+    const bool take_b = b_up < nJ && (a_up >= nI || b_up == 0 || (int64_t)b_up * nI < (int64_t)a_up * nJ);
     Strip t;
-    if (is_a) {
-      t.r0 = a_up * R; t.r1 = std::min<int64_t>(M, t.r0 + R);
-      t.c0 = 0; t.c1 = std::min<int64_t>(N, b_up * W);
-      PIPE_TRY(hipMemcpyAsync((T *)dA0 + t.r0 * rsA, A + t.r0 * rsA, (size_t)((t.r1 - t.r0 - 1) * rsA + K) * sizeof(T), hipMemcpyHostToDevice, D.s_up));
-      if (c_up)
-        PIPE_TRY(hipMemcpyAsync(dC0 + t.r0 * rsC, C + t.r0 * rsC, (size_t)((t.r1 - t.r0 - 1) * rsC + N) * sizeof(T), hipMemcpyHostToDevice, D.s_up));
-      a_up++;
-    } else {
+    if (take_b) {
       t.c0 = b_up * W; t.c1 = std::min<int64_t>(N, t.c0 + W);
       t.r0 = 0; t.r1 = std::min<int64_t>(M, a_up * R);
-      PIPE_TRY(hipMemcpy2DAsync((T *)dB0 + t.c0, (size_t)rsB * sizeof(T), B + t.c0, (size_t)rsB * sizeof(T), (size_t)(t.c1 - t.c0) * sizeof(T),
-                                (size_t)K, hipMemcpyHostToDevice, D.s_up));
+      if (nJ == 1) {  // all of B: its span, whatever its strides
+        int64_t blo, bhi;
+        view_span(K, N, rsB, csB, &blo, &bhi);
+        PIPE_TRY(hipMemcpyAsync((T *)dB0 + blo, B + blo, (size_t)(bhi - blo + 1) * sizeof(T), hipMemcpyHostToDevice, D.s_up));
+      } else {
+        PIPE_TRY(hipMemcpy2DAsync((T *)dB0 + t.c0, (size_t)rsB * sizeof(T), B + t.c0, (size_t)rsB * sizeof(T), (size_t)(t.c1 - t.c0) * sizeof(T),
+                                  (size_t)K, hipMemcpyHostToDevice, D.s_up));
+      }
       b_up++;
+    } else {  // a row panel of A, and of C when it is read
+      t.r0 = a_up * R; t.r1 = std::min<int64_t>(M, t.r0 + R);
+      t.c0 = 0; t.c1 = std::min<int64_t>(N, b_up * W);
+      PIPE_TRY(copy_rows((T *)dA0, A, t.r0, t.r1, rsA, ca, hipMemcpyHostToDevice, D.s_up));
+      if (c_up) PIPE_TRY(copy_rows(dC0, C, t.r0, t.r1, rsC, cc, hipMemcpyHostToDevice, D.s_up));
+      a_up++;
     }
-    if (t.r1 <= t.r0 || t.c1 <= t.c0) return LASER_HIP_OK;  // the very first upload has no partner yet
-    PIPE_TRY(hipEventRecord(ev, D.s_up));
-    PIPE_TRY(hipStreamWaitEvent(D.s_comp, ev, 0));  // s_up is in order: this event covers every earlier upload too
-    GemmArgs<T> a = make_args<T>(1, t.r1 - t.r0, t.c1 - t.c0, K, alpha, dA0 + t.r0 * rsA, rsA, 1, 0, dB0 + t.c0, rsB, 1, 0, beta,
-                                 dC0 + t.r0 * rsC + t.c0, rsC, 1, 0);
+    if (t.r1 <= t.r0 || t.c1 <= t.c0) continue;  // the very first upload has no partner yet
+    hipEvent_t up;
+    PIPE_TRY(new_event(&up));
+    PIPE_TRY(hipEventRecord(up, D.s_up));
+    PIPE_TRY(hipStreamWaitEvent(D.s_comp, up, 0));  // s_up is in order: this event covers every earlier upload too
+    GemmArgs<T> a = make_args<T>(1, t.r1 - t.r0, t.c1 - t.c0, K, alpha, dA0 + t.r0 * rsA, rsA, csA, 0, dB0 + t.c0 * csB, rsB, csB, 0,
+                                 beta, dC0 + t.r0 * rsC + t.c0 * csC, rsC, csC, 0);
     PIPE_TRY(run_gemm<T>(a, D.s_comp));
-    PIPE_TRY(hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
+    PIPE_TRY(new_event(&t.done));
     PIPE_TRY(hipEventRecord(t.done, D.s_comp));
     {
       std::lock_guard<std::mutex> lk(qm);
-      strips.push_back(t);
-      queue.push_back((int)strips.size() - 1);
+      queue.push_back(t);
     }
     qcv.notify_one();
-    return LASER_HIP_OK;
-  };
-  while (a_up < nI || b_up < nJ) {
-    // B first, then keep the uploaded fractions level (ties go to A: its panels are the cheaper, contiguous copies)
-    const bool take_b = b_up < nJ && (a_up >= nI || b_up == 0 || (int64_t)b_up * nI < (int64_t)a_up * nJ);
-    if (int rc = upload_and_launch(!take_b)) return rc;
   }
 #undef PIPE_TRY
   finish();
@@ -923,10 +822,8 @@ int gemm_host(int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA,
   const T *dA0 = (const T *)dA - alo, *dB0 = (const T *)dB - blo;
   T *dC0 = (T *)dC - clo;
 
-  // Large row-major-like problems: stream row panels so PCIe and the kernel overlap (rows of C are
-  // independent, so the per-element arithmetic is unchanged):
-  //   main thread : H2D B, then per panel  H2D A_i [+ C_i]  ->  kernel_i on its own stream
-  //   helper thread: D2H C_i as soon as kernel_i is done (PCIe is full duplex)
+  // Large problems: stream panels so PCIe and the kernel overlap (gemm_host_pipelined).  Row panels only need rows of A
+  // and C that do not overlap.
   auto iabs = [](int64_t v) { return v < 0 ? -v : v; };
   const bool panels_disjoint = rsA > 0 && rsC > 0 && rsA >= iabs(csA) * (K - 1) + 1 && rsC >= iabs(csC) * (N - 1) + 1;
   // fused epilogue: hepi->bias is a HOST view here; its span goes to the device next to the operands
@@ -943,10 +840,12 @@ int gemm_host(int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA,
       depi.bias = (const T *)dbias - lo;
     }
   }
-  // both operands and C row-major-like, and big enough that B's upload is worth hiding: the 2-D form.  Pinned (or
-  // registered) B and C only: their column panels / strips move as pitched 2-D copies, which are DMA transfers from
+  const int64_t R = std::max<int64_t>(256, (M / 8 + 255) / 256 * 256);  // ~8 row panels of whole 256-row tiles
+  const int64_t W = std::max<int64_t>(256, (N / 4 + 255) / 256 * 256);  // ~4 column panels of whole 256-column tiles
+  // both operands and C row-major-like, and big enough that B's upload is worth hiding: column panels as well.  Pinned
+  // (or registered) B and C only: their column panels / strips move as pitched 2-D copies, which are DMA transfers from
   // pinned memory but row-by-row staging from pageable memory (8192^3: 15.0 ms in one harness, 23 ms in another, against
-  // 15.7 ms for the row-panel form -- profiles/r02/host_pipeline_v2.jsonl, configs_v19.jsonl)
+  // 15.7 ms for row panels only -- profiles/r02/host_pipeline_v2.jsonl, configs_v19.jsonl)
   auto pinned = [](const void *p) {
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, p) != hipSuccess) {
@@ -957,10 +856,9 @@ int gemm_host(int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA,
   };
   if (!fused && g_ctx.host_pipeline_2d && pinned(B) && pinned(C) && csA == 1 && csB == 1 && csC == 1 && rsA >= K && rsB >= N && rsC >= N && M >= 2048 &&
       N >= 2048 && bn * sizeof(T) >= ((size_t)32 << 20) && (an + bn + cn) * sizeof(T) >= ((size_t)128 << 20))
-    return gemm_host_pipelined2d<T>(M, N, K, alpha, A, rsA, B, rsB, beta, C, rsC, dA0, dB0, dC0, c_up);
-  if (!fused && panels_disjoint && M >= 2048 && (an + bn + cn) * sizeof(T) >= ((size_t)64 << 20))
-    return gemm_host_pipelined<T>(M, N, K, alpha, A, rsA, csA, B + blo, bn, rsB, csB, beta, C, rsC, csC, dA0, dB0,
-                                  (T *)dB, dC0, c_up);
+    return gemm_host_pipelined<T>(M, N, K, R, W, alpha, A, rsA, csA, B, rsB, csB, beta, C, rsC, csC, dA0, dB0, dC0, c_up);
+  if (!fused && panels_disjoint && M >= 2048 && (an + bn + cn) * sizeof(T) >= ((size_t)64 << 20))  // row panels only
+    return gemm_host_pipelined<T>(M, N, K, R, N, alpha, A, rsA, csA, B, rsB, csB, beta, C, rsC, csC, dA0, dB0, dC0, c_up);
 
   HIP_TRY(hipMemcpy(dA, A + alo, an * sizeof(T), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(dB, B + blo, bn * sizeof(T), hipMemcpyHostToDevice));
