@@ -400,39 +400,99 @@ ForEachParam param(const char *name, T value) {
   std::memcpy(&p.slot, &value, sizeof(T));
   return p;
 }
-inline void forEach(const std::string &body, const std::vector<ForEachOperand> &ops, const std::vector<ForEachParam> &params = {},
-                    void *stream = nullptr) {
-  if (ops.empty()) throw Error(LASER_HIP_E_INVALID, "forEach: no operand");
+// the spec arrays and launch arrays of a forEach / forEachReduce call (numpy broadcasting of the read-only operands)
+struct ForEachCall {
   std::vector<const char *> names, pnames;
   std::vector<int> dtypes, writable, pdtypes;
   std::vector<void *> ptrs;
   std::vector<uint64_t> slots;
-  std::vector<int64_t> strides;
-  const std::vector<int64_t> &shape = ops[0].shape;
-  const int r = (int)shape.size();
-  for (const ForEachOperand &o : ops) {
-    names.push_back(o.name.c_str());
-    dtypes.push_back(o.dtype);
-    writable.push_back(o.writable);
-    ptrs.push_back(o.ptr);
-    const int pad = r - (int)o.shape.size();
-    if (pad < 0 || (o.writable && o.shape != shape))
-      throw Error(LASER_HIP_E_INVALID, ("forEach: operand " + o.name + " does not fit the iteration shape").c_str());
-    for (int d = 0; d < r; d++) {  // numpy broadcasting: missing / extent-1 dimensions get stride 0
-      const int64_t e = d < pad ? 1 : o.shape[d - pad];
-      if (e != shape[d] && e != 1) throw Error(LASER_HIP_E_INVALID, ("forEach: operand " + o.name + " does not broadcast").c_str());
-      strides.push_back(d < pad || (e == 1 && !o.writable) ? 0 : o.strides[d - pad]);
+  std::vector<int64_t> strides, shape;
+  ForEachCall(const char *what, const std::vector<ForEachOperand> &ops, const std::vector<ForEachParam> &params) {
+    if (ops.empty()) throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": no operand").c_str());
+    shape = ops[0].shape;
+    const int r = (int)shape.size();
+    for (const ForEachOperand &o : ops) {
+      names.push_back(o.name.c_str());
+      dtypes.push_back(o.dtype);
+      writable.push_back(o.writable);
+      ptrs.push_back(o.ptr);
+      const int pad = r - (int)o.shape.size();
+      if (pad < 0 || (o.writable && o.shape != shape))
+        throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": operand " + o.name + " does not fit the iteration shape").c_str());
+      for (int d = 0; d < r; d++) {  // numpy broadcasting: missing / extent-1 dimensions get stride 0
+        const int64_t e = d < pad ? 1 : o.shape[d - pad];
+        if (e != shape[d] && e != 1)
+          throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": operand " + o.name + " does not broadcast").c_str());
+        strides.push_back(d < pad || (e == 1 && !o.writable) ? 0 : o.strides[d - pad]);
+      }
+    }
+    for (const ForEachParam &p : params) {
+      pnames.push_back(p.name.c_str());
+      pdtypes.push_back(p.dtype);
+      slots.push_back(p.slot);
     }
   }
-  for (const ForEachParam &p : params) {
-    pnames.push_back(p.name.c_str());
-    pdtypes.push_back(p.dtype);
-    slots.push_back(p.slot);
-  }
+};
+inline void forEach(const std::string &body, const std::vector<ForEachOperand> &ops, const std::vector<ForEachParam> &params = {},
+                    void *stream = nullptr) {
+  ForEachCall c("forEach", ops, params);
   int64_t handle = 0;
-  check(laser_hip_foreach_kernel(body.c_str(), (int)ops.size(), names.data(), dtypes.data(), writable.data(), (int)params.size(),
-                                 pnames.data(), pdtypes.data(), &handle));
-  check(laser_hip_foreach_dev(handle, ptrs.data(), strides.data(), shape.data(), r, slots.data(), stream));
+  check(laser_hip_foreach_kernel(body.c_str(), (int)ops.size(), c.names.data(), c.dtypes.data(), c.writable.data(),
+                                 (int)params.size(), c.pnames.data(), c.pdtypes.data(), &handle));
+  check(laser_hip_foreach_dev(handle, c.ptrs.data(), c.strides.data(), c.shape.data(), (int)c.shape.size(), c.slots.data(), stream));
+}
+
+// ---- reductions (include/laser_hip.h "Reductions"): reductions.nim:48-116 over a device Tensor, in the fixed order ------
+//   float s = laser::reduce_sum(t);     (synchronous: the one value comes back to the host)
+template <typename T>
+T reduce(int op, const Tensor<T> &t, void *stream = nullptr) {
+  static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value || std::is_same<T, int32_t>::value ||
+                    std::is_same<T, int64_t>::value, "reductions: float, double, int32_t or int64_t");
+  void *d = nullptr;
+  check(laser_hip_storage_alloc_stream(&d, sizeof(T), stream));
+  const int r = (int)t.shape.size();
+  int rc;
+#define LASER_REDUCE_CALL(SFX, U)                                                                                     \
+  rc = op == 0 ? laser_hip_reduce_sum_##SFX##_dev((const U *)t.unsafe_raw_data(), t.strides.data(), t.shape.data(), r, (U *)d, stream) \
+     : op == 1 ? laser_hip_reduce_min_##SFX##_dev((const U *)t.unsafe_raw_data(), t.strides.data(), t.shape.data(), r, (U *)d, stream) \
+               : laser_hip_reduce_max_##SFX##_dev((const U *)t.unsafe_raw_data(), t.strides.data(), t.shape.data(), r, (U *)d, stream);
+  if constexpr (std::is_same<T, float>::value) { LASER_REDUCE_CALL(f32, float) }
+  else if constexpr (std::is_same<T, double>::value) { LASER_REDUCE_CALL(f64, double) }
+  else if constexpr (std::is_same<T, int32_t>::value) { LASER_REDUCE_CALL(i32, int32_t) }
+  else { LASER_REDUCE_CALL(i64, int64_t) }
+#undef LASER_REDUCE_CALL
+  T v{};
+  if (rc == LASER_HIP_OK) rc = laser_hip_storage_download_stream(&v, d, sizeof(T), stream);
+  laser_hip_storage_free(d);
+  check(rc);
+  return v;
+}
+template <typename T> T reduce_sum(const Tensor<T> &t, void *stream = nullptr) { return reduce<T>(0, t, stream); }
+template <typename T> T reduce_min(const Tensor<T> &t, void *stream = nullptr) { return reduce<T>(1, t, stream); }
+template <typename T> T reduce_max(const Tensor<T> &t, void *stream = nullptr) { return reduce<T>(2, t, stream); }
+
+// ---- forEachReduce (include/laser_hip.h "forEachReduce"): forEachStaged (foreach_staged.nim:318) over device Tensors ------
+//   double dot = laser::forEachReduce<double>("acc += x * y", "acc += other", 0.0, {laser::in("x", tx), laser::in("y", ty)});
+// The accumulator type is Acc; `init` must be an identity of `merge`.  Synchronous (returns the value).
+template <typename Acc>
+Acc forEachReduce(const std::string &body, const std::string &merge, Acc init, const std::vector<ForEachOperand> &ops,
+                  const std::vector<ForEachParam> &params = {}, const char *acc_name = "acc", void *stream = nullptr) {
+  ForEachCall c("forEachReduce", ops, params);
+  int64_t handle = 0;
+  check(laser_hip_foreach_reduce_kernel(body.c_str(), (int)ops.size(), c.names.data(), c.dtypes.data(), c.writable.data(),
+                                        (int)params.size(), c.pnames.data(), c.pdtypes.data(), acc_name, dtype_code<Acc>(),
+                                        merge.c_str(), &handle));
+  uint64_t slot = 0;
+  std::memcpy(&slot, &init, sizeof(Acc));
+  void *d = nullptr;
+  check(laser_hip_storage_alloc_stream(&d, sizeof(Acc), stream));
+  int rc = laser_hip_foreach_reduce_dev(handle, c.ptrs.data(), c.strides.data(), c.shape.data(), (int)c.shape.size(),
+                                        c.slots.data(), &slot, d, stream);
+  Acc v{};
+  if (rc == LASER_HIP_OK) rc = laser_hip_storage_download_stream(&v, d, sizeof(Acc), stream);
+  laser_hip_storage_free(d);
+  check(rc);
+  return v;
 }
 
 #undef LASER_DISPATCH

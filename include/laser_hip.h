@@ -161,8 +161,10 @@ int laser_hip_f32_config_count(void);
  *   "last_conv_tail"   how the last convolution's pixel tail ran: 0 no tail, 1 the direct tail kernel, 2 kc slices + combine, 3 one
  *                      compiler-kernel launch
  *   "last_split"       column where the last compiler-scheduled float GEMM / conv launch was cut into main + tail (0 = one launch)
- *   "foreach_compiles" hiprtc compiles of forEach bodies made by this process
- *   "last_foreach_variant"  kernel of the last laser_hip_foreach_dev launch: 0 contiguous vectorised, 1 contiguous scalar, 2 strided */
+ *   "foreach_compiles" hiprtc compiles of forEach and forEachReduce bodies made by this process
+ *   "last_foreach_variant"  kernel of the last laser_hip_foreach_dev / foreach_reduce_dev launch: 0 contiguous vectorised, 1 contiguous
+ *                      scalar, 2 strided
+ *   "last_reduce_variant"  traversal of the last laser_hip_reduce_* call: 0 contiguous vectorised, 1 contiguous scalar, 2 strided */
 int laser_hip_set_option(const char *name, int value);
 int laser_hip_get_option(const char *name, int64_t *value);
 const char *laser_hip_f32_config_name(int cfg);
@@ -521,7 +523,7 @@ LASER_HIP_DECL_MAP(i64, int64_t)
  *                  16 bytes of the widest operand's vector -> 16-byte loads / stores per lane; 1 = contiguous with an
  *                  unaligned base; 2 = strided (dimensions merged as map_strided does).
  * Errors: LASER_HIP_E_COMPILE when the body does not compile or hiprtc cannot be loaded -- laser_hip_last_error() holds the
- * compiler's log.  get_option "foreach_compiles": hiprtc compiles made by this process. */
+ * compiler's log.  get_option "foreach_compiles": hiprtc compiles made by this process (forEachReduce's included). */
 #define LASER_HIP_DT_F32 0
 #define LASER_HIP_DT_F64 1
 #define LASER_HIP_DT_I8 2
@@ -543,6 +545,77 @@ int laser_hip_foreach_kernel(const char *body, int nops, const char *const *name
                              const int *param_dtypes, int64_t *handle);
 int laser_hip_foreach_dev(int64_t handle, void *const *ptrs, const int64_t *strides, const int64_t *shape, int rank,
                           const void *params, void *stream);
+
+/* ---- Reductions: laser/primitives/reductions.nim:48-116 (reduce_sum / reduce_min / reduce_max) --------------------
+ * One number from a strided device view.  Unlike the reference's OpenMP sum, which "can give different results depending
+ * on thread timings", the order of the operations is fixed: it is a function of the element count alone, never of the
+ * device, the CU count, the grid, the stream, the base alignment or the strides.  In words:
+ *   x[0..n) are the elements in the row-major logical order of `shape`.  E = 16 / (bytes of the widest operand): 4 for f32
+ *   and i32, 2 for f64 and i64, 16 for int8.  W = LASER_HIP_REDUCE_LANES, R = LASER_HIP_REDUCE_STEPS; a chunk is S = R*W*E
+ *   elements.  In chunk c, lane t keeps E accumulators, each starting at `init`; for r = 0..R-1, then j = 0..E-1, it
+ *   applies the body to element c*S + r*W*E + t*E + j and accumulator j; elements at or past n are skipped.  The E
+ *   accumulators are folded by halving (the upper half merged onto the lower half, repeated), then the W lane results the
+ *   same way (lane t with t + W/2, then t + W/4, ...): the chunk's partial.  More than one chunk: the array of partials is
+ *   reduced by the same rule with E = 16 / (bytes of the accumulator) and `merge` as the body, until one value is left.
+ *   n = 0 gives `init`.  No float atomics: partials are plain stores into stream-ordered scratch, one launch per level.
+ * reduce_sum accumulates in the element type (no denormal flushing; integers wrap mod 2^n like numpy's sum with
+ * dtype = the element type).  reduce_min / reduce_max do not depend on the order at all: any NaN gives NaN (payload
+ * unspecified), -0 ranks below +0 (min {+0, -0} = -0, max = +0), otherwise the true min / max.  Empty: sum 0, min +Inf /
+ * the integer type's max, max -Inf / its min.
+ * _dev forms: asynchronous on `stream`, never synchronise the host; rank <= 6 ELEMENT strides, negative and 0 (broadcast)
+ * allowed; the result goes to the device address d_out.  get_option "last_reduce_variant": 0 = C-contiguous, 16-byte
+ * aligned (one 16-byte vector per lane and step), 1 = contiguous with an unaligned base, 2 = strided -- same bits all three.
+ * Host form (f32): the reference's `reduce_*(data: ptr float32, len: Natural): float32` -- synchronous, result in *out,
+ * the same bits as the _dev form on the same values.  No gfx950 device: LASER_HIP_E_NODEVICE. */
+#define LASER_HIP_REDUCE_LANES 256
+#define LASER_HIP_REDUCE_STEPS 8
+#define LASER_HIP_DECL_REDUCE(SFX, T)                                                                                  \
+  int laser_hip_reduce_sum_##SFX##_dev(const T *d_src, const int64_t *strides, const int64_t *shape, int rank,          \
+                                       T *d_out, void *stream);                                                        \
+  int laser_hip_reduce_min_##SFX##_dev(const T *d_src, const int64_t *strides, const int64_t *shape, int rank,          \
+                                       T *d_out, void *stream);                                                        \
+  int laser_hip_reduce_max_##SFX##_dev(const T *d_src, const int64_t *strides, const int64_t *shape, int rank,          \
+                                       T *d_out, void *stream);
+LASER_HIP_DECL_REDUCE(f32, float)
+LASER_HIP_DECL_REDUCE(f64, double)
+LASER_HIP_DECL_REDUCE(i32, int32_t)
+LASER_HIP_DECL_REDUCE(i64, int64_t)
+#undef LASER_HIP_DECL_REDUCE
+int laser_hip_reduce_sum_f32(const float *data, int64_t len, float *out);
+int laser_hip_reduce_min_f32(const float *data, int64_t len, float *out);
+int laser_hip_reduce_max_f32(const float *data, int64_t len, float *out);
+
+/* ---- forEachReduce: forEach with a private accumulator per lane, merged at the end ---------------------------------
+ * The device form of forEachStaged (laser/strided_iteration/foreach_staged.nim:318), e.g. a dot product:
+ *   forEachReduce acc (f64) in x, y:  body "acc += x * y",  merge "acc += other",  init 0
+ * The spec is forEach's (body, operands, writability, parameters; the same rules) plus
+ *   acc_name    the accumulator's name in the body and in `merge` (a C identifier under forEach's naming rules)
+ *   acc_dtype   its element type, any LASER_HIP_DT_*
+ *   merge       a C++ statement that merges the accumulator `other` into `acc_name`: "acc += other",
+ *               "acc = fmaxf(acc, other)".  `other` is reserved: no operand, parameter or accumulator may be called so.
+ * The body runs once per element of `shape` in the order of "Reductions" above (E from the widest OPERAND), with the
+ * accumulator as a reference; writable operands are stored back as in forEach, so "y = expf(x - m); acc += y" writes y and
+ * sums it in one pass.  `init` must be an identity of `merge` (every private accumulator starts from it, and the folds
+ * merge accumulators that saw no element).  Empty merge, a clash with `other`, or an acc_name equal to an operand or
+ * parameter name: LASER_HIP_E_INVALID.  Compiles are cached apart from forEach's and counted in "foreach_compiles".
+ * foreach_reduce_source / _code / _kernel   as foreach_source / _code / _kernel
+ * foreach_reduce_dev   as foreach_dev, plus `init` (one 8-byte slot like a parameter, the value in its low bytes: a new
+ *                      value does not compile again) and d_out (device address of one accumulator).  Asynchronous;
+ *                      size 0 writes init.  get_option "last_foreach_variant" tells its traversal as for foreach_dev. */
+int laser_hip_foreach_reduce_source(const char *body, int nops, const char *const *names, const int *dtypes,
+                                    const int *writable, int nparams, const char *const *param_names,
+                                    const int *param_dtypes, const char *acc_name, int acc_dtype, const char *merge,
+                                    char *buf, int64_t cap, int64_t *len);
+int laser_hip_foreach_reduce_code(const char *body, int nops, const char *const *names, const int *dtypes,
+                                  const int *writable, int nparams, const char *const *param_names,
+                                  const int *param_dtypes, const char *acc_name, int acc_dtype, const char *merge,
+                                  const char *arch, void *buf, int64_t cap, int64_t *len);
+int laser_hip_foreach_reduce_kernel(const char *body, int nops, const char *const *names, const int *dtypes,
+                                    const int *writable, int nparams, const char *const *param_names,
+                                    const int *param_dtypes, const char *acc_name, int acc_dtype, const char *merge,
+                                    int64_t *handle);
+int laser_hip_foreach_reduce_dev(int64_t handle, void *const *ptrs, const int64_t *strides, const int64_t *shape,
+                                 int rank, const void *params, const void *init, void *d_out, void *stream);
 
 /* ---- row-panel sharded gemm_strided over the GPUs of one node, ONE process ---------------------------------------
  * Laser partitions M across its OpenMP threads with no cross-thread reduction (gemm.nim:160-176: `omp for` over the

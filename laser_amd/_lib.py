@@ -119,6 +119,15 @@ def lib():
     L.laser_hip_foreach_code.argtypes = spec + [C.c_char_p, vp, i64, C.POINTER(i64)]
     L.laser_hip_foreach_kernel.argtypes = spec + [C.POINTER(i64)]
     L.laser_hip_foreach_dev.argtypes = [i64, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), ci, vp, vp]
+    L.laser_hip_foreach_reduce_source.argtypes = spec + [C.c_char_p, ci, C.c_char_p, vp, i64, C.POINTER(i64)]
+    L.laser_hip_foreach_reduce_code.argtypes = spec + [C.c_char_p, ci, C.c_char_p, C.c_char_p, vp, i64, C.POINTER(i64)]
+    L.laser_hip_foreach_reduce_kernel.argtypes = spec + [C.c_char_p, ci, C.c_char_p, C.POINTER(i64)]
+    L.laser_hip_foreach_reduce_dev.argtypes = [i64, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), ci, vp, vp, vp, vp]
+    for sfx in _CT:
+        for op in ("sum", "min", "max"):
+            getattr(L, f"laser_hip_reduce_{op}_{sfx}_dev").argtypes = [vp, C.POINTER(i64), C.POINTER(i64), ci, vp, vp]
+    for op in ("sum", "min", "max"):
+        getattr(L, f"laser_hip_reduce_{op}_f32").argtypes = [vp, i64, vp]
     L.laser_hip_cblas_sgemm.argtypes = [ci, ci, ci, i64, i64, i64, C.c_float, vp, i64, vp, i64, C.c_float, vp, i64]
     L.laser_hip_cblas_dgemm.argtypes = [ci, ci, ci, i64, i64, i64, C.c_double, vp, i64, vp, i64, C.c_double, vp, i64]
     _lib = L
@@ -152,13 +161,16 @@ def declared_symbols():
              "laser_hip_copy_strided_b32_dev", "laser_hip_copy_strided_b64_dev",
              "laser_hip_host_alloc", "laser_hip_host_free", "laser_hip_host_register", "laser_hip_host_unregister",
              "laser_hip_shard_plan", "laser_hip_set_shard_devices", "laser_hip_get_shard_devices",
-             "laser_hip_foreach_source", "laser_hip_foreach_code", "laser_hip_foreach_kernel", "laser_hip_foreach_dev"]
+             "laser_hip_foreach_source", "laser_hip_foreach_code", "laser_hip_foreach_kernel", "laser_hip_foreach_dev",
+             "laser_hip_foreach_reduce_source", "laser_hip_foreach_reduce_code", "laser_hip_foreach_reduce_kernel",
+             "laser_hip_foreach_reduce_dev", "laser_hip_reduce_sum_f32", "laser_hip_reduce_min_f32", "laser_hip_reduce_max_f32"]
     for s in _CT:
         names += [f"laser_hip_gemm_strided_{s}", f"laser_hip_gemm_strided_{s}_dev",
                   f"laser_hip_gemm_strided_batched_{s}_dev", f"laser_hip_gemm_packed_{s}",
                   f"laser_hip_gemm_strided_{s}_sharded", f"laser_hip_gemm_strided_{s}_sharded_dev",
                   f"laser_hip_map_strided_unary_{s}_dev", f"laser_hip_map_strided_binary_{s}_dev",
-                  f"laser_hip_gemm_packed_{s}_dev"]
+                  f"laser_hip_gemm_packed_{s}_dev", f"laser_hip_reduce_sum_{s}_dev", f"laser_hip_reduce_min_{s}_dev",
+                  f"laser_hip_reduce_max_{s}_dev"]
         for ab in "AB":
             names += [f"laser_hip_gemm_prepack{ab}_mem_required_{s}", f"laser_hip_gemm_prepack{ab}_{s}",
                       f"laser_hip_gemm_prepack{ab}_{s}_dev"]

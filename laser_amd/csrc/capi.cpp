@@ -1527,6 +1527,7 @@ int laser_hip_get_option(const char *name, int64_t *value) {
   else if (n == "last_narrow_mfma") *value = g_last_narrow_mfma;
   else if (n == "foreach_compiles") *value = api_foreach_compiles();
   else if (n == "last_foreach_variant") *value = api_last_foreach_variant();
+  else if (n == "last_reduce_variant") *value = g_last_reduce_variant;
   else if (n == "conv_implicit") *value = g_ctx.conv_implicit;
   else if (n == "conv_patch") *value = g_conv_patch;
   else if (n == "conv_direct") *value = g_conv_direct;
@@ -2069,6 +2070,62 @@ LH_DEF_MAP(f64, double)
 LH_DEF_MAP(i32, int32_t)
 LH_DEF_MAP(i64, int64_t)
 #undef LH_DEF_MAP
+
+// ---- reductions: laser/primitives/reductions.nim:48-116 in reduce_core.h's order (reduce.hip) --------------------------
+}  // extern "C"  (templates follow)
+namespace {
+template <typename T>
+int reduce_api(int op, const T *src, const int64_t *strides, const int64_t *shape, int rank, T *out, void *stream) {
+  if (rank < 0 || rank > kMaxRank) return fail(LASER_HIP_E_INVALID, "reduce: rank %d outside 0..%d (LASER_MAXRANK)", rank, kMaxRank);
+  if (rank > 0 && (!strides || !shape)) return fail(LASER_HIP_E_INVALID, "reduce: null shape / strides");
+  int64_t total = 1;
+  for (int d = 0; d < rank; d++) {
+    if (shape[d] < 0) return fail(LASER_HIP_E_INVALID, "reduce: negative extent");
+    total *= shape[d];
+  }
+  if (int rc = ensure_init()) return rc;
+  if (!out || (total > 0 && !src)) return fail(LASER_HIP_E_INVALID, "reduce: null buffer");
+  HIP_TRY(launch_reduce<T>(op, src, strides, shape, rank, out, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+// the host-pointer form: through device scratch, synchronous; the same kernels and so the same bits as the _dev form
+int reduce_host_f32(int op, const float *data, int64_t len, float *out) {
+  if (len < 0 || !out || (len > 0 && !data)) return fail(LASER_HIP_E_INVALID, "reduce: bad argument");
+  if (int rc = ensure_init()) return rc;
+  HostCall hc;
+  if (hc.rc) return hc.rc;
+  void *d_src, *d_out;
+  if (int rc = scratch_get(0, (size_t)len * sizeof(float), &d_src)) return rc;
+  if (int rc = scratch_get(2, sizeof(float), &d_out)) return rc;
+  if (len) HIP_TRY(hipMemcpy(d_src, data, (size_t)len * sizeof(float), hipMemcpyHostToDevice));
+  const int64_t stride = 1;
+  HIP_TRY(launch_reduce<float>(op, (const float *)d_src, &stride, &len, 1, (float *)d_out, nullptr));
+  HIP_TRY(hipMemcpy(out, d_out, sizeof(float), hipMemcpyDeviceToHost));
+  return LASER_HIP_OK;
+}
+}  // namespace
+extern "C" {
+#define LH_DEF_REDUCE(SFX, T)                                                                                           \
+  int laser_hip_reduce_sum_##SFX##_dev(const T *src, const int64_t *st, const int64_t *shape, int rank, T *out,       \
+                                       void *stream) {                                                                 \
+    return reduce_api<T>(0, src, st, shape, rank, out, stream);                                                       \
+  }                                                                                                                   \
+  int laser_hip_reduce_min_##SFX##_dev(const T *src, const int64_t *st, const int64_t *shape, int rank, T *out,       \
+                                       void *stream) {                                                                 \
+    return reduce_api<T>(1, src, st, shape, rank, out, stream);                                                       \
+  }                                                                                                                   \
+  int laser_hip_reduce_max_##SFX##_dev(const T *src, const int64_t *st, const int64_t *shape, int rank, T *out,       \
+                                       void *stream) {                                                                 \
+    return reduce_api<T>(2, src, st, shape, rank, out, stream);                                                       \
+  }
+LH_DEF_REDUCE(f32, float)
+LH_DEF_REDUCE(f64, double)
+LH_DEF_REDUCE(i32, int32_t)
+LH_DEF_REDUCE(i64, int64_t)
+#undef LH_DEF_REDUCE
+int laser_hip_reduce_sum_f32(const float *data, int64_t len, float *out) { return reduce_host_f32(0, data, len, out); }
+int laser_hip_reduce_min_f32(const float *data, int64_t len, float *out) { return reduce_host_f32(1, data, len, out); }
+int laser_hip_reduce_max_f32(const float *data, int64_t len, float *out) { return reduce_host_f32(2, data, len, out); }
 
 // ---- pinned host memory for the host-pointer entry points -----------------------------------------------------------
 // Laser leaves buffer management to the caller ("creating or reusing buffers is left at the discretion of the

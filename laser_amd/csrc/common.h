@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <functional>
 
 namespace laser_hip {
 
@@ -268,6 +269,21 @@ hipError_t launch_copy_strided(T *dst, const int64_t *dstrides, const T *src, co
 template <typename T>
 hipError_t launch_map_strided(int op, int nin, T *dst, const int64_t *dstrides, const T *a, const int64_t *astrides, const T *b,
                               const int64_t *bstrides, const int64_t *shape, int rank, T alpha, T beta, hipStream_t s);
+// Dimension merging of the strided traversals: extent-1 dimensions dropped, a dimension pair merged when it is contiguous on
+// every one of the nops operands (strides[i * rank + d]); never permutes.  Writes the merged strides st[i][..] and extents
+// sh[..], returns the merged rank (>= 1).
+int merge_dims(int nops, const int64_t *strides, const int64_t *shape, int rank, int64_t (*st)[kMaxRank], int64_t *sh);
+// reductions in reduce_core.h's order (reduce.hip): op 0 sum, 1 min, 2 max; the result to the device address `out`
+template <typename T>
+hipError_t launch_reduce(int op, const T *src, const int64_t *strides, const int64_t *shape, int rank, T *out, hipStream_t s);
+extern std::atomic<int> g_last_reduce_variant;  // traversal of the last launch_reduce: 0 vector, 1 unaligned scalar, 2 strided
+// The levels of a reduction of n elements (reduce.hip; forEachReduce uses it too).  level0(blocks, dst) launches the first
+// level (E = e0 elements per lane and step), one partial per workgroup into dst; partials(in, count, blocks, dst) reduces an
+// array of `count` accumulators of acc_size bytes.  Intermediate arrays live in stream-ordered scratch.
+typedef std::function<hipError_t(int64_t blocks, void *dst)> ReduceLevel0;
+typedef std::function<hipError_t(const void *in, int64_t count, int64_t blocks, void *dst)> ReducePartials;
+hipError_t reduce_levels(int64_t n, int e0, int acc_size, void *out, hipStream_t s, const ReduceLevel0 &level0,
+                         const ReducePartials &partials);
 template <typename T>
 hipError_t launch_pack_pad(T *dst, int64_t Rpad, int64_t Cpad, const T *src, int64_t R,
                            int64_t Ccols, int64_t rs, int64_t cs, hipStream_t s, int relu = 0);

@@ -602,3 +602,41 @@ proc forEachDevice*(body: string, operands: openarray[ForEachOperand], shape: op
   var shp = newSeq[int64](shape.len)
   for i, s in shape: shp[i] = int64(s)
   check laser_hip_foreach_dev(handle, ptrs[0].addr, strides[0].addr, shp[0].addr, cint(shape.len), slots[0].addr, stream)
+
+# ---- Reductions (include/laser_hip.h "Reductions"): reductions.nim:48-116 -----------------------------------------------
+# The order of the operations is fixed -- a function of the element count alone -- so, unlike the reference's OpenMP sum,
+# the same input gives the same bits on every run.  min / max: any NaN gives NaN, -0 ranks below +0.
+proc laser_hip_reduce_sum_f32(data: ptr float32, len: int64, res: ptr float32): cint {.lh, importc: "laser_hip_reduce_sum_f32".}
+proc laser_hip_reduce_min_f32(data: ptr float32, len: int64, res: ptr float32): cint {.lh, importc: "laser_hip_reduce_min_f32".}
+proc laser_hip_reduce_max_f32(data: ptr float32, len: int64, res: ptr float32): cint {.lh, importc: "laser_hip_reduce_max_f32".}
+# device views (asynchronous on `stream`, the result to the device address `res`)
+proc laser_hip_reduce_sum_f32_dev*(src: ptr float32, strides: ptr int64, shape: ptr int64, rank: cint, res: ptr float32, stream: pointer): cint {.lh, importc: "laser_hip_reduce_sum_f32_dev".}
+proc laser_hip_reduce_min_f32_dev*(src: ptr float32, strides: ptr int64, shape: ptr int64, rank: cint, res: ptr float32, stream: pointer): cint {.lh, importc: "laser_hip_reduce_min_f32_dev".}
+proc laser_hip_reduce_max_f32_dev*(src: ptr float32, strides: ptr int64, shape: ptr int64, rank: cint, res: ptr float32, stream: pointer): cint {.lh, importc: "laser_hip_reduce_max_f32_dev".}
+proc laser_hip_reduce_sum_f64_dev*(src: ptr float64, strides: ptr int64, shape: ptr int64, rank: cint, res: ptr float64, stream: pointer): cint {.lh, importc: "laser_hip_reduce_sum_f64_dev".}
+proc laser_hip_reduce_min_f64_dev*(src: ptr float64, strides: ptr int64, shape: ptr int64, rank: cint, res: ptr float64, stream: pointer): cint {.lh, importc: "laser_hip_reduce_min_f64_dev".}
+proc laser_hip_reduce_max_f64_dev*(src: ptr float64, strides: ptr int64, shape: ptr int64, rank: cint, res: ptr float64, stream: pointer): cint {.lh, importc: "laser_hip_reduce_max_f64_dev".}
+proc laser_hip_reduce_sum_i32_dev*(src: ptr int32, strides: ptr int64, shape: ptr int64, rank: cint, res: ptr int32, stream: pointer): cint {.lh, importc: "laser_hip_reduce_sum_i32_dev".}
+proc laser_hip_reduce_min_i32_dev*(src: ptr int32, strides: ptr int64, shape: ptr int64, rank: cint, res: ptr int32, stream: pointer): cint {.lh, importc: "laser_hip_reduce_min_i32_dev".}
+proc laser_hip_reduce_max_i32_dev*(src: ptr int32, strides: ptr int64, shape: ptr int64, rank: cint, res: ptr int32, stream: pointer): cint {.lh, importc: "laser_hip_reduce_max_i32_dev".}
+proc laser_hip_reduce_sum_i64_dev*(src: ptr int64, strides: ptr int64, shape: ptr int64, rank: cint, res: ptr int64, stream: pointer): cint {.lh, importc: "laser_hip_reduce_sum_i64_dev".}
+proc laser_hip_reduce_min_i64_dev*(src: ptr int64, strides: ptr int64, shape: ptr int64, rank: cint, res: ptr int64, stream: pointer): cint {.lh, importc: "laser_hip_reduce_min_i64_dev".}
+proc laser_hip_reduce_max_i64_dev*(src: ptr int64, strides: ptr int64, shape: ptr int64, rank: cint, res: ptr int64, stream: pointer): cint {.lh, importc: "laser_hip_reduce_max_i64_dev".}
+
+proc reduce_sum*(data: ptr (float32 or UncheckedArray[float32]), len: Natural): float32 =
+  ## reductions.nim:91-96: sum of a contiguous range of float32 (host memory; the GPU computes it)
+  check laser_hip_reduce_sum_f32(cast[ptr float32](data), int64(len), result.addr)
+
+proc reduce_min*(data: ptr (float32 or UncheckedArray[float32]), len: Natural): float32 =
+  ## reductions.nim:98-103 (+Inf when len = 0)
+  check laser_hip_reduce_min_f32(cast[ptr float32](data), int64(len), result.addr)
+
+proc reduce_max*(data: ptr (float32 or UncheckedArray[float32]), len: Natural): float32 =
+  ## reductions.nim:105-110 (-Inf when len = 0)
+  check laser_hip_reduce_max_f32(cast[ptr float32](data), int64(len), result.addr)
+
+# ---- forEachReduce (include/laser_hip.h "forEachReduce"): foreach_staged.nim:318 on device buffers ------------------------
+proc laser_hip_foreach_reduce_source(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, accName: cstring, accDtype: cint, merge: cstring, buf: pointer, cap: int64, len: ptr int64): cint {.lh, importc: "laser_hip_foreach_reduce_source".}
+proc laser_hip_foreach_reduce_code(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, accName: cstring, accDtype: cint, merge: cstring, arch: cstring, buf: pointer, cap: int64, len: ptr int64): cint {.lh, importc: "laser_hip_foreach_reduce_code".}
+proc laser_hip_foreach_reduce_kernel*(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, accName: cstring, accDtype: cint, merge: cstring, handle: ptr int64): cint {.lh, importc: "laser_hip_foreach_reduce_kernel".}
+proc laser_hip_foreach_reduce_dev*(handle: int64, ptrs: ptr pointer, strides: ptr int64, shape: ptr int64, rank: cint, params: pointer, init: pointer, res: pointer, stream: pointer): cint {.lh, importc: "laser_hip_foreach_reduce_dev".}
