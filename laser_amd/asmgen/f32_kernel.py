@@ -220,15 +220,7 @@ class Gen:
         c, p = self.c, self.p
         S, V = p.salloc, p.valloc
         self.sA, self.sB, self.sC, self.sTAB = None, None, None, None
-        self.ka0 = S(8, align=4)   # A, B, C, TAB pointers
-        self.ka1 = S(8, align=4)   # lda ldb ldc M N K - -
-        self.s_lda, self.s_ldb, self.s_ldc, self.s_M, self.s_N, self.s_K = (self.ka1[i] for i in range(6))
-        self.s_alpha, self.s_beta = self.ka1[6], self.ka1[7]     # float32 bit patterns
-        self.srdA, self.srdB, self.srdC = S(4), S(4), S(4)
-        self.s_rem, self.s_cnt = S(), S()
-        self.s_bstep = S()
-        self.s_m0, self.s_n0, self.s_wave, self.s_wm0, self.s_wn0 = S(), S(), S(), S(), S()
-        self.s_t = [S() for _ in range(6)]
+        self.alloc_args()
         self.s_ldc4, self.s_ldc20 = S(), S()
         self.s_csC4 = None if c.conv else S()      # column stride of C in bytes (KA_EPI + 12; 0 in the arguments = dense)
         self.s_preA, self.s_preB = (S(2, align=2), S(2, align=2)) if c.pre else (None, None)   # lane masks: all ones = apply relu
@@ -289,11 +281,7 @@ class Gen:
             self.s_epi = S(4, align=4)                               # rowStrideBias, colStrideBias (elements), activation, -
             # batch strides in bytes (grid y = batch index): read and consumed in once(), long before the fused epilogue loads its fields
             self.s_bsA, self.s_bsBC = self.srdBias.sub(0, 2), self.s_epi
-        if c.pipe:
-            # pipelined tile transitions: bit 0 = this launch may pipeline (beta == 0, plain epilogue, K a multiple of BK, >= 3 K-tiles),
-            # bit 1 = armed: the descriptors already point at the NEXT tile and (vC, srdCd) address the tile being finished
-            self.s_pipe = S()
-            self.srdCd = S(4)        # C from this wave's first row of the tile being finished: rows move on by the stores' scalar offset
+        self.alloc_pipe()
         self.vVA = [V() for _ in range(c.NPA)]
         self.vVB = [V() for _ in range(c.NPB)] if not c.conv else []
         self.vC = [V() for _ in range(c.TN)]
@@ -308,6 +296,26 @@ class Gen:
         self.vt = [blk[i] for i in range(10)]
         # filler experiments (timing only): dummy data / address registers that alias temporaries the loop does not use
         self.vF, self.vFaddr, self.vFoff = blk.sub(4, 4), blk[10], blk[11]
+
+    def alloc_args(self):
+        """the kernel arguments every family reads, the three descriptors, the tile's coordinates, scalar temporaries"""
+        S = self.p.salloc
+        self.ka0 = S(8, align=4)   # A, B, C, TAB pointers
+        self.ka1 = S(8, align=4)   # lda ldb ldc M N K - -
+        self.s_lda, self.s_ldb, self.s_ldc, self.s_M, self.s_N, self.s_K = (self.ka1[i] for i in range(6))
+        self.s_alpha, self.s_beta = self.ka1[6], self.ka1[7]     # float32 bit patterns (f64: unused, the doubles have slots of their own)
+        self.srdA, self.srdB, self.srdC = S(4), S(4), S(4)
+        self.s_rem, self.s_cnt = S(), S()
+        self.s_bstep = S()
+        self.s_m0, self.s_n0, self.s_wave, self.s_wm0, self.s_wn0 = S(), S(), S(), S(), S()
+        self.s_t = [S() for _ in range(6)]
+
+    def alloc_pipe(self):
+        if self.c.pipe:
+            # pipelined tile transitions: bit 0 = this launch may pipeline (beta == 0, plain epilogue, K a multiple of BK, >= 3 K-tiles),
+            # bit 1 = armed: the descriptors already point at the NEXT tile and (vC, srdCd) address the tile being finished
+            self.s_pipe = self.p.salloc()
+            self.srdCd = self.p.salloc(4)        # C from this wave's first row of the tile being finished: rows move on by the stores' scalar offset
 
     def alloc_sched(self):
         """scheduler state.  A persistent workgroup owns units [u0, u1) of the launch's unit sequence (unit = one K slice of one tile,
@@ -710,18 +718,7 @@ class Gen:
         e("s_load_dwordx8", self.ka0, s(0, 2), KA_A)
         e("s_load_dwordx8", self.ka1, s(0, 2), KA_LDA)
         if not c.conv:
-            # batched problems (gemm_strided_batched; the kc slices of the slice-parallel form): workgroup id y = batch index,
-            # operand b at base + b * batch stride (bytes, 64-bit; 0 for plain launches)
-            e("s_load_dwordx2", self.s_bsA, s(0, 2), KA_BSA)
-            e("s_load_dwordx4", self.s_bsBC, s(0, 2), KA_CONV1 + 8)
-            e("s_waitcnt", lgkmcnt=0)
-            for ptr, bs in ((self.ka0.sub(0, 2), self.s_bsA), (self.ka0.sub(2, 2), self.s_bsBC.sub(0, 2)), (self.ka0.sub(4, 2), self.s_bsBC.sub(2, 2))):
-                e("s_mul_i32", st[2], s(3), bs[0])
-                e("s_mul_hi_u32", st[3], s(3), bs[0])
-                e("s_mul_i32", st[4], s(3), bs[1])
-                e("s_add_u32", st[3], st[3], st[4])
-                e("s_add_u32", ptr[0], ptr[0], st[2])
-                e("s_addc_u32", ptr[1], ptr[1], st[3])
+            self.batch_offsets(KA_BSA)
         e("s_waitcnt", lgkmcnt=0)
         if c.pipe:
             self.pipe_eligible()
@@ -865,6 +862,21 @@ class Gen:
                     e("v_add_u32", self.WB[gi][ee][0], c.STAGE, self.WB[gi][ee][2])
                     e("v_add_u32", self.WB[gi][ee][1], 2 * c.STAGE, self.WB[gi][ee][2])
 
+    def batch_offsets(self, ka_bsa):
+        """batched problems (gemm_strided_batched; the kc slices of the slice-parallel form): workgroup id y = batch index, operand b at
+        base + b * batch stride (bytes, 64-bit; 0 for plain launches).  A's stride at `ka_bsa`, B's and C's at KA_CONV1 + 8."""
+        e, st = self.p.emit, self.s_t
+        e("s_load_dwordx2", self.s_bsA, s(0, 2), ka_bsa)
+        e("s_load_dwordx4", self.s_bsBC, s(0, 2), KA_CONV1 + 8)
+        e("s_waitcnt", lgkmcnt=0)
+        for ptr, bs in ((self.ka0.sub(0, 2), self.s_bsA), (self.ka0.sub(2, 2), self.s_bsBC.sub(0, 2)), (self.ka0.sub(4, 2), self.s_bsBC.sub(2, 2))):
+            e("s_mul_i32", st[2], s(3), bs[0])
+            e("s_mul_hi_u32", st[3], s(3), bs[0])
+            e("s_mul_i32", st[4], s(3), bs[1])
+            e("s_add_u32", st[3], st[3], st[4])
+            e("s_add_u32", ptr[0], ptr[0], st[2])
+            e("s_addc_u32", ptr[1], ptr[1], st[3])
+
     def pipe_eligible(self):
         """s_pipe bit 0: tile transitions of this launch may be pipelined -- beta == 0 (the running sum of the next tile starts at 0:
         nothing to fetch), no bias / activation (the plain store), K a multiple of BK (no K-tail masks to undo between tiles) and at
@@ -904,8 +916,9 @@ class Gen:
         e = p.emit
         st = self.s_t
         Keff = self.s_Keff
-        e("s_lshl_b32", st[3], self.s_lda, 2, comment="lda * 4 bytes")
-        e("s_lshl_b32", st[5], self.s_ldb, 2, comment="ldb * 4 bytes")
+        sh = c.ESZ.bit_length() - 1      # bytes of an element = 1 << sh (the comments below say 4)
+        e("s_lshl_b32", st[3], self.s_lda, sh, comment=f"lda * {c.ESZ} bytes")
+        e("s_lshl_b32", st[5], self.s_ldb, sh, comment=f"ldb * {c.ESZ} bytes")
         A_, B_, C_ = self.ka0.sub(0, 2), self.ka0.sub(2, 2), self.ka0.sub(4, 2)
         # A panel: base = A + m0 * lda * 4 + kb * 4; bytes = (min(M - m0, BM) - 1) * lda * 4 + Keff * 4
         e("s_mul_hi_u32", st[2], self.s_m0, st[3])
@@ -913,7 +926,7 @@ class Gen:
         e("s_add_u32", self.srdA[0], A_[0], st[0])
         e("s_addc_u32", self.srdA[1], A_[1], st[2])
         if c.persistent:
-            e("s_lshl_b32", st[0], self.s_kb, 2)
+            e("s_lshl_b32", st[0], self.s_kb, sh)
             e("s_add_u32", self.srdA[0], self.srdA[0], st[0])
             e("s_addc_u32", self.srdA[1], self.srdA[1], 0)
         e("s_and_b32", self.srdA[1], self.srdA[1], 0xffff)
@@ -921,7 +934,7 @@ class Gen:
         e("s_min_u32", st[0], st[0], c.BM)
         e("s_sub_u32", st[0], st[0], 1)
         e("s_mul_i32", st[0], st[0], st[3])
-        e("s_lshl_b32", st[2], Keff, 2)
+        e("s_lshl_b32", st[2], Keff, sh)
         e("s_add_u32", self.srdA[2], st[0], st[2])
         e("s_mov_b32", self.srdA[3], 0x00020000)
         if c.conv:
@@ -941,7 +954,7 @@ class Gen:
             e("s_add_u32", self.srdB[0], B_[0], st[0])
             e("s_addc_u32", self.srdB[1], B_[1], st[2])
             if c.persistent:
-                e("s_lshl_b32", st[0], self.s_kb, 2)
+                e("s_lshl_b32", st[0], self.s_kb, sh)
                 e("s_add_u32", self.srdB[0], self.srdB[0], st[0])
                 e("s_addc_u32", self.srdB[1], self.srdB[1], 0)
             e("s_and_b32", self.srdB[1], self.srdB[1], 0xffff)
@@ -949,11 +962,11 @@ class Gen:
             e("s_min_u32", st[0], st[0], c.BN)
             e("s_sub_u32", st[0], st[0], 1)
             e("s_mul_i32", st[0], st[0], st[5])
-            e("s_lshl_b32", st[2], Keff, 2)
+            e("s_lshl_b32", st[2], Keff, sh)
             e("s_add_u32", self.srdB[2], st[0], st[2])
         else:
             # B panel: base = B + n0 * 4 + kb * ldb * 4; bytes = (Keff - 1) * ldb * 4 + (N - n0) * 4
-            e("s_lshl_b32", st[0], self.s_n0, 2)
+            e("s_lshl_b32", st[0], self.s_n0, sh)
             e("s_add_u32", self.srdB[0], B_[0], st[0])
             e("s_addc_u32", self.srdB[1], B_[1], 0)
             if c.persistent:
@@ -965,7 +978,7 @@ class Gen:
             e("s_sub_u32", st[0], Keff, 1)
             e("s_mul_i32", st[0], st[0], st[5])
             e("s_sub_u32", st[2], self.s_N, self.s_n0)
-            e("s_lshl_b32", st[2], st[2], 2)
+            e("s_lshl_b32", st[2], st[2], sh)
             e("s_add_u32", self.srdB[2], st[0], st[2])
         e("s_mov_b32", self.srdB[3], 0x00020000)
 
@@ -978,19 +991,19 @@ class Gen:
         Keff = self.s_Keff
         # K tail: pieces of the last K-tile that lie beyond K get an offset the bounds check rejects (they read as 0, like
         # Laser's zero-padded panels, gemm_packing.nim:46-55)
-        nkq = c.BK // 4
+        sh = c.ESZ.bit_length() - 1      # bytes of an element = 1 << sh; a 16-byte piece holds 16 >> sh of them
         e("s_and_b32", self.s_ktail, Keff, c.BK - 1)
-        e("v_and_b32", t[5], nkq - 1, v(0))
-        e("v_lshlrev_b32", t[5], 2, t[5])
+        e("v_and_b32", t[5], (c.BK << sh) // 16 - 1, v(0))
+        e("v_lshlrev_b32", t[5], 4 - sh, t[5])
         e("v_cmp_gt_u32", self.s_tm, self.s_ktail, t[5])
-        # K % 4 != 0: the piece that straddles K is loaded whole (its tail belongs to the next row, or reads 0 past the panel) and
-        # its elements beyond K are zeroed in the staging registers before they are stored (mask_last_pieces)
-        for j in range(4):
+        # K % 4 != 0 (the families that allow it): the piece that straddles K is loaded whole (its tail belongs to the next row, or
+        # reads 0 past the panel) and its elements beyond K are zeroed in the staging registers before they are stored (mask_last_pieces)
+        for j, em in enumerate(self.s_em):
             e("v_add_u32", t[6], j, t[5])
-            e("v_cmp_gt_u32", self.s_em[j], self.s_ktail, t[6])
-        e("s_lshl_b32", st[3], self.s_lda, 2, comment="lda * 4 bytes")
+            e("v_cmp_gt_u32", em, self.s_ktail, t[6])
+        e("s_lshl_b32", st[3], self.s_lda, sh, comment=f"lda * {c.ESZ} bytes")
         self.kcontig_goff(self.vVA, c.NPA, st[3])
-        e("s_lshl_b32", st[5], self.s_ldb, 2, comment="ldb * 4 bytes")
+        e("s_lshl_b32", st[5], self.s_ldb, sh, comment=f"ldb * {c.ESZ} bytes")
         if c.b_kcontig:
             self.kcontig_goff(self.vVB, c.NPB, st[5])
         e("s_nop", 4)
@@ -1050,16 +1063,11 @@ class Gen:
                 # tile 0's loads; the table reads of tile 1's gathers were waited for before these stores were issued, in the other path
                 # after them: all LDS operations drained here keeps the two paths' queues alike)
                 self.run_ops([o for grp in self.conv_store_ops(2) for o in grp])
-            for pi in range(c.NPA):
-                self.store_A_piece(pi, k=2)
-            if c.conv:
+                for pi in range(c.NPA):
+                    self.store_A_piece(pi, k=2)
                 self.lg_wait(None)
-            elif c.b_kcontig:
-                for pj in range(c.NPB):
-                    self.store_B_kpiece(pj, k=2)
             else:
-                for gi in range(c.NPB // 2):
-                    self.store_B_pair(gi, k=2)
+                self.store_tile_to_lds(2)
             self.stA, self.stB = real
             e("s_branch", L_join)
             fast_state = (list(self.vmq), list(self.lgq))
@@ -1084,16 +1092,12 @@ class Gen:
                     self.dump(f"conv stB[{i_}][0]", self.stB[i_][0])
                     self.dump(f"conv stB[{i_}][1]", self.stB[i_][1])
             self.dump("stA_last[3]", self.stA[-1][3])
-        for pi in range(c.NPA):
-            self.store_A_piece(pi, k=2)     # tile 0 goes to LDS stage 0 = the "third" stage of the write triples
         if c.conv:
+            for pi in range(c.NPA):
+                self.store_A_piece(pi, k=2)
             self.run_ops([o for grp in self.conv_store_ops(2) for o in grp])
-        elif c.b_kcontig:
-            for pj in range(c.NPB):
-                self.store_B_kpiece(pj, k=2)
         else:
-            for gi in range(c.NPB // 2):
-                self.store_B_pair(gi, k=2)
+            self.store_tile_to_lds(2)       # tile 0 goes to LDS stage 0 = the "third" stage of the write triples
         if c.debug:
             self.lg_wait(None)
             e("s_barrier")
@@ -1195,17 +1199,22 @@ class Gen:
         if c.persistent:
             e("s_cmp_lg_u32", self.s_mode, MODE_NORMAL)
             e("s_cbranch_scc1", keep)
-        for b in range(c.NB):
-            for r in range(c.ACCR):
-                e("v_mov_b32" if c.runv else "v_accvgpr_write_b32", self.run[b][r], 0)
+        self.zero_run()
         self.load_beta_c()
         p.place(keep)
+
+    def zero_run(self):
+        c = self.c
+        for b in range(c.NB):
+            for r in range(c.ACCR):
+                self.p.emit("v_mov_b32" if c.runv else "v_accvgpr_write_b32", self.run[b][r], 0)
 
     def c_descriptor(self):
         """srdC = the whole C matrix (conv: this image's [M][oH*oW] block): bytes = (M - 1) * ldc * 4 + N * 4"""
         c, e, st = self.c, self.p.emit, self.s_t
         C_ = self.ka0.sub(4, 2)
-        e("s_lshl_b32", self.s_ldc4, self.s_ldc, 2)
+        sh = c.ESZ.bit_length() - 1
+        e("s_lshl_b32", self.s_ldc4, self.s_ldc, sh)
         if c.conv:
             img = self.s_img if c.cpers else s(3)
             e("s_mul_hi_u32", st[2], img, self.s_scr[12])
@@ -1218,8 +1227,8 @@ class Gen:
             e("s_and_b32", self.srdC[1], C_[1], 0xffff)
         e("s_sub_u32", st[0], self.s_M, 1)
         e("s_mul_i32", st[0], st[0], self.s_ldc4)
-        if c.conv:
-            e("s_lshl_b32", st[2], self.s_N, 2)
+        if self.s_csC4 is None:        # (convolution, f64: C's columns are adjacent)
+            e("s_lshl_b32", st[2], self.s_N, sh)
         else:
             # C[i][j] at i * ldc + j * csC (MatrixView, gemm_utils.nim:36-60): bytes = (M - 1) * ldc * 4 + (N - 1) * csC * 4 + 4
             e("s_load_dword", self.s_csC4, s(0, 2), KA_EPI + 12)
@@ -1231,7 +1240,11 @@ class Gen:
             e("s_add_u32", st[2], st[2], 4)
         e("s_add_u32", self.srdC[2], st[0], st[2])
         e("s_mov_b32", self.srdC[3], 0x00020000)
-        e("s_mul_i32", self.s_ldc20, self.s_ldc4, 5)
+        self.c_row_step()
+
+    def c_row_step(self):
+        """s_ldc20 = c_step's stride from the last row of a lane's row quad to the first of its next quad"""
+        self.p.emit("s_mul_i32", self.s_ldc20, self.s_ldc4, 5)
 
     def issue_loads_all(self):
         if self.c.conv:      # (B's gathers first, like the loop body: the two queues must carry the same order)
@@ -1441,13 +1454,17 @@ class Gen:
         """descriptors move one K-tile along k: base += step, bytes = max(bytes - step, 0)"""
         e = self.p.emit
         ops = []
-        for srd, step in ((self.srdA, self.c.BK * 4),) + (() if self.c.conv else ((self.srdB, self.s_bstep),)):
+        for srd, step in ((self.srdA, self.c.BK * self.c.ESZ),) + (() if self.c.conv else ((self.srdB, self.b_step()),)):
             ops += [("s_add_u32", srd[0], srd[0], step), ("s_addc_u32", srd[1], srd[1], 0),
                     ("s_sub_u32", srd[2], srd[2], step), ("s_cselect_b32", srd[2], 0, srd[2])]
         if which is None:
             for o in ops:
                 e(*o)
         return ops
+
+    def b_step(self):
+        """bytes B's descriptor moves per K-tile"""
+        return self.s_bstep
 
     def pre_op(self, regs, mask):
         """fused prologue: the staged elements become (mask ? max(x, 0) : x) before they are stored -- all of a piece's VALU work in one
@@ -1655,34 +1672,59 @@ class Gen:
         T = self.vT[0]
         if "foldreads" in self.c.ablate:      # (pricing experiments: results are wrong)
             return
-        for r in range(16):
+        for r in range(self.c.ACCR):
             self.p.emit("v_accvgpr_read_b32", T[r], self.acc[b][r])
 
-    def fold_after(self, b):
-        p, e, T = self.p, self.p.emit, self.vT[0]
-        # run += alpha * slice, unfused (gemm_ukernel_generic.nim:68-76); alpha == 1 (every reference caller): 1*x is x;
-        # the multiplies sit out of line (after s_endpgm) so that the usual case is a branch NOT taken
-        lmul, lback = p.label("amul"), p.label("aback")
-        e("s_cmp_lg_u32", self.s_alpha, 0x3f800000)
-        e("s_cbranch_scc1", lmul)
+    # a family's arithmetic on the slice sum T = vT[0] (a block's ACCR registers) is four hooks: T *= alpha, is alpha 1.0,
+    # an AGPR block += T, the running sum += T
+    def alpha_mul(self):
+        """T *= alpha, as instruction tuples"""
+        T = self.vT[0]
+        return [("v_mul_f32", T[r], self.s_alpha, T[r]) for r in range(self.c.ACCR)]
+
+    def cmp_alpha_one(self):
+        """scc = (alpha != 1.0)"""
+        self.p.emit("s_cmp_lg_u32", self.s_alpha, 0x3f800000)
+
+    def alpha_mul_outlined(self, hint):
+        """T *= alpha unless alpha == 1 (every reference caller; 1 * x is x): the multiplies sit out of line (after s_endpgm) so that the
+        usual case is a branch NOT taken"""
+        p = self.p
+        lmul, lback = p.label(hint + "mul"), p.label(hint + "back")
+        self.cmp_alpha_one()
+        p.emit("s_cbranch_scc1", lmul)
         p.place(lback)
-        self.outlined.append((lmul, [("v_mul_f32", T[r], self.s_alpha, T[r]) for r in range(16)], lback))
+        self.outlined.append((lmul, self.alpha_mul(), lback))
+
+    def agpr_add(self, dst):
+        """dst (a block in AGPRs, which no VALU instruction can address) += T, through temporaries"""
+        e, T = self.p.emit, self.vT[0]
+        for r in range(self.c.ACCR):
+            tt = self.vt[r % 4]
+            e("v_accvgpr_read_b32", tt, dst[r])
+            e("v_add_f32", tt, tt, T[r])
+            e("v_accvgpr_write_b32", dst[r], tt)
+
+    def run_add(self, b):
+        """run[b] += T"""
+        if not self.c.runv:
+            return self.agpr_add(self.run[b])
+        # the running sum is in arch VGPRs: two adds per instruction, nothing to move (8 VALU operations where the AGPR plan has 48)
+        T = self.vT[0]
+        for j in range(self.c.ACCR // 2):
+            self.p.emit("v_pk_add_f32", self.run[b].sub(2 * j, 2), self.run[b].sub(2 * j, 2), T.sub(2 * j, 2))
+
+    def fold_after(self, b):
+        # run += alpha * slice, unfused (gemm_ukernel_generic.nim:68-76)
+        self.alpha_mul_outlined("a")
         if c_runv(self):
-            # the running sum is in arch VGPRs: two adds per instruction, nothing to move (8 VALU operations where the AGPR plan has 48)
             if "foldadds" in self.c.ablate:
                 return
             if "foldscalar" in self.c.ablate:     # (pricing: 16 single adds instead of 8 packed ones -- same result)
-                for r in range(16):
-                    e("v_add_f32", self.run[b][r], self.run[b][r], T[r])
+                for r in range(self.c.ACCR):
+                    self.p.emit("v_add_f32", self.run[b][r], self.run[b][r], self.vT[0][r])
                 return
-            for j in range(8):
-                e("v_pk_add_f32", self.run[b].sub(2 * j, 2), self.run[b].sub(2 * j, 2), T.sub(2 * j, 2))
-            return
-        for r in range(16):
-            tt = self.vt[r % 4]
-            e("v_accvgpr_read_b32", tt, self.run[b][r])
-            e("v_add_f32", tt, tt, T[r])
-            e("v_accvgpr_write_b32", self.run[b][r], tt)
+        self.run_add(b)
 
     def trans_after(self, b):
         """transition body (Cfg.pipe), block b: vT holds alpha-less slice sum of the tile being FINISHED (fold_before), the MFMA in front of
@@ -1694,11 +1736,7 @@ class Gen:
         beyond N carry an out-of-range vC -- dropped exactly as in the epilogue.  No vector address arithmetic."""
         c, p, e, T, st = self.c, self.p, self.p.emit, self.vT[0], self.s_t
         i, n = b // c.TN, b % c.TN
-        lmul, lback = p.label("tmul"), p.label("tback")
-        e("s_cmp_lg_u32", self.s_alpha, 0x3f800000)
-        e("s_cbranch_scc1", lmul)
-        p.place(lback)
-        self.outlined.append((lmul, [("v_mul_f32", T[r], self.s_alpha, T[r]) for r in range(16)], lback))
+        self.alpha_mul_outlined("t")
         soff = st[0]
         if i:
             e("s_mul_i32", soff, self.s_ldc4, 32 * i)
@@ -1735,17 +1773,7 @@ class Gen:
         e("v_and_b32", lane, 63, v(0))
         e("v_and_b32", lo, 31, lane)
         e("v_lshrrev_b32", hi, 5, lane)
-        e("s_add_u32", st[0], self.s_m0, self.s_wm0)
-        e("s_mul_hi_u32", st[2], st[0], self.s_ldc4)
-        e("s_mul_i32", st[3], st[0], self.s_ldc4)
-        e("s_add_u32", self.srdCd[0], self.srdC[0], st[3])
-        e("s_addc_u32", self.srdCd[1], self.srdC[1], st[2])
-        e("s_and_b32", self.srdCd[1], self.srdCd[1], 0xffff)
-        e("s_mov_b32", self.srdCd[3], 0x00020000)
-        e("s_sub_u32", self.srdCd[2], self.srdC[2], st[3])              # what is left of C from there (0: the wave's rows lie beyond M)
-        e("s_cselect_b32", self.srdCd[2], 0, self.srdCd[2])
-        e("s_cmp_lg_u32", st[2], 0)
-        e("s_cselect_b32", self.srdCd[2], 0, self.srdCd[2])
+        self.srdCd_setup()
         e("v_lshlrev_b32", t[3], 2, hi)
         e("v_mul_lo_u32", t[3], t[3], self.s_ldc4)
         e("s_add_u32", st[1], self.s_n0, self.s_wn0)
@@ -1766,6 +1794,21 @@ class Gen:
                 e("v_add_u32", t[6], st[5], t[6])
             e("v_mov_b32", t[7], 0x80000000)
             e("v_cndmask_b32", self.vC[n], t[7], t[6], VCC)
+
+    def srdCd_setup(self):
+        """srdCd = C from row m0 + wm0, this wave's first of the tile (m0, n0).  Clobbers s_t[0], [2], [3]."""
+        e, st = self.p.emit, self.s_t
+        e("s_add_u32", st[0], self.s_m0, self.s_wm0)
+        e("s_mul_hi_u32", st[2], st[0], self.s_ldc4)
+        e("s_mul_i32", st[3], st[0], self.s_ldc4)
+        e("s_add_u32", self.srdCd[0], self.srdC[0], st[3])
+        e("s_addc_u32", self.srdCd[1], self.srdC[1], st[2])
+        e("s_and_b32", self.srdCd[1], self.srdCd[1], 0xffff)
+        e("s_mov_b32", self.srdCd[3], 0x00020000)
+        e("s_sub_u32", self.srdCd[2], self.srdC[2], st[3])              # what is left of C from there (0: the wave's rows lie beyond M)
+        e("s_cselect_b32", self.srdCd[2], 0, self.srdCd[2])
+        e("s_cmp_lg_u32", st[2], 0)
+        e("s_cselect_b32", self.srdCd[2], 0, self.srdCd[2])
 
     def next_unit(self, L_none):
         """Cfg.cpers: the workgroup's next unit -> s_img, s_m0, s_n0 (L_none when there is none).  KA_SCHED2 carries, for these kernels,
@@ -2456,29 +2499,15 @@ class Gen:
             self.fold_block(b)
 
     def fold_block(self, b):
-        e, T = self.p.emit, self.vT[0]
-        for r in range(16):
-            e("v_accvgpr_read_b32", T[r], self.acc[b][r])
-        for r in range(16):
-            e("v_mul_f32", T[r], self.s_alpha, T[r])      # (1.0 * x is x: no branch here, the hand-over is not the hot loop)
-        if self.c.runv:
-            for j in range(8):
-                e("v_pk_add_f32", self.run[b].sub(2 * j, 2), self.run[b].sub(2 * j, 2), T.sub(2 * j, 2))
-            return
-        for r in range(16):
-            tt = self.vt[r % 4]
-            e("v_accvgpr_read_b32", tt, self.run[b][r])
-            e("v_add_f32", tt, tt, T[r])
-            e("v_accvgpr_write_b32", self.run[b][r], tt)
+        for r in range(self.c.ACCR):
+            self.p.emit("v_accvgpr_read_b32", self.vT[0][r], self.acc[b][r])
+        for o in self.alpha_mul():      # (1.0 * x is x: no branch here, the hand-over is not the hot loop)
+            self.p.emit(*o)
+        self.run_add(b)
 
     def acc_add_block(self, b):
         """acc[b] += the partial in vT"""
-        e, T = self.p.emit, self.vT[0]
-        for r in range(16):
-            tt = self.vt[r % 4]
-            e("v_accvgpr_read_b32", tt, self.acc[b][r])
-            e("v_add_f32", tt, tt, T[r])
-            e("v_accvgpr_write_b32", self.acc[b][r], tt)
+        self.agpr_add(self.acc[b])
 
     def load_received(self, t_off):
         """laser-order: the received sum becomes the running sum; one chain: acc += received partial"""
@@ -2688,17 +2717,23 @@ amdhsa.kernels:
 """
 
 
-if __name__ == "__main__":
+def write_kernels(prefix, configs, make):
+    """the generator modules' command line (`python3 -m laser_amd.asmgen.MODULE --out DIR`): every configuration of the module as
+    DIR/<prefix><name>.s, one line per kernel on stdout"""
     import argparse
     import os
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
-    for name in CONFIGS:
+    for name in configs:
         g = make(name)
         g.build()
-        sym = "lh_f32_" + name
+        sym = prefix + name
         with open(os.path.join(args.out, sym + ".s"), "w") as f:
             f.write(kernel_text(g, sym))
         print(sym, len(g.p.ins), "instructions")
+
+
+if __name__ == "__main__":
+    write_kernels("lh_f32_", CONFIGS, make)

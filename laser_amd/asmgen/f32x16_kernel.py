@@ -11,7 +11,8 @@ CPU the same way (gemm_tiling.nim:147-219: MR x NR from the register file); here
 
 Program structure: f32_kernel.Gen's (3-stage LDS ring, one barrier per K-tile, one straight-line body per stage with every memory
 operation assigned to a gap between two MFMAs and counted waits, accumulators + running sum in AGPRs, persistent scheduler with
-K-slice hand-overs), with the f64 kernels' padded-row LDS image (f64_kernel.py) at 4-byte elements:
+K-slice hand-overs), on the 16x16-block families' padded-row LDS image (gen16x16.Gen16x16, the base class shared with f64_kernel) at
+4-byte elements:
   a row holds BK = 32 floats as 8 chunks of 16 bytes, chunk 4 * (k / 16) + k % 4 holding k, k + 4, k + 8, k + 12 -- the four k-steps
   lane group q = k % 4 needs from ONE ds_read_b128 -- and is 144 bytes long (9 chunks: the 16 rows a 16-lane group reads fall into
   16 different 4-bank groups, no swizzle).  Stores are two ds_write2_b32 per 16-byte piece:
@@ -21,8 +22,8 @@ Operands: A row-major (k-contiguous), B row-major or passed transposed (`_nt`), 
 of 4 (16-byte pieces are all-or-nothing); any alpha / beta; fused epilogue C = act(.. + bias) with a strided bias view and relu like the
 32x32-block kernels (README.md:238-242 of the reference plans this fusion); no fused prologue."""
 from .core import v, s, VCC
-from .f32_kernel import Gen, Cfg, kernel_text, KA_A, KA_LDA, KA_CONV1, KA_BSA, KA_BIAS, KA_EPI  # noqa: F401
-from .f64_kernel import Gen64
+from .f32_kernel import Cfg, kernel_text, write_kernels, KA_A, KA_LDA, KA_BSA, KA_BIAS, KA_EPI  # noqa: F401
+from .gen16x16 import Gen16x16
 
 CONFIGS = {
     # 2 x 2 waves of 48x48 = 9 blocks: 36 accumulator registers (+ 36 for the running sum); 81 KiB of LDS
@@ -45,260 +46,64 @@ CONFIGS = {
 }
 
 
-class Gen16(Gen64):
-    ab_descriptors = Gen.ab_descriptors      # 4-byte elements: the f32 kernels' descriptors (run_setup and the pipelined switch)
-
+class Gen16(Gen16x16):
     # ------------------------------------------------------------------ registers
-    def alloc(self):
-        c, p = self.c, self.p
-        S, V = p.salloc, p.valloc
-        assert c.BK == 32 and c.BM % 32 == 0 and c.BN % 32 == 0 and not c.debug
-        self.ka0 = S(8, align=4)
-        self.ka1 = S(8, align=4)
-        self.s_lda, self.s_ldb, self.s_ldc, self.s_M, self.s_N, self.s_K = (self.ka1[i] for i in range(6))
-        self.s_alpha, self.s_beta = self.ka1[6], self.ka1[7]     # float32 bit patterns
-        self.srdA, self.srdB, self.srdC = S(4), S(4), S(4)
-        self.s_rem, self.s_cnt = S(), S()
-        self.s_bstep = S()
-        self.s_m0, self.s_n0, self.s_wave, self.s_wm0, self.s_wn0 = S(), S(), S(), S(), S()
-        self.s_t = [S() for _ in range(6)]
+    def alloc_scalars(self):
+        S = self.p.salloc
+        self.alloc_args()
         self.s_bsA, self.s_bsBC = S(2, align=2), S(4, align=4)   # batch strides in bytes (grid y = batch index)
         self.s_ldc4 = S()
         self.s_csC4 = S()                      # column stride of C in bytes (KA_EPI + 12; 0 in the arguments = dense)
         self.alloc_sched()
         self.srdBias = S(4)                    # fused epilogue: the bias view (base, -, bytes, flags)
         self.s_epi = S(4, align=4)             # rowStrideBias, colStrideBias (elements), activation, -
-        if c.pipe:
-            # pipelined tile transitions (f32_kernel.py Cfg.pipe): bit 0 = this launch may pipeline, bit 1 = armed
-            self.s_pipe = S()
-            self.srdCd = S(4)        # C from this wave's first row of the tile being finished
-        self.acc = [p.aalloc(4) for _ in range(c.NB)]
-        # runv (f32_kernel.py Cfg): the running sum in arch VGPRs -- the slice fold is 4 v_accvgpr_read + 2 v_pk_add_f32 per block where
-        # the all-AGPR plan has 16 VALU operations; dataa: fragments + staging in AGPRs (the tiles whose VGPR file would overflow)
-        self.run = [V(4) if c.runv else p.aalloc(4) for _ in range(c.NB)] if c.exact else None
-        D4 = (lambda n: p.aalloc(n)) if c.dataa else V
-        self.fa = [[D4(4) for _ in range(c.TM)] for _ in range(2)]
-        self.fb = [[D4(4) for _ in range(c.TN)] for _ in range(2)]
-        self.stA = [D4(4) for _ in range(c.NPA)]
-        self.stB = [D4(4) for _ in range(c.NPB)]
-        self.st_sets = [(self.stA, self.stB)]
-        self.RA = [[V() for _ in range(3)] for _ in range(c.NG)]
-        self.RB = [[V() for _ in range(3)] for _ in range(c.NG)]
-        self.WA = [[V() for _ in range(3)] for _ in range(c.NPA)]   # [piece][stage]
-        self.WB = [[V() for _ in range(3)] for _ in range(c.NPB)]
-        self.v_oob = V()
-        self.s_tm = S(2)
-        self.s_ktail = S()
-        self.vVA = [V() for _ in range(c.NPA)]
-        self.vVB = [V() for _ in range(c.NPB)]
-        self.vC = [V() for _ in range(c.TN)]
-        self.ndump = 0
-        self.dump_names = []
-        self.vT = [V(16)]
-        blk = V(12, align=4)
-        self.vt = [blk[i] for i in range(10)]
-        self.vF, self.vFaddr, self.vFoff = blk.sub(4, 4), blk[10], blk[11]
+        self.alloc_pipe()
 
     # ------------------------------------------------------------------ prologue (f32_kernel.Gen.prologue: once, scheduler, run_setup)
     def once(self):
         c, p = self.c, self.p
-        e = p.emit
-        t, st = self.vt, self.s_t
-        RS = c.RS
         p.note(f"f32 (16x16 blocks) {c.name}: {c.BM}x{c.BN}x{c.BK} tile, 4 waves, wave tile {c.WTM}x{c.WTN}, "
                f"{'laser-order (kc = 512 slices)' if c.exact else 'one accumulation chain'}")
-        e("s_load_dwordx8", self.ka0, s(0, 2), KA_A)
-        e("s_load_dwordx8", self.ka1, s(0, 2), KA_LDA)
-        # batched problems: workgroup id y = batch index, operand b at base + b * batch stride (bytes; 0 for plain launches) -- the
-        # f32 kernels' argument slots
-        e("s_load_dwordx2", self.s_bsA, s(0, 2), KA_BSA)
-        e("s_load_dwordx4", self.s_bsBC, s(0, 2), KA_CONV1 + 8)
-        e("s_waitcnt", lgkmcnt=0)
-        for ptr, bs in ((self.ka0.sub(0, 2), self.s_bsA), (self.ka0.sub(2, 2), self.s_bsBC.sub(0, 2)), (self.ka0.sub(4, 2), self.s_bsBC.sub(2, 2))):
-            e("s_mul_i32", st[2], s(3), bs[0])
-            e("s_mul_hi_u32", st[3], s(3), bs[0])
-            e("s_mul_i32", st[4], s(3), bs[1])
-            e("s_add_u32", st[3], st[3], st[4])
-            e("s_add_u32", ptr[0], ptr[0], st[2])
-            e("s_addc_u32", ptr[1], ptr[1], st[3])
+        p.emit("s_load_dwordx8", self.ka0, s(0, 2), KA_A)
+        p.emit("s_load_dwordx8", self.ka1, s(0, 2), KA_LDA)
+        self.batch_offsets(KA_BSA)           # (the f32 kernels' argument slots)
         if c.pipe:
-            # tile transitions of this launch may be pipelined: beta == 0 (the next tile's running sum starts at 0), K a multiple of BK
-            # (no K-tail masks to undo between tiles), at least three K-tiles (the switch happens two tile bodies before a tile's end)
-            e("s_load_dwordx2", self.srdBias.sub(0, 2), s(0, 2), KA_BIAS)
-            e("s_load_dword", st[2], s(0, 2), KA_EPI + 8)
-            e("s_waitcnt", lgkmcnt=0)
-            e("s_or_b32", st[3], self.srdBias[0], self.srdBias[1])
-            e("s_or_b32", st[3], st[3], st[2])             # (a bias pointer or an activation: the fused epilogue, not a transition body)
-            e("s_and_b32", st[4], self.s_beta, 0x7fffffff)
-            e("s_or_b32", st[3], st[3], st[4])
-            e("s_and_b32", st[4], self.s_K, c.BK - 1)
-            e("s_or_b32", st[3], st[3], st[4])
-            e("s_cmp_eq_u32", st[3], 0)
-            e("s_cselect_b32", self.s_pipe, 1, 0)
-            e("s_cmp_lt_u32", self.s_K, 3 * c.BK)
-            e("s_cselect_b32", self.s_pipe, 0, self.s_pipe)
-        tid = v(0)
-        lane, r16, q = t[0], t[1], t[2]
-        e("v_and_b32", lane, 63, tid)
-        e("v_lshrrev_b32", t[5], 6, tid)
-        e("s_nop", 1, comment="VALU write -> v_readfirstlane of the same VGPR needs wait states")
-        e("v_readfirstlane_b32", self.s_wave, t[5])
-        e("s_nop", 3)
-        e("v_and_b32", r16, 15, lane)
-        e("v_lshrrev_b32", q, 4, lane)
-        e("s_lshr_b32", st[2], self.s_wave, 1)
-        e("s_mul_i32", self.s_wm0, st[2], c.WTM)
-        e("s_and_b32", st[2], self.s_wave, 1)
-        e("s_mul_i32", self.s_wn0, st[2], c.WTN)
-        # fragment reads of group g (16 k): (wm0 + r16) * RS [+ BM * RS + (wn0 + r16) * RS for B] + (4g + q) * 16
-        e("v_add_u32", t[5], self.s_wm0, r16)
-        e("v_mul_u32_u24", t[6], RS, t[5])
-        e("v_add_u32", t[5], self.s_wn0, r16)
-        e("v_mul_u32_u24", t[7], RS, t[5])
-        e("v_add_u32", t[7], c.BM * RS, t[7])
-        for g in range(c.NG):
-            e("v_lshl_add_u32", t[5], q, 4, 64 * g)
-            for R, row in ((self.RA, t[6]), (self.RB, t[7])):
-                e("v_add_u32", R[g][0], t[5], row)
-                e("v_add_u32", R[g][1], c.STAGE, R[g][0])
-                e("v_add_u32", R[g][2], 2 * c.STAGE, R[g][0])
-        pc, xr = t[0], t[1]
-        e("v_and_b32", pc, 7, tid)
-        e("v_lshrrev_b32", xr, 3, tid)
-        e("v_mov_b32", self.v_oob, 0x80000000)
-        # k-contiguous pieces (A always; B when it is passed transposed): piece column pc = tid % 8 (k0 = 4 pc), row xr = tid / 8
-        # (+ 32 per piece);  LDS: row * RS + (pc >> 2) * 64 + (pc & 3) * 4, element j of the piece 16 j bytes further
-        e("v_lshrrev_b32", t[5], 2, pc)
-        e("v_lshlrev_b32", t[5], 6, t[5])                    # (pc >> 2) * 64
+            self.pipe_eligible()
+        self.lane_setup()
+
+    def kpiece_word(self, pc):
+        """A piece (k0 = 4 pc .. k0 + 3 of one row): + (pc & 3) * 4, element j of the piece 16 j bytes further"""
+        e, t = self.p.emit, self.vt
         e("v_and_b32", t[6], 3, pc)
-        e("v_lshl_add_u32", t[5], t[6], 2, t[5])             # + (pc & 3) * 4
-        e("v_mul_u32_u24", t[6], RS, xr)
+        e("v_lshl_add_u32", t[5], t[6], 2, t[5])
+
+    def xpieces_B(self):
+        """B pieces (x-contiguous: columns x0 .. x0 + 3 of one k): column quad c8 = tid % 8, row k = tid / 8 (all 32 k of the K-tile in
+        one pass), pass j covers columns 32 j .. 32 j + 31 (8 lanes read 128 contiguous bytes of a row of B)
+        LDS: (BM + 32 j + 4 c8) * RS + (k >> 4) * 64 + (k & 3) * 16 + ((k >> 2) & 3) * 4, element e of the piece e * RS further"""
+        c, e, t, st = self.c, self.p.emit, self.vt, self.s_t
+        RS = c.RS
+        c8, k = t[0], t[1]          # (lane_setup's pc, xr)
+        e("v_lshrrev_b32", t[5], 4, k)
+        e("v_lshlrev_b32", t[5], 6, t[5])                    # (k >> 4) * 64
+        e("v_and_b32", t[6], 3, k)
+        e("v_lshl_add_u32", t[5], t[6], 4, t[5])             # + (k & 3) * 16
+        e("v_bfe_u32", t[6], k, 2, 2)
+        e("v_lshl_add_u32", t[5], t[6], 2, t[5])             # + ((k >> 2) & 3) * 4
+        e("v_mul_u32_u24", t[6], 4 * RS, c8)
         e("v_add_u32", t[5], t[5], t[6])
-        for i in range(c.NPA):
-            e("v_add_u32", self.WA[i][2], 32 * RS * i, t[5])
-            e("v_add_u32", self.WA[i][0], c.STAGE, self.WA[i][2])
-            e("v_add_u32", self.WA[i][1], 2 * c.STAGE, self.WA[i][2])
-        e("s_lshl_b32", st[5], self.s_ldb, 2, comment="ldb * 4 bytes")
-        if c.b_kcontig:
-            e("v_add_u32", t[5], c.BM * RS, t[5])
-            for j in range(c.NPB):
-                e("v_add_u32", self.WB[j][2], 32 * RS * j, t[5])
-                e("v_add_u32", self.WB[j][0], c.STAGE, self.WB[j][2])
-                e("v_add_u32", self.WB[j][1], 2 * c.STAGE, self.WB[j][2])
-            e("s_mov_b32", self.s_bstep, c.BK * 4)
-        else:
-            # B pieces (x-contiguous: columns x0 .. x0 + 3 of one k): column quad c8 = tid % 8, row k = tid / 8 (all 32 k of the
-            # K-tile in one pass), pass j covers columns 32 j .. 32 j + 31 (8 lanes read 128 contiguous bytes of a row of B)
-            #   LDS: (BM + 32 j + 4 c8) * RS + (k >> 4) * 64 + (k & 3) * 16 + ((k >> 2) & 3) * 4, element e of the piece e * RS further
-            c8, k = t[0], t[1]
-            e("v_lshrrev_b32", t[5], 4, k)
-            e("v_lshlrev_b32", t[5], 6, t[5])                    # (k >> 4) * 64
-            e("v_and_b32", t[6], 3, k)
-            e("v_lshl_add_u32", t[5], t[6], 4, t[5])             # + (k & 3) * 16
-            e("v_bfe_u32", t[6], k, 2, 2)
-            e("v_lshl_add_u32", t[5], t[6], 2, t[5])             # + ((k >> 2) & 3) * 4
-            e("v_mul_u32_u24", t[6], 4 * RS, c8)
-            e("v_add_u32", t[5], t[5], t[6])
-            e("v_add_u32", t[5], c.BM * RS, t[5])
-            for j in range(c.NPB):
-                e("v_add_u32", self.WB[j][2], 32 * RS * j, t[5])
-                e("v_add_u32", self.WB[j][0], c.STAGE, self.WB[j][2])
-                e("v_add_u32", self.WB[j][1], 2 * c.STAGE, self.WB[j][2])
-            e("v_mul_lo_u32", t[7], k, st[5])
-            e("v_lshl_add_u32", self.vVB[0], c8, 4, t[7])
-            for j in range(1, c.NPB):
-                e("v_add_u32", self.vVB[j], 128, self.vVB[j - 1])
-            e("s_mul_i32", self.s_bstep, st[5], c.BK, comment="B advances BK rows per K-tile")
+        e("v_add_u32", t[5], c.BM * RS, t[5])
+        for j in range(c.NPB):
+            e("v_add_u32", self.WB[j][2], 32 * RS * j, t[5])
+            e("v_add_u32", self.WB[j][0], c.STAGE, self.WB[j][2])
+            e("v_add_u32", self.WB[j][1], 2 * c.STAGE, self.WB[j][2])
+        e("v_mul_lo_u32", t[7], k, st[5])
+        e("v_lshl_add_u32", self.vVB[0], c8, 4, t[7])
+        for j in range(1, c.NPB):
+            e("v_add_u32", self.vVB[j], 128, self.vVB[j - 1])
 
-    def run_setup(self):
-        """one run = k in [kb, kb + Keff) of tile (m0, n0) (Keff a multiple of 4)"""
-        c, p = self.c, self.p
-        e = p.emit
-        t, st = self.vt, self.s_t
-        Keff = self.s_Keff
-        # K tail: pieces of the last K-tile beyond K get an offset the bounds check rejects (they read as 0, like Laser's zero-padded
-        # panels, gemm_packing.nim:46-55)
-        e("s_and_b32", self.s_ktail, Keff, c.BK - 1)
-        e("v_and_b32", t[5], 7, v(0))
-        e("v_lshlrev_b32", t[5], 2, t[5])
-        e("v_cmp_gt_u32", self.s_tm, self.s_ktail, t[5])
-        e("s_lshl_b32", st[3], self.s_lda, 2, comment="lda * 4 bytes")
-        self.kcontig_goff64(self.vVA, c.NPA, st[3])          # (xr + 32 i) * ld bytes + pc * 16: the same piece map as the f64 kernels
-        e("s_lshl_b32", st[5], self.s_ldb, 2, comment="ldb * 4 bytes")
-        if c.b_kcontig:
-            self.kcontig_goff64(self.vVB, c.NPB, st[5])
-        e("s_nop", 4)
-        Gen.ab_descriptors(self)                             # 4-byte elements: the f32 kernels' descriptors
-        self.c_descriptor()
-        e("s_add_u32", self.s_rem, Keff, c.BK - 1)
-        e("s_lshr_b32", self.s_rem, self.s_rem, (c.BK).bit_length() - 1)
-        # ---- tile 0 -> LDS stage 0, tile 1 -> staging registers ----
-        # three or more K-tiles: tiles 0 and 1 requested back to back (tile 0 through the idle fragment registers): a run starts after
-        # one memory latency instead of two (f32_kernel.py run_setup)
-        L_slow, L_join = p.label("fewtiles"), p.label("tiles01")
-        state = (list(self.vmq), list(self.lgq))
-        e("s_cmp_lt_u32", self.s_rem, 3)
-        e("s_cbranch_scc1", L_slow)
-        pool = [r for slot in range(2) for r in (self.fa[slot] + self.fb[slot])]
-        assert len(pool) >= c.NPA + c.NPB
-        real = (self.stA, self.stB)
-        tmp = (pool[:c.NPA], pool[c.NPA:c.NPA + c.NPB])
-        self.stA, self.stB = tmp
-        self.issue_loads_all()
-        self.advance_srds()
-        self.stA, self.stB = real
-        self.issue_loads_all()
-        self.advance_srds()
-        self.stA, self.stB = tmp
-        for pi in range(c.NPA):
-            self.store_A_piece(pi, k=2)
-        for pj in range(c.NPB):
-            self.store_B_piece(pj, k=2)
-        self.stA, self.stB = real
-        e("s_branch", L_join)
-        fast_state = (list(self.vmq), list(self.lgq))
-        self.vmq, self.lgq = state
-        p.place(L_slow)
-        self.tail_mask_if(self.s_rem, 1)
-        self.issue_loads_all()
-        self.advance_srds()
-        for pi in range(c.NPA):
-            self.store_A_piece(pi, k=2)
-        for pj in range(c.NPB):
-            self.store_B_piece(pj, k=2)
-        self.tail_mask_if(self.s_rem, 2)
-        self.issue_loads_all()
-        self.advance_srds()
-        assert (self.vmq, self.lgq) == fast_state, "the two prologue paths must leave the same loads and stores in flight"
-        p.place(L_join)
-        self.tail_mask_if(self.s_rem, 3)
-        self.init_accumulators()
-        self.lg_wait(None)
-        e("s_barrier")
-        self.read_group(0, 0, 0)
-
-    def c_descriptor(self):
-        """srdC = the whole matrix: bytes = (M - 1) * ldc * 4 + N * 4"""
-        e, st = self.p.emit, self.s_t
-        C_ = self.ka0.sub(4, 2)
-        e("s_lshl_b32", self.s_ldc4, self.s_ldc, 2)
-        e("s_mov_b32", self.srdC[0], C_[0])
-        e("s_and_b32", self.srdC[1], C_[1], 0xffff)
-        e("s_sub_u32", st[0], self.s_M, 1)
-        e("s_mul_i32", st[0], st[0], self.s_ldc4)
-        # C[i][j] at i * ldc + j * csC (MatrixView, gemm_utils.nim:36-60): bytes = (M - 1) * ldc * 4 + (N - 1) * csC * 4 + 4
-        e("s_load_dword", self.s_csC4, s(0, 2), KA_EPI + 12)
-        e("s_waitcnt", lgkmcnt=0)
-        e("s_max_u32", self.s_csC4, self.s_csC4, 1)
-        e("s_lshl_b32", self.s_csC4, self.s_csC4, 2)
-        e("s_sub_u32", st[2], self.s_N, 1)
-        e("s_mul_i32", st[2], st[2], self.s_csC4)
-        e("s_add_u32", st[2], st[2], 4)
-        e("s_add_u32", self.srdC[2], st[0], st[2])
-        e("s_mov_b32", self.srdC[3], 0x00020000)
-
-    def advance_srds(self, which=None):
-        return Gen.advance_srds(self, which)                 # steps of BK * 4 bytes (A, B^T) / BK rows (B)
+    def c_row_step(self):
+        pass      # (a lane's rows travel in the accesses' scalar offset: c_addr_setup)
 
     # ------------------------------------------------------------------ LDS stores: two ds_write2_b32 per piece
     def store_A_piece(self, pi, ops=None, k=0):
@@ -324,29 +129,6 @@ class Gen16(Gen64):
     def emit_mfma(self, b, slot, i, n, u, srcc):
         self.p.emit("v_mfma_f32_16x16x4_f32", self.acc[b], self.fa[slot][i][u], self.fb[slot][n][u], srcc)
 
-    def fold_before(self, b):
-        T = self.vT[0]
-        for r in range(4):
-            self.p.emit("v_accvgpr_read_b32", T[r], self.acc[b][r])
-
-    def fold_after(self, b):
-        p, e, T = self.p, self.p.emit, self.vT[0]
-        # run += alpha * slice, unfused (gemm_ukernel_generic.nim:68-76); alpha == 1: the multiplies (out of line) are a branch not taken
-        lmul, lback = p.label("amul"), p.label("aback")
-        e("s_cmp_lg_u32", self.s_alpha, 0x3f800000)
-        e("s_cbranch_scc1", lmul)
-        p.place(lback)
-        self.outlined.append((lmul, [("v_mul_f32", T[r], self.s_alpha, T[r]) for r in range(4)], lback))
-        if self.c.runv:
-            for j in range(2):
-                e("v_pk_add_f32", self.run[b].sub(2 * j, 2), self.run[b].sub(2 * j, 2), T.sub(2 * j, 2))
-            return
-        for r in range(4):
-            tt = self.vt[r]
-            e("v_accvgpr_read_b32", tt, self.run[b][r])
-            e("v_add_f32", tt, tt, T[r])
-            e("v_accvgpr_write_b32", self.run[b][r], tt)
-
     def trans_after(self, b):
         """transition body (Cfg.pipe), block b = (i, n): vT[0..3] hold the slice sum of the tile being FINISHED, the MFMA in front of this
         gap has restarted the chain for the new tile: C = run + alpha * slice (one chain: alpha * sum) leaves for memory from here, the
@@ -354,11 +136,7 @@ class Gen16(Gen64):
         from srdCd = this wave's first row of the old tile."""
         c, p, e, T, st = self.c, self.p, self.p.emit, self.vT[0], self.s_t
         i, n = b // c.TN, b % c.TN
-        lmul, lback = p.label("tmul"), p.label("tback")
-        e("s_cmp_lg_u32", self.s_alpha, 0x3f800000)
-        e("s_cbranch_scc1", lmul)
-        p.place(lback)
-        self.outlined.append((lmul, [("v_mul_f32", T[r], self.s_alpha, T[r]) for r in range(4)], lback))
+        self.alpha_mul_outlined("t")
         soff = st[0]
         pair = v(self.vt[0].idx, 4)
         for d in range(4):
@@ -385,80 +163,12 @@ class Gen16(Gen64):
     def pipe_c_addr(self):
         """(vC, srdCd) for the deferred stores of the tile (m0, n0): srdCd starts at this wave's first row, vC[n] = the lane's offset
         from there (4 q rows down, block column n; out of bounds beyond N)"""
-        c, e, t, st = self.c, self.p.emit, self.vt, self.s_t
-        lane, r16, q = t[0], t[1], t[2]
-        e("v_and_b32", lane, 63, v(0))
-        e("v_and_b32", r16, 15, lane)
-        e("v_lshrrev_b32", q, 4, lane)
-        e("s_add_u32", st[0], self.s_m0, self.s_wm0)
-        e("s_mul_hi_u32", st[2], st[0], self.s_ldc4)
-        e("s_mul_i32", st[3], st[0], self.s_ldc4)
-        e("s_add_u32", self.srdCd[0], self.srdC[0], st[3])
-        e("s_addc_u32", self.srdCd[1], self.srdC[1], st[2])
-        e("s_and_b32", self.srdCd[1], self.srdCd[1], 0xffff)
-        e("s_mov_b32", self.srdCd[3], 0x00020000)
-        e("s_sub_u32", self.srdCd[2], self.srdC[2], st[3])              # what is left of C from there (0: the wave's rows lie beyond M)
-        e("s_cselect_b32", self.srdCd[2], 0, self.srdCd[2])
-        e("s_cmp_lg_u32", st[2], 0)
-        e("s_cselect_b32", self.srdCd[2], 0, self.srdCd[2])
+        e, t = self.p.emit, self.vt
+        r16, q = self.lane_rq()
+        self.srdCd_setup()
         e("v_lshlrev_b32", t[3], 2, q)
         e("v_mul_lo_u32", t[3], t[3], self.s_ldc4)
-        e("s_add_u32", st[1], self.s_n0, self.s_wn0)
-        e("v_add_u32", t[4], st[1], r16)
-        e("v_mul_lo_u32", t[6], t[4], self.s_csC4)
-        e("v_add_u32", t[3], t[3], t[6])
-        e("s_lshl_b32", st[1], self.s_csC4, 4)
-        for n in range(c.TN):
-            e("v_add_u32", t[5], 16 * n, t[4])
-            e("v_cmp_gt_u32", VCC, self.s_N, t[5])
-            if n:
-                e("v_add_u32", t[3], st[1], t[3])
-            e("v_mov_b32", t[7], 0x80000000)
-            e("v_cndmask_b32", self.vC[n], t[7], t[3], VCC)
-
-    def init_accumulators(self):
-        if not self.c.runv:
-            return Gen.init_accumulators(self)
-        # (f32_kernel.Gen.init_accumulators with the running sum in arch VGPRs)
-        from .f32_kernel import MODE_NORMAL
-        c, p = self.c, self.p
-        e = p.emit
-        for b in range(c.NB):
-            for r in range(c.ACCR):
-                e("v_accvgpr_write_b32", self.acc[b][r], 0)
-        keep = p.label("keeprun")
-        if c.persistent:
-            e("s_cmp_lg_u32", self.s_mode, MODE_NORMAL)
-            e("s_cbranch_scc1", keep)
-        for b in range(c.NB):
-            for j in range(2):
-                e("v_mov_b64", self.run[b].sub(2 * j, 2), 0)
-        self.load_beta_c()
-        p.place(keep)
-
-    def fold_block(self, b):
-        e, T = self.p.emit, self.vT[0]
-        for r in range(4):
-            e("v_accvgpr_read_b32", T[r], self.acc[b][r])
-        for r in range(4):
-            e("v_mul_f32", T[r], self.s_alpha, T[r])      # (1.0 * x is x)
-        if self.c.runv:
-            for j in range(2):
-                e("v_pk_add_f32", self.run[b].sub(2 * j, 2), self.run[b].sub(2 * j, 2), T.sub(2 * j, 2))
-            return
-        for r in range(4):
-            tt = self.vt[r]
-            e("v_accvgpr_read_b32", tt, self.run[b][r])
-            e("v_add_f32", tt, tt, T[r])
-            e("v_accvgpr_write_b32", self.run[b][r], tt)
-
-    def acc_add_block(self, b):
-        e, T = self.p.emit, self.vT[0]
-        for r in range(4):
-            tt = self.vt[r]
-            e("v_accvgpr_read_b32", tt, self.acc[b][r])
-            e("v_add_f32", tt, tt, T[r])
-            e("v_accvgpr_write_b32", self.acc[b][r], tt)
+        self.c_columns(r16)
 
     # ------------------------------------------------------------------ epilogue
     def c_addr_setup(self):
@@ -466,14 +176,16 @@ class Gen16(Gen64):
         check always rejects for columns beyond N).  The rows of a lane -- + d within a block, + 16 per block row -- travel in the
         accesses' SCALAR offset, which gfx950 includes in a raw buffer's range check (scripts/probes/buffer_soffset.hip): rows beyond
         M fall off the end of srdC.  No vector address arithmetic between the stores."""
-        c, e, t, st = self.c, self.p.emit, self.vt, self.s_t
-        lane, r16, q = t[0], t[1], t[2]
-        e("v_and_b32", lane, 63, v(0))
-        e("v_and_b32", r16, 15, lane)
-        e("v_lshrrev_b32", q, 4, lane)
+        e, t, st = self.p.emit, self.vt, self.s_t
+        r16, q = self.lane_rq()
         e("s_add_u32", st[0], self.s_m0, self.s_wm0)
         e("v_lshl_add_u32", t[3], q, 2, st[0])
         e("v_mul_lo_u32", t[3], t[3], self.s_ldc4)
+        self.c_columns(r16)
+
+    def c_columns(self, r16):
+        """vC[n] = vt[3] (the row's bytes) + the bytes of column n0 + wn0 + r16 + 16 n; out of bounds beyond N"""
+        c, e, t, st = self.c, self.p.emit, self.vt, self.s_t
         e("s_add_u32", st[1], self.s_n0, self.s_wn0)
         e("v_add_u32", t[4], st[1], r16)
         e("v_mul_lo_u32", t[6], t[4], self.s_csC4)
@@ -486,6 +198,11 @@ class Gen16(Gen64):
                 e("v_add_u32", t[3], st[1], t[3])
             e("v_mov_b32", t[7], 0x80000000)
             e("v_cndmask_b32", self.vC[n], t[7], t[3], VCC)
+
+    def read_acc(self, tt, b, d):
+        """tt = alpha * (element d of block b's chain)"""
+        self.p.emit("v_accvgpr_read_b32", tt, self.acc[b][d])
+        self.p.emit("v_mul_f32", tt, self.s_alpha, tt)
 
     def c_rows(self, fn):
         """fn(i, d, soff): this lane's accumulator rows in C order; soff = the SGPR holding (16 i + d) * ldc * 4"""
@@ -597,8 +314,7 @@ class Gen16(Gen64):
                 for n in range(c.TN):
                     b = i * c.TN + n
                     tt, uu = t[n], t[5 + n]
-                    e("v_accvgpr_read_b32", tt, self.acc[b][d])
-                    e("v_mul_f32", tt, self.s_alpha, tt)
+                    self.read_acc(tt, b, d)
                     if c.exact and c.runv:
                         e("v_add_f32", tt, self.run[b][d], tt)
                     elif c.exact:
@@ -634,8 +350,7 @@ class Gen16(Gen64):
                 for n in range(c.TN):
                     b = i * c.TN + n
                     tt, uu = t[(2 * n) % 8], t[(2 * n + 1) % 8]
-                    e("v_accvgpr_read_b32", tt, self.acc[b][d])
-                    e("v_mul_f32", tt, self.s_alpha, tt)
+                    self.read_acc(tt, b, d)
                     if c.runv:
                         e("v_add_f32", tt, self.run[b][d], tt)
                     else:
@@ -654,8 +369,7 @@ class Gen16(Gen64):
             def row0(i, d, soff):
                 for n in range(c.TN):
                     tt = t[(2 * n) % 8]
-                    e("v_accvgpr_read_b32", tt, self.acc[i * c.TN + n][d])
-                    e("v_mul_f32", tt, self.s_alpha, tt)
+                    self.read_acc(tt, i * c.TN + n, d)
                     e("buffer_store_dword", tt, self.vC[n], self.srdC, soff, offen=True)
             self.c_rows(row0)
             e("s_branch", done)
@@ -669,8 +383,7 @@ class Gen16(Gen64):
                 for n in range(c.TN):
                     tt, x = t[4 + n % 4], P[n]
                     e("v_mul_f32", x, self.s_beta, x)
-                    e("v_accvgpr_read_b32", tt, self.acc[i * c.TN + n][d])
-                    e("v_mul_f32", tt, self.s_alpha, tt)
+                    self.read_acc(tt, i * c.TN + n, d)
                     e("v_add_f32", tt, x, tt)
                     e("buffer_store_dword", tt, self.vC[n], self.srdC, soff, offen=True)
             self.c_rows(row1)
@@ -686,16 +399,4 @@ def make(name, **over):
 
 
 if __name__ == "__main__":
-    import argparse
-    import os
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", required=True)
-    args = ap.parse_args()
-    os.makedirs(args.out, exist_ok=True)
-    for name in CONFIGS:
-        g = make(name)
-        g.build()
-        sym = "lh_f32x16_" + name
-        with open(os.path.join(args.out, sym + ".s"), "w") as f:
-            f.write(kernel_text(g, sym))
-        print(sym, len(g.p.ins), "instructions")
+    write_kernels("lh_f32x16_", CONFIGS, make)

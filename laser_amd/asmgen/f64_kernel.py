@@ -1,6 +1,6 @@
 """float64 GEMM kernels for gfx950, hand-scheduled: the f32 generator's program structure (f32_kernel.Gen: 3-stage LDS ring,
 one barrier per K-tile, one body per stage, counted waits, accumulators in AGPRs, laser-order fold every kc) with the f64
-matrix instruction and its own LDS image.
+matrix instruction on the 16x16-block families' padded-row LDS image (gen16x16.Gen16x16, the base class shared with f32x16_kernel).
 
   v_mfma_f64_16x16x4_f64   16x16 block, 4 k per instruction (64 cycles per SIMD on MI355X), lane l feeds A[l % 16][l / 16] and
                            B[l / 16][l % 16] and holds D[l / 16 + 4 * d][l % 16], d = 0..3: 8 accumulator registers per block
@@ -14,8 +14,9 @@ ds_read_b128 -- and is 144 bytes long: with 9 chunks per row the 16 rows a 16-la
   B piece (16 bytes = columns x0, x0 + 1 of one k) -> the same chunk of rows x0 and x0 + 1:     offsets 0, +144 bytes
 Operands: A row-major (k-contiguous), B row-major (x-contiguous) or passed transposed (`_nt`: k-contiguous, stored like A), C
 row-major; K a multiple of 2; any alpha / beta (float64 in the kernel arguments)."""
-from .core import v, a, s, VCC
-from .f32_kernel import Gen, Cfg, kernel_text, KA_A, KA_LDA, KA_DBG, KA_CONV1  # noqa: F401
+from .core import v, s, VCC
+from .f32_kernel import Cfg, kernel_text, write_kernels, KA_A, KA_LDA  # noqa: F401
+from .gen16x16 import Gen16x16
 
 CONFIGS = {
     # one wave per SIMD: 2 x 2 waves of 64x64 = 16 blocks = 128 accumulator registers (+ 128 for the running sum)
@@ -34,389 +35,94 @@ KA_ALPHA64 = 72      # alpha, beta as float64 (the f32 kernels' float fields at 
 KA_BSA64 = 88        # batch stride of A in bytes (u64); B's and C's at 112 / 120 as in the f32 kernels
 
 
-class Gen64(Gen):
+class Gen64(Gen16x16):
+    VT_ALIGN = 2         # (register pairs)
+
     # ------------------------------------------------------------------ registers
-    def alloc(self):
-        c, p = self.c, self.p
-        S, V = p.salloc, p.valloc
-        self.ka0 = S(8, align=4)
-        self.ka1 = S(8, align=4)
-        self.s_lda, self.s_ldb, self.s_ldc, self.s_M, self.s_N, self.s_K = (self.ka1[i] for i in range(6))
-        self.s_alpha, self.s_beta = self.ka1[6], self.ka1[7]
-        self.srdA, self.srdB, self.srdC = S(4), S(4), S(4)
-        self.s_rem, self.s_cnt = S(), S()
-        self.s_bstep = S()
-        self.s_m0, self.s_n0, self.s_wave, self.s_wm0, self.s_wn0 = S(), S(), S(), S(), S()
-        self.s_t = [S() for _ in range(6)]
+    def alloc_scalars(self):
+        S = self.p.salloc
+        self.alloc_args()
         self.s_ab = S(4, align=4)                 # alpha (2 registers), beta (2 registers): float64
         self.s_al, self.s_be = self.s_ab.sub(0, 2), self.s_ab.sub(2, 2)
         self.s_a1, self.s_b0 = S(), S()           # 0 when alpha == 1.0 / when beta == +-0.0
         self.s_bsA, self.s_bsBC = S(2, align=2), S(4, align=4)   # batch strides in bytes (grid y = batch index)
         self.s_ldc4, self.s_ldc20 = S(), S()      # here: ldc * 8 bytes, 4 * ldc * 8 (the next accumulator row of a lane)
         self.s_csC4 = None
-        if c.pipe:
-            # pipelined tile transitions (f32_kernel.py Cfg.pipe): bit 0 = this launch may pipeline, bit 1 = armed
-            self.s_pipe = S()
-            self.srdCd = S(4)        # C from this wave's first row of the tile being finished (rows through the stores' scalar offset)
+        self.alloc_pipe()
         self.alloc_sched()
-        self.acc = [p.aalloc(8) for _ in range(c.NB)]
-        # runv / dataa (f32_kernel.py Cfg, round 6): the running sum in arch VGPRs (the slice fold of a block is 8 v_accvgpr_read + 4
-        # v_add_f64 where the all-AGPR plan has 28 VALU operations), fragments + staging in AGPRs where the VGPR file would overflow
-        self.run = [V(8) if c.runv else p.aalloc(8) for _ in range(c.NB)] if c.exact else None
-        D4 = (lambda n: p.aalloc(n)) if c.dataa else V
-        self.fa = [[D4(4) for _ in range(c.TM)] for _ in range(2)]
-        self.fb = [[D4(4) for _ in range(c.TN)] for _ in range(2)]
-        self.stA = [D4(4) for _ in range(c.NPA)]
-        self.stB = [D4(4) for _ in range(c.NPB)]
-        self.st_sets = [(self.stA, self.stB)]
-        self.RA = [[V() for _ in range(3)] for _ in range(c.NG)]
-        self.RB = [[V() for _ in range(3)] for _ in range(c.NG)]
-        self.WA = [[V() for _ in range(3)] for _ in range(c.NPA)]   # [piece][stage]
-        self.WB = [[V() for _ in range(3)] for _ in range(c.NPB)]
-        self.v_oob = V()
-        self.s_tm = S(2)
-        self.s_ktail = S()
-        self.vVA = [V() for _ in range(c.NPA)]
-        self.vVB = [V() for _ in range(c.NPB)]
-        self.vC = [V() for _ in range(c.TN)]
-        if c.debug:
-            self.srdD = S(4)
-            self.s_dslot = S()
-            self.v_dbg = V()
-        self.ndump = 0
-        self.dump_names = []
-        self.vT = [V(16, align=2)]
-        blk = V(12, align=4)
-        self.vt = [blk[i] for i in range(10)]
-        self.vF, self.vFaddr, self.vFoff = blk.sub(4, 4), blk[10], blk[11]
 
     # ------------------------------------------------------------------ prologue (f32_kernel.Gen.prologue: once, scheduler, run_setup)
     def once(self):
         c, p = self.c, self.p
-        e = p.emit
-        t, st = self.vt, self.s_t
-        RS = c.RS
+        e, st = p.emit, self.s_t
         p.note(f"f64 {c.name}: {c.BM}x{c.BN}x{c.BK} tile, 4 waves, wave tile {c.WTM}x{c.WTN}, "
                f"{'laser-order (kc = 256 slices)' if c.exact else 'one accumulation chain'}")
         e("s_load_dwordx8", self.ka0, s(0, 2), KA_A)
         e("s_load_dwordx8", self.ka1, s(0, 2), KA_LDA)
         e("s_load_dwordx4", self.s_ab, s(0, 2), KA_ALPHA64)
-        # batched problems (gemm_strided_batched; the kc slices of the slice-parallel form): workgroup id y = batch index, operand b at
-        # base + b * batch stride (bytes, 64-bit; 0 for plain launches) -- as in the f32 kernels
-        e("s_load_dwordx2", self.s_bsA, s(0, 2), KA_BSA64)
-        e("s_load_dwordx4", self.s_bsBC, s(0, 2), KA_CONV1 + 8)
-        e("s_waitcnt", lgkmcnt=0)
-        for ptr, bs in ((self.ka0.sub(0, 2), self.s_bsA), (self.ka0.sub(2, 2), self.s_bsBC.sub(0, 2)), (self.ka0.sub(4, 2), self.s_bsBC.sub(2, 2))):
-            e("s_mul_i32", st[2], s(3), bs[0])
-            e("s_mul_hi_u32", st[3], s(3), bs[0])
-            e("s_mul_i32", st[4], s(3), bs[1])
-            e("s_add_u32", st[3], st[3], st[4])
-            e("s_add_u32", ptr[0], ptr[0], st[2])
-            e("s_addc_u32", ptr[1], ptr[1], st[3])
+        self.batch_offsets(KA_BSA64)
         e("s_xor_b32", st[2], self.s_al[1], 0x3ff00000)
         e("s_or_b32", self.s_a1, st[2], self.s_al[0])
         e("s_and_b32", st[2], self.s_be[1], 0x7fffffff)
         e("s_or_b32", self.s_b0, st[2], self.s_be[0])
         if c.pipe:
-            # tile transitions of this launch may be pipelined: beta == 0 (the next tile's running sum starts at 0), K a multiple of BK
-            # (no K-tail masks to undo between tiles), at least three K-tiles (the switch happens two tile bodies before a tile ends)
-            e("s_and_b32", st[2], self.s_K, c.BK - 1)
-            e("s_or_b32", st[2], st[2], self.s_b0)
-            e("s_cmp_eq_u32", st[2], 0)
-            e("s_cselect_b32", self.s_pipe, 1, 0)
-            e("s_cmp_lt_u32", self.s_K, 3 * c.BK)
-            e("s_cselect_b32", self.s_pipe, 0, self.s_pipe)
-        if c.debug:
-            e("s_load_dwordx2", self.srdD.sub(0, 2), s(0, 2), KA_DBG)
-            e("s_waitcnt", lgkmcnt=0)
-            e("s_and_b32", self.srdD[1], self.srdD[1], 0xffff)
-            e("s_mov_b32", self.srdD[2], 0x10000000)
-            e("s_mov_b32", self.srdD[3], 0x00020000)
-            e("v_lshlrev_b32", self.v_dbg, 2, v(0))
-            self.dump("tid", v(0))
-        tid = v(0)
-        lane, r16, q = t[0], t[1], t[2]
-        e("v_and_b32", lane, 63, tid)
-        e("v_lshrrev_b32", t[5], 6, tid)
-        e("s_nop", 1, comment="VALU write -> v_readfirstlane of the same VGPR needs wait states")
-        e("v_readfirstlane_b32", self.s_wave, t[5])
-        e("s_nop", 3)
-        e("v_and_b32", r16, 15, lane)
-        e("v_lshrrev_b32", q, 4, lane)
-        e("s_lshr_b32", st[2], self.s_wave, 1)
-        e("s_mul_i32", self.s_wm0, st[2], c.WTM)
-        e("s_and_b32", st[2], self.s_wave, 1)
-        e("s_mul_i32", self.s_wn0, st[2], c.WTN)
-        # fragment reads of group g: (wm0 + r16) * RS [+ BM * RS + (wn0 + r16) * RS for B] + (4g + q) * 16
-        e("v_add_u32", t[5], self.s_wm0, r16)
-        e("v_mul_u32_u24", t[6], RS, t[5])
-        e("v_add_u32", t[5], self.s_wn0, r16)
-        e("v_mul_u32_u24", t[7], RS, t[5])
-        e("v_add_u32", t[7], c.BM * RS, t[7])
-        for g in range(c.NG):
-            e("v_lshl_add_u32", t[5], q, 4, 64 * g)
-            for R, row in ((self.RA, t[6]), (self.RB, t[7])):
-                e("v_add_u32", R[g][0], t[5], row)
-                e("v_add_u32", R[g][1], c.STAGE, R[g][0])
-                e("v_add_u32", R[g][2], 2 * c.STAGE, R[g][0])
-        pc, xr = t[0], t[1]
-        e("v_and_b32", pc, 7, tid)
-        e("v_lshrrev_b32", xr, 3, tid)
-        e("v_mov_b32", self.v_oob, 0x80000000)
-        # A pieces: piece column pc = tid % 8 (k0 = 2 pc), row xr = tid / 8 (+ 32 per piece)
-        #   LDS: row * RS + (4 * (pc >> 2) + 2 * (pc & 1)) * 16 + ((pc >> 1) & 1) * 8
-        e("v_lshrrev_b32", t[5], 2, pc)
-        e("v_lshlrev_b32", t[5], 6, t[5])                    # (pc >> 2) * 64
+            self.pipe_eligible()
+        self.lane_setup()
+
+    def pipe_eligible(self):
+        """tile transitions of this launch may be pipelined: beta == 0 (the next tile's running sum starts at 0), K a multiple of BK
+        (no K-tail masks to undo between tiles), at least three K-tiles (the switch happens two tile bodies before a tile ends)"""
+        c, e, st = self.c, self.p.emit, self.s_t
+        e("s_and_b32", st[2], self.s_K, c.BK - 1)
+        e("s_or_b32", st[2], st[2], self.s_b0)
+        e("s_cmp_eq_u32", st[2], 0)
+        e("s_cselect_b32", self.s_pipe, 1, 0)
+        e("s_cmp_lt_u32", self.s_K, 3 * c.BK)
+        e("s_cselect_b32", self.s_pipe, 0, self.s_pipe)
+
+    def kpiece_word(self, pc):
+        """A piece (k0 = 2 pc, k0 + 1 of one row): + (pc & 1) * 32 + ((pc >> 1) & 1) * 8 -- chunk 4 * (k / 8) + k % 4 holds k and k + 4"""
+        e, t = self.p.emit, self.vt
         e("v_and_b32", t[6], 1, pc)
-        e("v_lshl_add_u32", t[5], t[6], 5, t[5])             # + (pc & 1) * 32
+        e("v_lshl_add_u32", t[5], t[6], 5, t[5])
         e("v_bfe_u32", t[6], pc, 1, 1)
-        e("v_lshl_add_u32", t[5], t[6], 3, t[5])             # + ((pc >> 1) & 1) * 8
-        e("v_mul_u32_u24", t[6], RS, xr)
+        e("v_lshl_add_u32", t[5], t[6], 3, t[5])
+
+    def xpieces_B(self):
+        """B pieces (x-contiguous): x pair px = tid % (BN / 2), row k = tid / (BN / 2) (+ KS per piece, KS = 512 / BN)
+        LDS: BM * RS + 2 px * RS + (4 * (k >> 3) + (k & 3)) * 16 + ((k >> 2) & 1) * 8; k = k0 + KS * j with k0 < KS"""
+        c, e, t, st = self.c, self.p.emit, self.vt, self.s_t
+        RS, tid = c.RS, v(0)
+        HB = c.BN // 2
+        KS = 256 // HB
+        px, k0 = t[0], t[1]
+        e("v_and_b32", px, HB - 1, tid)
+        e("v_lshrrev_b32", k0, HB.bit_length() - 1, tid)
+        e("v_and_b32", t[5], 3, k0)
+        e("v_lshlrev_b32", t[5], 4, t[5])                    # (k0 & 3) * 16
+        e("v_bfe_u32", t[6], k0, 2, 1)
+        e("v_lshl_add_u32", t[5], t[6], 3, t[5])             # + ((k0 >> 2) & 1) * 8      (k0 < 8)
+        e("v_mul_u32_u24", t[6], 2 * RS, px)
         e("v_add_u32", t[5], t[5], t[6])
-        for i in range(c.NPA):
-            e("v_add_u32", self.WA[i][2], 32 * RS * i, t[5])
-            e("v_add_u32", self.WA[i][0], c.STAGE, self.WA[i][2])
-            e("v_add_u32", self.WA[i][1], 2 * c.STAGE, self.WA[i][2])
-        e("s_lshl_b32", st[5], self.s_ldb, 3, comment="ldb * 8 bytes")
-        if c.b_kcontig:
-            # B passed transposed: its pieces are (column x, k0 .. k0 + 1) -- the A layout with the B panel's offsets
-            e("v_add_u32", t[5], c.BM * RS, t[5])
-            for j in range(c.NPB):
-                e("v_add_u32", self.WB[j][2], 32 * RS * j, t[5])
-                e("v_add_u32", self.WB[j][0], c.STAGE, self.WB[j][2])
-                e("v_add_u32", self.WB[j][1], 2 * c.STAGE, self.WB[j][2])
-            e("s_mov_b32", self.s_bstep, c.BK * 8)
-        else:
-            # B pieces: x pair px = tid % (BN / 2), row k = tid / (BN / 2) (+ KS per piece, KS = 512 / BN)
-            #   LDS: BM * RS + 2 px * RS + (4 * (k >> 3) + (k & 3)) * 16 + ((k >> 2) & 1) * 8; k = k0 + KS * j with k0 < KS
-            HB = c.BN // 2
-            KS = 256 // HB
-            px, k0 = t[0], t[1]
-            e("v_and_b32", px, HB - 1, tid)
-            e("v_lshrrev_b32", k0, HB.bit_length() - 1, tid)
-            e("v_and_b32", t[5], 3, k0)
-            e("v_lshlrev_b32", t[5], 4, t[5])                    # (k0 & 3) * 16
-            e("v_bfe_u32", t[6], k0, 2, 1)
-            e("v_lshl_add_u32", t[5], t[6], 3, t[5])             # + ((k0 >> 2) & 1) * 8      (k0 < 8)
-            e("v_mul_u32_u24", t[6], 2 * RS, px)
-            e("v_add_u32", t[5], t[5], t[6])
-            e("v_add_u32", t[5], c.BM * RS, t[5])
-            for j in range(c.NPB):
-                kk = KS * j
-                cst = 64 * (kk >> 3) + 16 * (kk & 3) + 8 * ((kk >> 2) & 1)
-                assert (kk & 3) == 0 or KS >= 8, "k0 and KS * j must not share bits"
-                e("v_add_u32", self.WB[j][2], cst, t[5])
-                e("v_add_u32", self.WB[j][0], c.STAGE, self.WB[j][2])
-                e("v_add_u32", self.WB[j][1], 2 * c.STAGE, self.WB[j][2])
-            e("v_mul_lo_u32", t[7], k0, st[5])
-            e("v_lshl_add_u32", self.vVB[0], px, 4, t[7])
-            e("s_mul_i32", st[4], st[5], KS)
-            for j in range(1, c.NPB):
-                e("v_add_u32", self.vVB[j], st[4], self.vVB[j - 1])
-            e("s_mul_i32", self.s_bstep, st[5], c.BK, comment="B advances BK rows per K-tile")
+        e("v_add_u32", t[5], c.BM * RS, t[5])
+        for j in range(c.NPB):
+            kk = KS * j
+            cst = 64 * (kk >> 3) + 16 * (kk & 3) + 8 * ((kk >> 2) & 1)
+            assert (kk & 3) == 0 or KS >= 8, "k0 and KS * j must not share bits"
+            e("v_add_u32", self.WB[j][2], cst, t[5])
+            e("v_add_u32", self.WB[j][0], c.STAGE, self.WB[j][2])
+            e("v_add_u32", self.WB[j][1], 2 * c.STAGE, self.WB[j][2])
+        e("v_mul_lo_u32", t[7], k0, st[5])
+        e("v_lshl_add_u32", self.vVB[0], px, 4, t[7])
+        e("s_mul_i32", st[4], st[5], KS)
+        for j in range(1, c.NPB):
+            e("v_add_u32", self.vVB[j], st[4], self.vVB[j - 1])
 
-    def kcontig_goff64(self, Voff, NP, ld_bytes):
-        """global offsets of a k-contiguous operand's pieces: (xr + 32 i) * ld * 8 + pc * 16, pc = tid % 8, xr = tid / 8 (per run: the K
-        tail of a run overwrites them with the out-of-bounds offset)"""
-        e, t, st = self.p.emit, self.vt, self.s_t
-        e("v_and_b32", t[0], 7, v(0))
-        e("v_lshrrev_b32", t[1], 3, v(0))
-        e("v_mul_lo_u32", t[7], t[1], ld_bytes)
-        e("v_lshl_add_u32", Voff[0], t[0], 4, t[7])
-        e("s_lshl_b32", st[4], ld_bytes, 5)                  # 32 rows
-        for i in range(1, NP):
-            e("v_add_u32", Voff[i], st[4], Voff[i - 1])
+    def c_row_step(self):
+        self.p.emit("s_lshl_b32", self.s_ldc20, self.s_ldc4, 2)
 
-    def ab_descriptors(self, again=False):
-        """srdA / srdB of the run k in [kb, kb + Keff) of tile (m0, n0).  Clobbers s_t[0], [2], [3], [5]."""
-        c, p = self.c, self.p
-        e = p.emit
-        st = self.s_t
-        Keff = self.s_Keff
-        e("s_lshl_b32", st[3], self.s_lda, 3, comment="lda * 8 bytes")
-        e("s_lshl_b32", st[5], self.s_ldb, 3, comment="ldb * 8 bytes")
-        A_, B_ = self.ka0.sub(0, 2), self.ka0.sub(2, 2)
-        # A panel: base = A + m0 * lda * 8 + kb * 8; bytes = (min(M - m0, BM) - 1) * lda * 8 + Keff * 8
-        e("s_mul_hi_u32", st[2], self.s_m0, st[3])
-        e("s_mul_i32", st[0], self.s_m0, st[3])
-        e("s_add_u32", self.srdA[0], A_[0], st[0])
-        e("s_addc_u32", self.srdA[1], A_[1], st[2])
-        if c.persistent:
-            e("s_lshl_b32", st[0], self.s_kb, 3)
-            e("s_add_u32", self.srdA[0], self.srdA[0], st[0])
-            e("s_addc_u32", self.srdA[1], self.srdA[1], 0)
-        e("s_and_b32", self.srdA[1], self.srdA[1], 0xffff)
-        e("s_sub_u32", st[0], self.s_M, self.s_m0)
-        e("s_min_u32", st[0], st[0], c.BM)
-        e("s_sub_u32", st[0], st[0], 1)
-        e("s_mul_i32", st[0], st[0], st[3])
-        e("s_lshl_b32", st[2], Keff, 3)
-        e("s_add_u32", self.srdA[2], st[0], st[2])
-        e("s_mov_b32", self.srdA[3], 0x00020000)
-        if c.b_kcontig:
-            # B^T panel: base = B + n0 * ldb * 8 + kb * 8; bytes = (min(N - n0, BN) - 1) * ldb * 8 + Keff * 8
-            e("s_mul_hi_u32", st[2], self.s_n0, st[5])
-            e("s_mul_i32", st[0], self.s_n0, st[5])
-            e("s_add_u32", self.srdB[0], B_[0], st[0])
-            e("s_addc_u32", self.srdB[1], B_[1], st[2])
-            if c.persistent:
-                e("s_lshl_b32", st[0], self.s_kb, 3)
-                e("s_add_u32", self.srdB[0], self.srdB[0], st[0])
-                e("s_addc_u32", self.srdB[1], self.srdB[1], 0)
-            e("s_and_b32", self.srdB[1], self.srdB[1], 0xffff)
-            e("s_sub_u32", st[0], self.s_N, self.s_n0)
-            e("s_min_u32", st[0], st[0], c.BN)
-            e("s_sub_u32", st[0], st[0], 1)
-            e("s_mul_i32", st[0], st[0], st[5])
-            e("s_lshl_b32", st[2], Keff, 3)
-            e("s_add_u32", self.srdB[2], st[0], st[2])
-        else:
-            # B panel: base = B + n0 * 8 + kb * ldb * 8; bytes = (Keff - 1) * ldb * 8 + (N - n0) * 8
-            e("s_lshl_b32", st[0], self.s_n0, 3)
-            e("s_add_u32", self.srdB[0], B_[0], st[0])
-            e("s_addc_u32", self.srdB[1], B_[1], 0)
-            if c.persistent:
-                e("s_mul_hi_u32", st[2], self.s_kb, st[5])
-                e("s_mul_i32", st[0], self.s_kb, st[5])
-                e("s_add_u32", self.srdB[0], self.srdB[0], st[0])
-                e("s_addc_u32", self.srdB[1], self.srdB[1], st[2])
-            e("s_and_b32", self.srdB[1], self.srdB[1], 0xffff)
-            e("s_sub_u32", st[0], Keff, 1)
-            e("s_mul_i32", st[0], st[0], st[5])
-            e("s_sub_u32", st[2], self.s_N, self.s_n0)
-            e("s_lshl_b32", st[2], st[2], 3)
-            e("s_add_u32", self.srdB[2], st[0], st[2])
-        e("s_mov_b32", self.srdB[3], 0x00020000)
-
-    def run_setup(self):
-        """one run = k in [kb, kb + Keff) of tile (m0, n0)"""
-        c, p = self.c, self.p
-        e = p.emit
-        t, st = self.vt, self.s_t
-        RS = c.RS
-        Keff = self.s_Keff
-        # K tail (Keff a multiple of 2): A pieces of the last K-tile beyond K read as 0
-        e("s_and_b32", self.s_ktail, Keff, c.BK - 1)
-        e("v_and_b32", t[5], 7, v(0))
-        e("v_lshlrev_b32", t[5], 1, t[5])
-        e("v_cmp_gt_u32", self.s_tm, self.s_ktail, t[5])
-        e("s_lshl_b32", st[3], self.s_lda, 3, comment="lda * 8 bytes")
-        self.kcontig_goff64(self.vVA, c.NPA, st[3])
-        e("s_lshl_b32", st[5], self.s_ldb, 3, comment="ldb * 8 bytes")
-        if c.b_kcontig:
-            self.kcontig_goff64(self.vVB, c.NPB, st[5])
-        e("s_nop", 4)
-        self.ab_descriptors()
-        self.c_descriptor()
-        e("s_add_u32", self.s_rem, Keff, c.BK - 1)
-        e("s_lshr_b32", self.s_rem, self.s_rem, (c.BK).bit_length() - 1)
-        # ---- tile 0 -> LDS stage 0, tile 1 -> staging registers ----
-        L_slow, L_join = p.label("fewtiles"), p.label("tiles01")
-        fast = not c.debug
-        if fast:
-            # three or more K-tiles: tiles 0 and 1 requested back to back (tile 0 through the idle fragment registers): a run starts
-            # after one memory latency instead of two (f32_kernel.py run_setup)
-            state = (list(self.vmq), list(self.lgq))
-            e("s_cmp_lt_u32", self.s_rem, 3)
-            e("s_cbranch_scc1", L_slow)
-            pool = [r for slot in range(2) for r in (self.fa[slot] + self.fb[slot])]
-            assert len(pool) >= c.NPA + c.NPB
-            real = (self.stA, self.stB)
-            tmp = (pool[:c.NPA], pool[c.NPA:c.NPA + c.NPB])
-            self.stA, self.stB = tmp
-            self.issue_loads_all()
-            self.advance_srds()
-            self.stA, self.stB = real
-            self.issue_loads_all()
-            self.advance_srds()
-            self.stA, self.stB = tmp
-            for pi in range(c.NPA):
-                self.store_A_piece(pi, k=2)
-            for pj in range(c.NPB):
-                self.store_B_piece(pj, k=2)
-            self.stA, self.stB = real
-            e("s_branch", L_join)
-            fast_state = (list(self.vmq), list(self.lgq))
-            self.vmq, self.lgq = state
-            p.place(L_slow)
-        self.tail_mask_if(self.s_rem, 1)
-        self.issue_loads_all()
-        self.advance_srds()
-        if c.debug:
-            e("s_waitcnt", vmcnt=0)
-            self.vmq.clear()
-            for k_ in range(4):
-                self.dump(f"stA0[{k_}]", self.stA[0][k_])
-            for k_ in range(4):
-                self.dump(f"stB0[{k_}]", self.stB[0][k_])
-        for pi in range(c.NPA):
-            self.store_A_piece(pi, k=2)
-        for pj in range(c.NPB):
-            self.store_B_piece(pj, k=2)
-        if c.debug:
-            self.lg_wait(None)
-            e("s_barrier")
-            for k_ in range(0, 4):
-                self.dump_lds(f"lds[{k_ * 1024}+4tid]", k_ * 1024)
-            self.dump_lds("ldsB[0+4tid]", c.BM * RS)
-            e("s_barrier")
-        self.tail_mask_if(self.s_rem, 2)
-        self.issue_loads_all()
-        self.advance_srds()
-        if fast:
-            assert (self.vmq, self.lgq) == fast_state, "the two prologue paths must leave the same loads and stores in flight"
-            p.place(L_join)
-        self.tail_mask_if(self.s_rem, 3)
-        self.init_accumulators()
-        self.lg_wait(None)
-        e("s_barrier")
-        self.read_group(0, 0, 0)
-        if c.debug:
-            self.lg_wait(None)
-            for k_ in range(4):
-                self.dump(f"fa[0][0][{k_}]", self.fa[0][0][k_])
-            for k_ in range(4):
-                self.dump(f"fb[0][0][{k_}]", self.fb[0][0][k_])
-            for _ in range(c.TM + c.TN):
-                self.lg_issue(("R", 0))
-
-    def c_descriptor(self):
-        """srdC = the whole matrix: bytes = (M - 1) * ldc * 8 + N * 8"""
-        e, st = self.p.emit, self.s_t
-        C_ = self.ka0.sub(4, 2)
-        e("s_lshl_b32", self.s_ldc4, self.s_ldc, 3)
-        e("s_mov_b32", self.srdC[0], C_[0])
-        e("s_and_b32", self.srdC[1], C_[1], 0xffff)
-        e("s_sub_u32", st[0], self.s_M, 1)
-        e("s_mul_i32", st[0], st[0], self.s_ldc4)
-        e("s_lshl_b32", st[2], self.s_N, 3)
-        e("s_add_u32", self.srdC[2], st[0], st[2])
-        e("s_mov_b32", self.srdC[3], 0x00020000)
-        e("s_lshl_b32", self.s_ldc20, self.s_ldc4, 2)
-
-    def issue_loads_all(self):
-        for pi in range(self.c.NPA):
-            self.load_A_piece(pi)
-        for pj in range(self.c.NPB):
-            self.load_B_piece(pj)
-
-    def advance_srds(self, which=None):
-        e = self.p.emit
-        ops = []
-        for srd, step in ((self.srdA, self.c.BK * 8), (self.srdB, self.c.BK * 8 if self.c.b_kcontig else self.s_bstep)):
-            ops += [("s_add_u32", srd[0], srd[0], step), ("s_addc_u32", srd[1], srd[1], 0),
-                    ("s_sub_u32", srd[2], srd[2], step), ("s_cselect_b32", srd[2], 0, srd[2])]
-        if which is None:
-            for o in ops:
-                e(*o)
-        return ops
-
-    def mask_last_pieces_if(self, sreg, value):
-        pass      # (K is even: the 16-byte pieces of 2 doubles are all-or-nothing)
-
-    def apply_tail_mask(self):
-        for r in list(self.vVA) + (list(self.vVB) if self.c.b_kcontig else []):
-            self.p.emit("v_cndmask_b32", r, self.v_oob, r, self.s_tm)
+    def b_step(self):
+        return self.c.BK * 8 if self.c.b_kcontig else self.s_bstep      # (B passed transposed: a literal)
 
     # ------------------------------------------------------------------ LDS stores: one ds_write2_b64 per piece
     def store_A_piece(self, pi, ops=None, k=0):
@@ -436,91 +142,32 @@ class Gen64(Gen):
             self.run_ops(out)
         return out
 
-    def staging_ops(self, wr_k):
-        c, stg = self.c, []
-        for pi in range(c.NPA):
-            stg += self.store_A_piece(pi, ops=[], k=wr_k)
-            stg.append(("loadA", pi))
-        for pj in range(c.NPB):
-            stg += self.store_B_piece(pj, ops=[], k=wr_k)
-            stg.append(("loadB", pj))
-        return stg
-
     # ------------------------------------------------------------------ matrix instruction, slice fold
     def emit_mfma(self, b, slot, i, n, u, srcc):
         self.p.emit("v_mfma_f64_16x16x4_f64", self.acc[b], self.fa[slot][i].sub(2 * u, 2), self.fb[slot][n].sub(2 * u, 2), srcc)
 
-    def fold_before(self, b):
+    def alpha_mul(self):
         T = self.vT[0]
-        for r in range(8):
-            self.p.emit("v_accvgpr_read_b32", T[r], self.acc[b][r])
+        return [("v_mul_f64", T.sub(2 * d, 2), self.s_al, T.sub(2 * d, 2)) for d in range(4)]
 
-    def fold_after(self, b):
-        p, e, T = self.p, self.p.emit, self.vT[0]
-        # run += alpha * slice, unfused; alpha == 1: the multiplies (out of line) are a branch not taken
-        lmul, lback = p.label("amul"), p.label("aback")
-        e("s_cmp_lg_u32", self.s_a1, 0)
-        e("s_cbranch_scc1", lmul)
-        p.place(lback)
-        self.outlined.append((lmul, [("v_mul_f64", T.sub(2 * d, 2), self.s_al, T.sub(2 * d, 2)) for d in range(4)], lback))
-        if self.c.runv:
-            for d in range(4):
-                e("v_add_f64", self.run[b].sub(2 * d, 2), self.run[b].sub(2 * d, 2), T.sub(2 * d, 2))
-            return
+    def cmp_alpha_one(self):
+        self.p.emit("s_cmp_lg_u32", self.s_a1, 0)
+
+    def agpr_add(self, dst):
+        e, T = self.p.emit, self.vT[0]
         for d in range(4):
             tt = T.sub(8 + 2 * (d % 2), 2)
-            e("v_accvgpr_read_b32", tt[0], self.run[b][2 * d])
-            e("v_accvgpr_read_b32", tt[1], self.run[b][2 * d + 1])
+            e("v_accvgpr_read_b32", tt[0], dst[2 * d])
+            e("v_accvgpr_read_b32", tt[1], dst[2 * d + 1])
             e("v_add_f64", tt, tt, T.sub(2 * d, 2))
-            e("v_accvgpr_write_b32", self.run[b][2 * d], tt[0])
-            e("v_accvgpr_write_b32", self.run[b][2 * d + 1], tt[1])
+            e("v_accvgpr_write_b32", dst[2 * d], tt[0])
+            e("v_accvgpr_write_b32", dst[2 * d + 1], tt[1])
 
-    def init_accumulators(self):
+    def run_add(self, b):
         if not self.c.runv:
-            return Gen.init_accumulators(self)
-        from .f32_kernel import MODE_NORMAL
-        c, p = self.c, self.p
-        e = p.emit
-        for b in range(c.NB):
-            for r in range(c.ACCR):
-                e("v_accvgpr_write_b32", self.acc[b][r], 0)
-        keep = p.label("keeprun")
-        if c.persistent:
-            e("s_cmp_lg_u32", self.s_mode, MODE_NORMAL)
-            e("s_cbranch_scc1", keep)
-        for b in range(c.NB):
-            for d in range(4):
-                e("v_mov_b64", self.run[b].sub(2 * d, 2), 0)
-        self.load_beta_c()
-        p.place(keep)
-
-    def fold_block(self, b):
-        e, T = self.p.emit, self.vT[0]
-        for r in range(8):
-            e("v_accvgpr_read_b32", T[r], self.acc[b][r])
+            return self.agpr_add(self.run[b])
         for d in range(4):
-            e("v_mul_f64", T.sub(2 * d, 2), self.s_al, T.sub(2 * d, 2))      # (1.0 * x is x)
-        if self.c.runv:
-            for d in range(4):
-                e("v_add_f64", self.run[b].sub(2 * d, 2), self.run[b].sub(2 * d, 2), T.sub(2 * d, 2))
-            return
-        for d in range(4):
-            tt = T.sub(8 + 2 * (d % 2), 2)
-            e("v_accvgpr_read_b32", tt[0], self.run[b][2 * d])
-            e("v_accvgpr_read_b32", tt[1], self.run[b][2 * d + 1])
-            e("v_add_f64", tt, tt, T.sub(2 * d, 2))
-            e("v_accvgpr_write_b32", self.run[b][2 * d], tt[0])
-            e("v_accvgpr_write_b32", self.run[b][2 * d + 1], tt[1])
-
-    def acc_add_block(self, b):
-        e, T = self.p.emit, self.vT[0]
-        for d in range(4):
-            tt = T.sub(8 + 2 * (d % 2), 2)
-            e("v_accvgpr_read_b32", tt[0], self.acc[b][2 * d])
-            e("v_accvgpr_read_b32", tt[1], self.acc[b][2 * d + 1])
-            e("v_add_f64", tt, tt, T.sub(2 * d, 2))
-            e("v_accvgpr_write_b32", self.acc[b][2 * d], tt[0])
-            e("v_accvgpr_write_b32", self.acc[b][2 * d + 1], tt[1])
+            self.p.emit("v_add_f64", self.run[b].sub(2 * d, 2), self.run[b].sub(2 * d, 2), self.vT[0].sub(2 * d, 2))
 
     # ------------------------------------------------------------------ pipelined tile transitions (f32_kernel.py Cfg.pipe)
     def trans_after(self, b):
@@ -531,11 +178,7 @@ class Gen64(Gen):
         c, p, e, T, st = self.c, self.p, self.p.emit, self.vT[0], self.s_t
         i, n = b // c.TN, b % c.TN
         assert c.runv or not c.exact
-        lmul, lback = p.label("tmul"), p.label("tback")
-        e("s_cmp_lg_u32", self.s_a1, 0)
-        e("s_cbranch_scc1", lmul)
-        p.place(lback)
-        self.outlined.append((lmul, [("v_mul_f64", T.sub(2 * d, 2), self.s_al, T.sub(2 * d, 2)) for d in range(4)], lback))
+        self.alpha_mul_outlined("t")
         soff = st[0]
         for d in range(4):
             if c.exact:
@@ -554,45 +197,25 @@ class Gen64(Gen):
     def pipe_c_addr(self):
         """(vC, srdCd) for the deferred stores of the tile (m0, n0): srdCd starts at this wave's first row, vC[n] = the lane's offset
         from there (q rows down, block column n; out of bounds beyond N)"""
-        c, e, t, st = self.c, self.p.emit, self.vt, self.s_t
-        lane, r16, q = t[0], t[1], t[2]
-        e("v_and_b32", lane, 63, v(0))
-        e("v_and_b32", r16, 15, lane)
-        e("v_lshrrev_b32", q, 4, lane)
-        e("s_add_u32", st[0], self.s_m0, self.s_wm0)
-        e("s_mul_hi_u32", st[2], st[0], self.s_ldc4)
-        e("s_mul_i32", st[3], st[0], self.s_ldc4)
-        e("s_add_u32", self.srdCd[0], self.srdC[0], st[3])
-        e("s_addc_u32", self.srdCd[1], self.srdC[1], st[2])
-        e("s_and_b32", self.srdCd[1], self.srdCd[1], 0xffff)
-        e("s_mov_b32", self.srdCd[3], 0x00020000)
-        e("s_sub_u32", self.srdCd[2], self.srdC[2], st[3])              # what is left of C from there (0: the wave's rows lie beyond M)
-        e("s_cselect_b32", self.srdCd[2], 0, self.srdCd[2])
-        e("s_cmp_lg_u32", st[2], 0)
-        e("s_cselect_b32", self.srdCd[2], 0, self.srdCd[2])
-        e("v_mul_lo_u32", t[3], q, self.s_ldc4)
-        e("s_add_u32", st[1], self.s_n0, self.s_wn0)
-        e("v_add_u32", t[4], st[1], r16)
-        e("v_lshl_add_u32", t[3], t[4], 3, t[3])
-        for n in range(c.TN):
-            e("v_add_u32", t[5], 16 * n, t[4])
-            e("v_cmp_gt_u32", VCC, self.s_N, t[5])
-            e("v_add_u32", t[6], 128 * n, t[3])
-            e("v_mov_b32", t[7], 0x80000000)
-            e("v_cndmask_b32", self.vC[n], t[7], t[6], VCC)
+        r16, q = self.lane_rq()
+        self.srdCd_setup()
+        self.p.emit("v_mul_lo_u32", self.vt[3], q, self.s_ldc4)
+        self.c_columns(r16)
 
     # ------------------------------------------------------------------ epilogue
     def c_addr_setup(self):
         """vC[n] = byte offset in C of D[q][r16] of block column n: row m0 + wm0 + q (+ 4 per accumulator element, + 16 per
         block row), col n0 + wn0 + r16 + 16n"""
-        c, e, t, st = self.c, self.p.emit, self.vt, self.s_t
-        lane, r16, q = t[0], t[1], t[2]
-        e("v_and_b32", lane, 63, v(0))
-        e("v_and_b32", r16, 15, lane)
-        e("v_lshrrev_b32", q, 4, lane)
+        e, t, st = self.p.emit, self.vt, self.s_t
+        r16, q = self.lane_rq()
         e("s_add_u32", st[0], self.s_m0, self.s_wm0)
         e("v_add_u32", t[3], st[0], q)
         e("v_mul_lo_u32", t[3], t[3], self.s_ldc4)
+        self.c_columns(r16)
+
+    def c_columns(self, r16):
+        """vC[n] = vt[3] (the row's bytes) + the bytes of column n0 + wn0 + r16 + 16 n; out of bounds beyond N"""
+        c, e, t, st = self.c, self.p.emit, self.vt, self.s_t
         e("s_add_u32", st[1], self.s_n0, self.s_wn0)
         e("v_add_u32", t[4], st[1], r16)
         e("v_lshl_add_u32", t[3], t[4], 3, t[3])
@@ -651,9 +274,6 @@ class Gen64(Gen):
         e("s_waitcnt", vmcnt=0, lgkmcnt=0)
         self.vmq.clear()
         self.lgq.clear()
-        if c.debug:
-            for k_ in range(4):
-                self.dump(f"acc[0][{k_}]", self.acc[0][k_])
         self.mode_dispatch()
         self.c_addr_setup()
         T = self.vT[0]
@@ -714,16 +334,4 @@ def make(name, **over):
 
 
 if __name__ == "__main__":
-    import argparse
-    import os
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", required=True)
-    args = ap.parse_args()
-    os.makedirs(args.out, exist_ok=True)
-    for name in CONFIGS:
-        g = make(name)
-        g.build()
-        sym = "lh_f64_" + name
-        with open(os.path.join(args.out, sym + ".s"), "w") as f:
-            f.write(kernel_text(g, sym))
-        print(sym, len(g.p.ins), "instructions")
+    write_kernels("lh_f64_", CONFIGS, make)

@@ -22,7 +22,7 @@ int64 (`make("i64_64x64x32")`): eight planes, 36 products, eight accumulator gro
 block and the workgroup tile is 64x64 (blocks of [8 planes][2 halves][64 rows][16 bytes] = the same 16 KiB); the epilogue sums
 sext(G_s) << 8s in 64-bit (add-with-carry for s <= 3, shifted adds into the high word above), then alpha * (...) + beta * C0 wrapping."""
 from .core import v, a, s, VCC, M0
-from .f32_kernel import Gen, Cfg, kernel_text, KA_A, KA_LDA, KA_DBG, KA_SCHED, KA_SCHED2  # noqa: F401
+from .f32_kernel import Gen, Cfg, kernel_text, write_kernels, KA_A, KA_LDA, KA_DBG, KA_SCHED, KA_SCHED2  # noqa: F401
 
 KA_ALPHA64 = 72   # int64 alpha, beta (16 bytes): the slot of the f64 kernels' doubles
 
@@ -476,16 +476,4 @@ def make(name="i32_128x128x32", **over):
 CONFIGS = {"i32_128x128x32": {}, "i64_64x64x32": {}}
 
 if __name__ == "__main__":
-    import argparse
-    import os
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", required=True)
-    args = ap.parse_args()
-    os.makedirs(args.out, exist_ok=True)
-    for name in CONFIGS:
-        g = make(name)
-        g.build()
-        sym = "lh_" + name
-        with open(os.path.join(args.out, sym + ".s"), "w") as f:
-            f.write(kernel_text(g, sym))
-        print(sym, len(g.p.ins), "instructions")
+    write_kernels("lh_", CONFIGS, make)
