@@ -60,6 +60,7 @@ class Cfg:
         # the launcher cuts tiles along K at slice boundaries -- head slices stored to a workspace / tail runs that fold them in
         # order.  The convolution kernels (out of SGPRs, never split) run exactly one tile per workgroup.
         self.persistent = (not conv and not debug) if persistent is None else persistent
+        self.loops = self.persistent or cpers       # the workgroup goes back for its next run (L_run; the end is L_exit)
         # pipe (round 6): tile transitions of a persistent workgroup are software-pipelined.  When the run that follows a whole tile is
         # another whole tile, the K loop never stops: the last two tile bodies of tile T already fetch the first two K-tiles of tile
         # T + 1 (today they fetch zeros past K), and the first body of tile T + 1 is a TRANSITION body -- a fold tile whose fold also
@@ -203,10 +204,6 @@ def magic_u32(d):
     return 0 if d == 1 else ((1 << 32) // d + 1) & 0xffffffff
 
 
-def c_runv(gen):
-    return getattr(gen.c, "runv", False)
-
-
 class Gen:
     def __init__(self, cfg):
         self.c = cfg
@@ -222,7 +219,7 @@ class Gen:
         self.sA, self.sB, self.sC, self.sTAB = None, None, None, None
         self.alloc_args()
         self.s_ldc4, self.s_ldc20 = S(), S()
-        self.s_csC4 = None if c.conv else S()      # column stride of C in bytes (KA_EPI + 12; 0 in the arguments = dense)
+        self.s_csC4 = S() if self.C_STRIDED else None     # column stride of C in bytes (KA_EPI + 12; 0 in the arguments = dense)
         self.s_preA, self.s_preB = (S(2, align=2), S(2, align=2)) if c.pre else (None, None)   # lane masks: all ones = apply relu
         self.alloc_sched()
         # accumulators
@@ -235,7 +232,7 @@ class Gen:
         self.fb = [[D4(4) for _ in range(c.TN)] for _ in range(2)]
         # staging pieces
         self.stA = [D4(4) for _ in range(c.NPA)]
-        self.stB = [D4(2) for _ in range(c.NPB)] if c.conv else [D4(4) for _ in range(c.NPB)]
+        self.stB = [D4(self.STB_REGS) for _ in range(c.NPB)]
         # deep: tile t waits in set t & 1 (the loop body that multiplies tile t stores tile t + 1 from its set and requests tile t + 3 into it)
         self.st_sets = [(self.stA, self.stB)]
         if c.deep:
@@ -245,45 +242,18 @@ class Gen:
         # v_swap is free beside the MFMA stream while any other VALU op costs ~11 cycles of matrix-pipe time
         # (profiles/r03/asm_probe_v3_fillers.jsonl, asm_probe_v4_fillers.jsonl), so the loop computes no address at all
         # (il: one register + the stage as an immediate offset: an entry is (register, bytes); see lds_at)
-        def triple(read):
-            if not c.il:
-                return [V() for _ in range(3)]
-            r = V()
-            return [(r, 0), (r, c.RS), (r, 2 * c.RS)] if read else [(r, c.RS), (r, 2 * c.RS), (r, 0)]
-        self.RA = [triple(True) for _ in range(c.NG)]
-        self.RB = [triple(True) for _ in range(c.NG)]
-        self.WA = [[triple(False) for _ in range(c.NPA)] for _ in range(2)]   # [MFMA half][piece][stage]
-        if c.conv:
-            self.WB = [[triple(False) for _ in range(2)] for _ in range(4)]       # [pair][pixel of the piece][stage]
-            self.vB0 = [V() for _ in range(8)]             # per piece: buffer offset of the lane's first / second pixel for the
-            self.vB1 = [V() for _ in range(8)]             # piece's tap (read from the LDS table; 0x80000000 = padding)
-            scr = S(16, align=4)
-            self.s_scr = scr
-            self.s_koff = [scr[i] for i in range(8)]       # per piece: (c*H*W + kh*W + kw) * 4 of the k it gathers
-            self.s_k0 = S()                                # this wave's first k (= c * taps + kh * kW + kw) in the tile being loaded
-            self.s_NT, self.s_kW, self.s_M10 = S(), S(), S()   # taps kH * kW; kW; ceil(1024 / kW): r / kW = (r * M10) >> 10 for r < 49
-            self.s_pok = [S(2), S(2)]                      # prologue: lanes whose first / second output pixel exists (ragged last tile)
-            self.s_m = S(2)
-            self.s_HW4, self.s_W4, self.s_Cin = S(), S(), S()
-            self.s_sc = scr.sub(0, 8)                      # (the scheduler constants are dead before conv_setup loads the geometry)
-        elif c.b_kcontig:
-            self.WB = [[triple(False) for _ in range(c.NPB)] for _ in range(2)]   # like A: [MFMA half][piece][stage]
-        else:
-            self.WB = [[triple(False) for _ in range(4)] for _ in range(c.NPB // 2)]   # [pair][element][stage]
+        self.RA = [self.triple(True) for _ in range(c.NG)]
+        self.RB = [self.triple(True) for _ in range(c.NG)]
+        self.WA = [[self.triple(False) for _ in range(c.NPA)] for _ in range(2)]   # [MFMA half][piece][stage]
+        self.alloc_WB()
         self.v_oob = V()            # 0x80000000: a buffer offset the bounds check always rejects (reads as 0)
         self.s_tm = S(2)            # lanes whose 16-byte piece of a k-contiguous operand is real data in the LAST K-tile
         self.s_ktail = S()
         self.s_em = [S(2) for _ in range(4)]   # K % 4 != 0: lanes whose element j of their piece is real data in the last K-tile
-        if c.conv:     # (the convolution kernels are out of SGPRs: the tap state is dead by the epilogue)
-            self.srdBias, self.s_epi = self.s_scr.sub(0, 4), self.s_scr.sub(4, 4)
-        else:
-            self.srdBias = S(4)                                      # fused epilogue: the bias view (base, -, bytes, flags)
-            self.s_epi = S(4, align=4)                               # rowStrideBias, colStrideBias (elements), activation, -
-            # batch strides in bytes (grid y = batch index): read and consumed in once(), long before the fused epilogue loads its fields
-            self.s_bsA, self.s_bsBC = self.srdBias.sub(0, 2), self.s_epi
+        self.alloc_epi()
         self.alloc_pipe()
         self.vVA = [V() for _ in range(c.NPA)]
-        self.vVB = [V() for _ in range(c.NPB)] if not c.conv else []
+        self.vVB = [V() for _ in range(c.NPB)] if self.HAS_VVB else []
         self.vC = [V() for _ in range(c.TN)]
         if c.debug:
             self.srdD = S(4)
@@ -296,6 +266,31 @@ class Gen:
         self.vt = [blk[i] for i in range(10)]
         # filler experiments (timing only): dummy data / address registers that alias temporaries the loop does not use
         self.vF, self.vFaddr, self.vFoff = blk.sub(4, 4), blk[10], blk[11]
+
+    # B's registers are the family's (conv_kernel.ConvGen: gathered pixel pairs, the tap state), asked for where alloc fixes their numbers:
+    # registers of a staged piece, per-lane global offsets vVB or none, a column stride of C or none; alloc_WB, alloc_epi
+    STB_REGS, HAS_VVB, C_STRIDED = 4, True, True
+
+    def triple(self, read):
+        c, V = self.c, self.p.valloc
+        if not c.il:
+            return [V() for _ in range(3)]
+        r = V()
+        return [(r, 0), (r, c.RS), (r, 2 * c.RS)] if read else [(r, c.RS), (r, 2 * c.RS), (r, 0)]
+
+    def alloc_WB(self):
+        c = self.c
+        if c.b_kcontig:
+            self.WB = [[self.triple(False) for _ in range(c.NPB)] for _ in range(2)]   # like A: [MFMA half][piece][stage]
+        else:
+            self.WB = [[self.triple(False) for _ in range(4)] for _ in range(c.NPB // 2)]   # [pair][element][stage]
+
+    def alloc_epi(self):
+        S = self.p.salloc
+        self.srdBias = S(4)                                      # fused epilogue: the bias view (base, -, bytes, flags)
+        self.s_epi = S(4, align=4)                               # rowStrideBias, colStrideBias (elements), activation, -
+        # batch strides in bytes (grid y = batch index): read and consumed in once(), long before the fused epilogue loads its fields
+        self.s_bsA, self.s_bsBC = self.srdBias.sub(0, 2), self.s_epi
 
     def alloc_args(self):
         """the kernel arguments every family reads, the three descriptors, the tile's coordinates, scalar temporaries"""
@@ -323,7 +318,6 @@ class Gen:
         is sent on to the next workgroup), its whole tiles, and last the END piece [p0, P) of tile t0, which continues the running sum
         received from the previous workgroup -- by then long since sent (sched_next)."""
         c, S = self.c, self.p.salloc
-        self.s_sc = None
         if c.persistent:
             self.s_sc = S(8, align=4)                      # scheduler constants, (re)loaded where they are used
             self.s_vid, self.s_t0, self.s_p0, self.s_t1, self.s_pe, self.s_tcur, self.s_phase = (S() for _ in range(7))
@@ -332,10 +326,7 @@ class Gen:
         else:
             self.s_Keff = self.s_K
             self.s_tile = None
-            if not c.conv:
-                self.s_sc = S(8, align=4)
-            if c.cpers:
-                self.s_tcur, self.s_img = S(), S()         # the next unit of this workgroup; the image of the tile being loaded
+            self.s_sc = S(8, align=4)
 
     # ------------------------------------------------------------------ queue models -> counted waits
     def vm_issue(self, tag):
@@ -686,27 +677,29 @@ class Gen:
             tile = st[4]
             e("s_load_dwordx8", self.s_sc, s(0, 2), KA_SCHED)
             e("s_waitcnt", lgkmcnt=0)
-        elif c.cpers:
-            e("s_mov_b32", self.s_tcur, s(2))
-            p.place(self.L_run)
-            e("s_barrier", comment="every wave is done with the previous unit's LDS tiles and tap table")
-            self.next_unit(self.L_exit)
-            self.run_setup()
-            return
         else:
-            e("s_load_dwordx8", self.s_sc, s(0, 2), KA_SCHED)
-            e("s_load_dword", st[5], s(0, 2), KA_SCHED2)
-            e("s_waitcnt", lgkmcnt=0)
-            self.xcd_remap(st[4], s(2), self.s_sc[7], st[5], st[0])
-            if not c.conv:
-                e("s_add_u32", st[4], st[4], self.ka0[6])       # (the launch's first tile, see above)
-            tile = st[4]
+            tile = self.wg_tile()
+            e("s_add_u32", tile, tile, self.ka0[6])       # (the launch's first tile, see above)
+        self.tile_origin(tile)
+        self.run_setup()
+
+    def wg_tile(self):
+        """one tile per workgroup: the workgroup's tile (XCD remap of its id) in s_t[4], the KA_SCHED block in s_sc"""
+        e, st = self.p.emit, self.s_t
+        e("s_load_dwordx8", self.s_sc, s(0, 2), KA_SCHED)
+        e("s_load_dword", st[5], s(0, 2), KA_SCHED2)
+        e("s_waitcnt", lgkmcnt=0)
+        self.xcd_remap(st[4], s(2), self.s_sc[7], st[5], st[0])
+        return st[4]
+
+    def tile_origin(self, tile):
+        """s_m0, s_n0 of `tile` (s_sc holds the KA_SCHED block).  Clobbers s_t[0..3], s_t[5]."""
+        c, e, st = self.c, self.p.emit, self.s_t
         self.tile_coords(tile, self.s_sc, st[0], st[1], (st[2], st[3], st[5]))
         self.dump("pid_m", st[0])
         self.dump("pid_n", st[1])
         e("s_mul_i32", self.s_m0, st[0], c.BM)
         e("s_mul_i32", self.s_n0, st[1], c.BN)
-        self.run_setup()
 
     def once(self):
         c, p = self.c, self.p
@@ -717,8 +710,7 @@ class Gen:
                f"{'laser-order (kc = 512 slices)' if c.exact else 'one accumulation chain'}")
         e("s_load_dwordx8", self.ka0, s(0, 2), KA_A)
         e("s_load_dwordx8", self.ka1, s(0, 2), KA_LDA)
-        if not c.conv:
-            self.batch_offsets(KA_BSA)
+        self.batch_offsets(KA_BSA)
         e("s_waitcnt", lgkmcnt=0)
         if c.pipe:
             self.pipe_eligible()
@@ -812,55 +804,60 @@ class Gen:
         if c.b_kcontig:
             kcontig_lds(self.WB, c.NPB, c.ROWP * c.BM)
             e("s_mov_b32", self.s_bstep, c.BK * 4, comment="B (stored transposed) advances BK elements along its rows per K-tile")
-        if not c.b_kcontig and not c.conv:
-            # B pieces (x-contiguous, 16 B = 4 consecutive x of row k), handled in pairs (k, k+2) -- DESIGN.md 3.2 pair mode
-            aa, pp, hh, c0, xq, kb0 = t[0], t[1], t[2], t[3], t[4], t[6]
-            BX16 = c.BN // 16
-            KG = 8 * 16 // BX16
-            e("v_and_b32", aa, 3, tid)
-            e("v_bfe_u32", pp, tid, 2, 1)
-            e("v_bfe_u32", hh, tid, 3, 1)
-            e("v_lshrrev_b32", c0, 4, tid)
-            e("v_and_b32", t[5], BX16 - 1, c0)
-            e("v_lshl_add_u32", xq, t[5], 2, aa)                 # xq = (c0 % BX16) * 4 + a
-            e("v_lshrrev_b32", t[5], BX16.bit_length() - 1, c0)  # c0 / BX16
-            e("v_lshlrev_b32", t[5], 3, t[5])
-            e("v_lshl_add_u32", kb0, hh, 2, t[5])
-            e("v_add_u32", kb0, kb0, pp)                         # kb0 = 8 * (c0 / BX16) + 4h + p
-            e("v_mul_lo_u32", t[7], kb0, st[5])
-            e("v_lshl_add_u32", self.vVB[0], xq, 4, t[7])        # VB(gi = 0, j = 0)
-            e("s_lshl_b32", st[4], st[5], 1)                     # 2 * ldb * 4
-            e("s_mul_i32", st[3], st[5], KG)                     # KG * ldb * 4
-            for gi in range(c.NPB // 2):
-                if gi:
-                    e("v_add_u32", self.vVB[2 * gi], st[3], self.vVB[2 * gi - 2])
-                e("v_add_u32", self.vVB[2 * gi + 1], st[4], self.vVB[2 * gi])
-            e("s_mul_i32", self.s_bstep, st[5], c.BK, comment="B advances BK rows per K-tile")
-            # LDS write addresses of the B pairs: for element e of the pieces: x = 4xq + e, row = 4xq + (e ^ (xq & 1)),
-            #   L = 2 * (k / 8) + (k & 1), word = (k % 8) >> 1;  WB = BK*BM*4 + row*BK*4 + 16 * (L ^ kq_swz(x)) + 4 * word
-            e("s_mov_b32", st[0], c.ROWP * c.BM, comment="the B panel follows the A panel in a stage")
-            for gi in range(c.NPB // 2):
-                kk = t[7]
-                e("v_add_u32", kk, gi * KG, kb0)
-                e("v_lshrrev_b32", t[8], 3, kk)
-                e("v_lshlrev_b32", t[8], 1, t[8])
-                e("v_and_b32", t[9], 1, kk)
-                e("v_or_b32", t[8], t[8], t[9])                  # L
-                e("v_bfe_u32", t[9], kk, 1, 2)                   # word = (k & 7) >> 1  (k % 8 in {0,1,4,5} -> 0 or 2)
-                e("v_lshlrev_b32", t[9], 2, t[9])                # 4 * word
-                for ee in range(4):
-                    xx, rr, ss = t[0], t[1], t[2]  # aa / pp / hh are dead from here on
-                    e("v_lshl_add_u32", xx, xq, 2, ee)           # x = 4xq + e
-                    self.kq_row(rr, xx, t[5])
-                    self.kq_swz(ss, xx, t[5])
-                    e("v_xor_b32", ss, ss, t[8])                 # L ^ swz
-                    e("v_mul_u32_u24", rr, c.ROWP, rr)
-                    e("v_lshl_add_u32", rr, ss, 4, rr)
-                    e("v_add3_u32", self.lds_at(self.WB[gi][ee][2])[0], rr, t[9], st[0])
-                    if c.il:
-                        continue
-                    e("v_add_u32", self.WB[gi][ee][0], c.STAGE, self.WB[gi][ee][2])
-                    e("v_add_u32", self.WB[gi][ee][1], 2 * c.STAGE, self.WB[gi][ee][2])
+        else:
+            self.xpieces_B()
+
+    def xpieces_B(self):
+        """once(), B row-major: the global offsets and LDS write addresses of its pieces, its step per K-tile (s_t[5] = ldb * 4)"""
+        c, e, t, st, tid = self.c, self.p.emit, self.vt, self.s_t, v(0)
+        # B pieces (x-contiguous, 16 B = 4 consecutive x of row k), handled in pairs (k, k+2) -- DESIGN.md 3.2 pair mode
+        aa, pp, hh, c0, xq, kb0 = t[0], t[1], t[2], t[3], t[4], t[6]
+        BX16 = c.BN // 16
+        KG = 8 * 16 // BX16
+        e("v_and_b32", aa, 3, tid)
+        e("v_bfe_u32", pp, tid, 2, 1)
+        e("v_bfe_u32", hh, tid, 3, 1)
+        e("v_lshrrev_b32", c0, 4, tid)
+        e("v_and_b32", t[5], BX16 - 1, c0)
+        e("v_lshl_add_u32", xq, t[5], 2, aa)                 # xq = (c0 % BX16) * 4 + a
+        e("v_lshrrev_b32", t[5], BX16.bit_length() - 1, c0)  # c0 / BX16
+        e("v_lshlrev_b32", t[5], 3, t[5])
+        e("v_lshl_add_u32", kb0, hh, 2, t[5])
+        e("v_add_u32", kb0, kb0, pp)                         # kb0 = 8 * (c0 / BX16) + 4h + p
+        e("v_mul_lo_u32", t[7], kb0, st[5])
+        e("v_lshl_add_u32", self.vVB[0], xq, 4, t[7])        # VB(gi = 0, j = 0)
+        e("s_lshl_b32", st[4], st[5], 1)                     # 2 * ldb * 4
+        e("s_mul_i32", st[3], st[5], KG)                     # KG * ldb * 4
+        for gi in range(c.NPB // 2):
+            if gi:
+                e("v_add_u32", self.vVB[2 * gi], st[3], self.vVB[2 * gi - 2])
+            e("v_add_u32", self.vVB[2 * gi + 1], st[4], self.vVB[2 * gi])
+        e("s_mul_i32", self.s_bstep, st[5], c.BK, comment="B advances BK rows per K-tile")
+        # LDS write addresses of the B pairs: for element e of the pieces: x = 4xq + e, row = 4xq + (e ^ (xq & 1)),
+        #   L = 2 * (k / 8) + (k & 1), word = (k % 8) >> 1;  WB = BK*BM*4 + row*BK*4 + 16 * (L ^ kq_swz(x)) + 4 * word
+        e("s_mov_b32", st[0], c.ROWP * c.BM, comment="the B panel follows the A panel in a stage")
+        for gi in range(c.NPB // 2):
+            kk = t[7]
+            e("v_add_u32", kk, gi * KG, kb0)
+            e("v_lshrrev_b32", t[8], 3, kk)
+            e("v_lshlrev_b32", t[8], 1, t[8])
+            e("v_and_b32", t[9], 1, kk)
+            e("v_or_b32", t[8], t[8], t[9])                  # L
+            e("v_bfe_u32", t[9], kk, 1, 2)                   # word = (k & 7) >> 1  (k % 8 in {0,1,4,5} -> 0 or 2)
+            e("v_lshlrev_b32", t[9], 2, t[9])                # 4 * word
+            for ee in range(4):
+                xx, rr, ss = t[0], t[1], t[2]  # aa / pp / hh are dead from here on
+                e("v_lshl_add_u32", xx, xq, 2, ee)           # x = 4xq + e
+                self.kq_row(rr, xx, t[5])
+                self.kq_swz(ss, xx, t[5])
+                e("v_xor_b32", ss, ss, t[8])                 # L ^ swz
+                e("v_mul_u32_u24", rr, c.ROWP, rr)
+                e("v_lshl_add_u32", rr, ss, 4, rr)
+                e("v_add3_u32", self.lds_at(self.WB[gi][ee][2])[0], rr, t[9], st[0])
+                if c.il:
+                    continue
+                e("v_add_u32", self.WB[gi][ee][0], c.STAGE, self.WB[gi][ee][2])
+                e("v_add_u32", self.WB[gi][ee][1], 2 * c.STAGE, self.WB[gi][ee][2])
 
     def batch_offsets(self, ka_bsa):
         """batched problems (gemm_strided_batched; the kc slices of the slice-parallel form): workgroup id y = batch index, operand b at
@@ -910,76 +907,60 @@ class Gen:
         for i in range(1, NP):
             e("v_add_u32", Voff[i], st[4], Voff[i - 1])
 
-    def ab_descriptors(self, again=False):
+    def ab_descriptors(self):
         """srdA / srdB of the run k in [kb, kb + Keff) of tile (m0, n0).  Clobbers s_t[0], [2], [3], [5]."""
-        c, p = self.c, self.p
-        e = p.emit
-        st = self.s_t
-        Keff = self.s_Keff
+        self.a_descriptor()
+        self.b_descriptor()
+
+    def a_descriptor(self):
+        """srdA; leaves ldb in bytes in s_t[5] for b_descriptor"""
+        c, e, st = self.c, self.p.emit, self.s_t
         sh = c.ESZ.bit_length() - 1      # bytes of an element = 1 << sh (the comments below say 4)
         e("s_lshl_b32", st[3], self.s_lda, sh, comment=f"lda * {c.ESZ} bytes")
         e("s_lshl_b32", st[5], self.s_ldb, sh, comment=f"ldb * {c.ESZ} bytes")
-        A_, B_, C_ = self.ka0.sub(0, 2), self.ka0.sub(2, 2), self.ka0.sub(4, 2)
-        # A panel: base = A + m0 * lda * 4 + kb * 4; bytes = (min(M - m0, BM) - 1) * lda * 4 + Keff * 4
-        e("s_mul_hi_u32", st[2], self.s_m0, st[3])
-        e("s_mul_i32", st[0], self.s_m0, st[3])
-        e("s_add_u32", self.srdA[0], A_[0], st[0])
-        e("s_addc_u32", self.srdA[1], A_[1], st[2])
+        self.kpanel_descriptor(self.srdA, self.ka0.sub(0, 2), self.s_m0, st[3], self.s_M, c.BM)
+
+    def kpanel_descriptor(self, srd, X_, x0, ld4, nx, BX):
+        """a k-contiguous panel (A; B passed transposed): base = X + x0 * ld * 4 + kb * 4; bytes = (min(nx - x0, BX) - 1) * ld * 4 + Keff * 4"""
+        c, e, st = self.c, self.p.emit, self.s_t
+        sh = c.ESZ.bit_length() - 1
+        e("s_mul_hi_u32", st[2], x0, ld4)
+        e("s_mul_i32", st[0], x0, ld4)
+        e("s_add_u32", srd[0], X_[0], st[0])
+        e("s_addc_u32", srd[1], X_[1], st[2])
         if c.persistent:
             e("s_lshl_b32", st[0], self.s_kb, sh)
-            e("s_add_u32", self.srdA[0], self.srdA[0], st[0])
-            e("s_addc_u32", self.srdA[1], self.srdA[1], 0)
-        e("s_and_b32", self.srdA[1], self.srdA[1], 0xffff)
-        e("s_sub_u32", st[0], self.s_M, self.s_m0)
-        e("s_min_u32", st[0], st[0], c.BM)
+            e("s_add_u32", srd[0], srd[0], st[0])
+            e("s_addc_u32", srd[1], srd[1], 0)
+        e("s_and_b32", srd[1], srd[1], 0xffff)
+        e("s_sub_u32", st[0], nx, x0)
+        e("s_min_u32", st[0], st[0], BX)
         e("s_sub_u32", st[0], st[0], 1)
-        e("s_mul_i32", st[0], st[0], st[3])
-        e("s_lshl_b32", st[2], Keff, sh)
-        e("s_add_u32", self.srdA[2], st[0], st[2])
-        e("s_mov_b32", self.srdA[3], 0x00020000)
-        if c.conv:
-            self.conv_setup(again)
-            if c.debug:
-                for r_ in range(0, 20, 4):
-                    self.dump_lds(f"tab[{r_ * 256}+4tid]", r_ * 256)
-                self.dump("conv k0", self.s_k0)
-                self.dump("conv HW4", self.s_HW4)
-                self.dump("conv Cin", self.s_Cin)
-                self.dump("conv WB00", self.lds_at(self.WB[0][0][2])[0])
-                self.dump("conv WB31", self.lds_at(self.WB[3][1][2])[0])
-        elif c.b_kcontig:
-            # B^T panel: base = B + n0 * ldb * 4 + kb * 4; bytes = (min(N - n0, BN) - 1) * ldb * 4 + Keff * 4
-            e("s_mul_hi_u32", st[2], self.s_n0, st[5])
-            e("s_mul_i32", st[0], self.s_n0, st[5])
-            e("s_add_u32", self.srdB[0], B_[0], st[0])
-            e("s_addc_u32", self.srdB[1], B_[1], st[2])
-            if c.persistent:
-                e("s_lshl_b32", st[0], self.s_kb, sh)
-                e("s_add_u32", self.srdB[0], self.srdB[0], st[0])
-                e("s_addc_u32", self.srdB[1], self.srdB[1], 0)
-            e("s_and_b32", self.srdB[1], self.srdB[1], 0xffff)
-            e("s_sub_u32", st[0], self.s_N, self.s_n0)
-            e("s_min_u32", st[0], st[0], c.BN)
-            e("s_sub_u32", st[0], st[0], 1)
-            e("s_mul_i32", st[0], st[0], st[5])
-            e("s_lshl_b32", st[2], Keff, sh)
-            e("s_add_u32", self.srdB[2], st[0], st[2])
-        else:
-            # B panel: base = B + n0 * 4 + kb * ldb * 4; bytes = (Keff - 1) * ldb * 4 + (N - n0) * 4
-            e("s_lshl_b32", st[0], self.s_n0, sh)
-            e("s_add_u32", self.srdB[0], B_[0], st[0])
-            e("s_addc_u32", self.srdB[1], B_[1], 0)
-            if c.persistent:
-                e("s_mul_hi_u32", st[2], self.s_kb, st[5])
-                e("s_mul_i32", st[0], self.s_kb, st[5])
-                e("s_add_u32", self.srdB[0], self.srdB[0], st[0])
-                e("s_addc_u32", self.srdB[1], self.srdB[1], st[2])
-            e("s_and_b32", self.srdB[1], self.srdB[1], 0xffff)
-            e("s_sub_u32", st[0], Keff, 1)
-            e("s_mul_i32", st[0], st[0], st[5])
-            e("s_sub_u32", st[2], self.s_N, self.s_n0)
-            e("s_lshl_b32", st[2], st[2], sh)
-            e("s_add_u32", self.srdB[2], st[0], st[2])
+        e("s_mul_i32", st[0], st[0], ld4)
+        e("s_lshl_b32", st[2], self.s_Keff, sh)
+        e("s_add_u32", srd[2], st[0], st[2])
+        e("s_mov_b32", srd[3], 0x00020000)
+
+    def b_descriptor(self):
+        c, e, st, Keff, B_ = self.c, self.p.emit, self.s_t, self.s_Keff, self.ka0.sub(2, 2)
+        if c.b_kcontig:
+            return self.kpanel_descriptor(self.srdB, B_, self.s_n0, st[5], self.s_N, c.BN)
+        # B panel: base = B + n0 * 4 + kb * ldb * 4; bytes = (Keff - 1) * ldb * 4 + (N - n0) * 4
+        sh = c.ESZ.bit_length() - 1
+        e("s_lshl_b32", st[0], self.s_n0, sh)
+        e("s_add_u32", self.srdB[0], B_[0], st[0])
+        e("s_addc_u32", self.srdB[1], B_[1], 0)
+        if c.persistent:
+            e("s_mul_hi_u32", st[2], self.s_kb, st[5])
+            e("s_mul_i32", st[0], self.s_kb, st[5])
+            e("s_add_u32", self.srdB[0], self.srdB[0], st[0])
+            e("s_addc_u32", self.srdB[1], self.srdB[1], st[2])
+        e("s_and_b32", self.srdB[1], self.srdB[1], 0xffff)
+        e("s_sub_u32", st[0], Keff, 1)
+        e("s_mul_i32", st[0], st[0], st[5])
+        e("s_sub_u32", st[2], self.s_N, self.s_n0)
+        e("s_lshl_b32", st[2], st[2], sh)
+        e("s_add_u32", self.srdB[2], st[0], st[2])
         e("s_mov_b32", self.srdB[3], 0x00020000)
 
     def run_setup(self):
@@ -1008,7 +989,7 @@ class Gen:
             self.kcontig_goff(self.vVB, c.NPB, st[5])
         e("s_nop", 4)
         self.ab_descriptors()
-        # C: the whole matrix (conv: this image's [M][oH*oW] block), bytes = (M - 1) * ldc * 4 + N * 4
+        # C: the whole matrix, bytes = (M - 1) * ldc * 4 + N * 4
         self.c_descriptor()
         # number of K-tiles
         e("s_add_u32", self.s_rem, Keff, c.BK - 1)
@@ -1021,9 +1002,8 @@ class Gen:
                 self.dump(f"srdB[{k_}]", self.srdB[k_])
             self.dump("vVA0", self.vVA[0])
             self.dump("vVA1", self.vVA[1])
-            if not c.conv:
-                self.dump("vVB0", self.vVB[0])
-                self.dump("vVB1", self.vVB[1])
+            for k_, r_ in enumerate(self.vVB[:2]):
+                self.dump(f"vVB{k_}", r_)
             self.dump("WA0", self.lds_at(self.WA[0][0][2])[0])
             self.dump("WA1", self.lds_at(self.WA[1][0][2])[0])
             self.dump("WB00", self.lds_at(self.WB[0][0][2])[0])
@@ -1043,14 +1023,8 @@ class Gen:
             state = (list(self.vmq), list(self.lgq))
             e("s_cmp_lt_u32", self.s_rem, 3)
             e("s_cbranch_scc1", L_slow)
-            pool = [r for slot in range(2) for r in (self.fa[slot] + self.fb[slot])]
             real = (self.stA, self.stB)
-            if c.conv:      # (B's pieces are register PAIRS there: two to a fragment register quad)
-                assert 4 * len(pool) >= 4 * c.NPA + 2 * c.NPB
-                tmp = (pool[:c.NPA], [pool[c.NPA + i // 2].sub(2 * (i % 2), 2) for i in range(c.NPB)])
-            else:
-                assert len(pool) >= c.NPA + c.NPB
-                tmp = (pool[:c.NPA], pool[c.NPA:c.NPA + c.NPB])
+            tmp = self.tmp_staging()
             self.stA, self.stB = tmp
             self.issue_loads_all()
             self.advance_srds()
@@ -1058,46 +1032,21 @@ class Gen:
             self.issue_loads_all()
             self.advance_srds()
             self.stA, self.stB = tmp
-            if c.conv:
-                # (the gathers of a tile are requested before its filter pieces: stored in that order, so that every counted wait names
-                # tile 0's loads; the table reads of tile 1's gathers were waited for before these stores were issued, in the other path
-                # after them: all LDS operations drained here keeps the two paths' queues alike)
-                self.run_ops([o for grp in self.conv_store_ops(2) for o in grp])
-                for pi in range(c.NPA):
-                    self.store_A_piece(pi, k=2)
-                self.lg_wait(None)
-            else:
-                self.store_tile_to_lds(2)
+            self.store_tile0_early()
             self.stA, self.stB = real
             e("s_branch", L_join)
             fast_state = (list(self.vmq), list(self.lgq))
             self.vmq, self.lgq = state
             p.place(L_slow)
-        self.tail_mask_if(self.s_rem, 1)        # a single K-tile: tile 0 is the last one
-        self.issue_loads_all()
-        self.mask_last_pieces_if(self.s_rem, 1)
-        self.advance_srds()
+        self.request_tile(1)        # a single K-tile: tile 0 is the last one
         if c.debug:
             e("s_waitcnt", vmcnt=0)
             self.vmq.clear()
             for k_ in range(4):
                 self.dump(f"stA0[{k_}]", self.stA[0][k_])
-            for k_ in range(2 if c.conv else 4):
-                self.dump(f"stB0[{k_}]", self.stB[0][k_])
-            if c.conv:
-                for i_ in range(8):
-                    self.dump(f"conv koff[{i_}]", self.s_koff[i_])
-                    self.dump(f"conv vB0[{i_}]", self.vB0[i_])
-                    self.dump(f"conv vB1[{i_}]", self.vB1[i_])
-                    self.dump(f"conv stB[{i_}][0]", self.stB[i_][0])
-                    self.dump(f"conv stB[{i_}][1]", self.stB[i_][1])
+            self.dump_stB()
             self.dump("stA_last[3]", self.stA[-1][3])
-        if c.conv:
-            for pi in range(c.NPA):
-                self.store_A_piece(pi, k=2)
-            self.run_ops([o for grp in self.conv_store_ops(2) for o in grp])
-        else:
-            self.store_tile_to_lds(2)       # tile 0 goes to LDS stage 0 = the "third" stage of the write triples
+        self.store_tile_to_lds(2)       # tile 0 goes to LDS stage 0 = the "third" stage of the write triples
         if c.debug:
             self.lg_wait(None)
             e("s_barrier")
@@ -1105,42 +1054,50 @@ class Gen:
                 self.dump_lds(f"lds[{k_ * 1024}+4tid]", c.LDS0 + k_ * 1024)
             self.dump_lds("ldsB[0+4tid]", c.LDS0 + c.BK * c.BM * 4)
             e("s_barrier")
-        self.tail_mask_if(self.s_rem, 2)
-        self.issue_loads_all()
-        self.mask_last_pieces_if(self.s_rem, 2)
-        self.advance_srds()
+        self.request_tile(2)
         if fast:
             assert (self.vmq, self.lgq) == fast_state, "the two prologue paths must leave the same loads and stores in flight"
             p.place(L_join)
         self.tail_mask_if(self.s_rem, 3)        # the first loop body loads tile 2
         self.first_tiles_done()
 
+    def request_tile(self, n):
+        """the next K-tile -> the current staging registers, as the last one if the run has n K-tiles"""
+        self.tail_mask_if(self.s_rem, n)
+        self.issue_loads_all()
+        self.mask_last_pieces_if(self.s_rem, n)
+        self.advance_srds()
+
+    def tmp_staging(self):
+        """staging registers for one more tile in flight, (A's, B's): the fragment registers, idle until the first fragment read"""
+        c, w = self.c, self.STB_REGS      # (B pieces narrower than a fragment register quad share one)
+        pool = [r for slot in range(2) for r in (self.fa[slot] + self.fb[slot])]
+        assert 4 * len(pool) >= 4 * c.NPA + w * c.NPB
+        return pool[:c.NPA], [pool[c.NPA + i * w // 4].sub(i * w % 4, w) for i in range(c.NPB)]
+
+    def dump_stB(self):
+        for k_ in range(self.STB_REGS):
+            self.dump(f"stB0[{k_}]", self.stB[0][k_])
+
+    def store_tile0_early(self):
+        """run_setup, tiles 0 and 1 requested back to back: tile 0 (in tmp_staging's registers) -> LDS stage 0"""
+        self.store_tile_to_lds(2)
+
     def store_tile_to_lds(self, k):
-        """every piece of the tile in the current staging registers -> LDS (write-address triple index k)"""
-        c = self.c
-        for pi in range(c.NPA):
-            self.store_A_piece(pi, k=k)
-        if c.b_kcontig:
-            for pj in range(c.NPB):
-                self.store_B_kpiece(pj, k=k)
-        else:
-            for gi in range(c.NPB // 2):
-                self.store_B_pair(gi, k=k)
+        """every piece of the tile in the current staging registers -> LDS (write-address triple index k): staging_ops without its loads"""
+        self.run_ops([o for o in self.staging_ops(k) if o[0] not in ("loadA", "loadB")])
 
     def first_tiles_deep(self):
         """deep staging: tile 0 -> LDS stage 0, tile 1 -> register set 1, tile 2 -> register set 0, both still in flight at the loop's
         entry.  Four or more K-tiles: all three requested back to back (tile 0 into the fragment registers), one memory latency
         per run; fewer: one after the other, each with the masks of a ragged last tile."""
-        c, p = self.c, self.p
-        e = p.emit
+        p, e = self.p, self.p.emit
         set0, set1 = self.st_sets
         L_slow, L_join = p.label("fewtiles"), p.label("tiles012")
         state = (list(self.vmq), list(self.lgq))
         e("s_cmp_lt_u32", self.s_rem, 4)
         e("s_cbranch_scc1", L_slow)
-        pool = [r for slot in range(2) for r in (self.fa[slot] + self.fb[slot])]
-        assert len(pool) >= c.NPA + c.NPB
-        tmp = (pool[:c.NPA], pool[c.NPA:c.NPA + c.NPB])
+        tmp = self.tmp_staging()
         for regs in (tmp, set1, set0):
             self.stA, self.stB = regs
             self.issue_loads_all()
@@ -1154,10 +1111,7 @@ class Gen:
         p.place(L_slow)
         for n, regs in ((1, set0), (2, set1), (3, set0)):
             self.stA, self.stB = regs
-            self.tail_mask_if(self.s_rem, n)        # n K-tiles: tile n - 1 is the last one
-            self.issue_loads_all()
-            self.mask_last_pieces_if(self.s_rem, n)
-            self.advance_srds()
+            self.request_tile(n)        # n K-tiles: tile n - 1 is the last one
             if n == 1:
                 self.store_tile_to_lds(2)
         self.stA, self.stB = set0
@@ -1210,21 +1164,11 @@ class Gen:
                 self.p.emit("v_mov_b32" if c.runv else "v_accvgpr_write_b32", self.run[b][r], 0)
 
     def c_descriptor(self):
-        """srdC = the whole C matrix (conv: this image's [M][oH*oW] block): bytes = (M - 1) * ldc * 4 + N * 4"""
+        """srdC = the whole C matrix (c_base), bytes = (M - 1) * ldc * 4 + N * 4"""
         c, e, st = self.c, self.p.emit, self.s_t
-        C_ = self.ka0.sub(4, 2)
         sh = c.ESZ.bit_length() - 1
         e("s_lshl_b32", self.s_ldc4, self.s_ldc, sh)
-        if c.conv:
-            img = self.s_img if c.cpers else s(3)
-            e("s_mul_hi_u32", st[2], img, self.s_scr[12])
-            e("s_mul_i32", st[0], img, self.s_scr[12])
-            e("s_add_u32", self.srdC[0], C_[0], st[0])
-            e("s_addc_u32", self.srdC[1], C_[1], st[2])
-            e("s_and_b32", self.srdC[1], self.srdC[1], 0xffff)
-        else:
-            e("s_mov_b32", self.srdC[0], C_[0])
-            e("s_and_b32", self.srdC[1], C_[1], 0xffff)
+        self.c_base(self.ka0.sub(4, 2))
         e("s_sub_u32", st[0], self.s_M, 1)
         e("s_mul_i32", st[0], st[0], self.s_ldc4)
         if self.s_csC4 is None:        # (convolution, f64: C's columns are adjacent)
@@ -1242,201 +1186,20 @@ class Gen:
         e("s_mov_b32", self.srdC[3], 0x00020000)
         self.c_row_step()
 
+    def c_base(self, C_):
+        """srdC[0], srdC[1] = where C starts: the kernel argument"""
+        self.p.emit("s_mov_b32", self.srdC[0], C_[0])
+        self.p.emit("s_and_b32", self.srdC[1], C_[1], 0xffff)
+
     def c_row_step(self):
         """s_ldc20 = c_step's stride from the last row of a lane's row quad to the first of its next quad"""
         self.p.emit("s_mul_i32", self.s_ldc20, self.s_ldc4, 5)
 
     def issue_loads_all(self):
-        if self.c.conv:      # (B's gathers first, like the loop body: the two queues must carry the same order)
-            self.run_ops([o for grp in self.conv_load_ops() for o in grp])
         for pi in range(self.c.NPA):
             self.load_A_piece(pi)
-        if self.c.conv:
-            return
         for pj in range(self.c.NPB):
             self.load_B_piece(pj)
-
-    # ------------------------------------------------------------------ implicit-GEMM convolution: the B operand
-    # B "matrix" [K = Cin*kH*kW][N = oH*oW] of image b is never materialised (conv2d_im2col.nim:62-87 builds it explicitly):
-    # element (k, pixel) = input[c][oh*sH + kh - pH][ow*sW + kw - pW], k = (c*kH + kh)*kW + kw.  One wave-instruction gathers one
-    # output pixel per lane of ONE k: lane l owns pixels n0 + 2l and n0 + 2l + 1 (two dword loads per piece).  The k part of the
-    # address -- (c*H*W + kh*W + kw) * 4 -- is wave-uniform and rides in the load's SGPR offset; the pixel part is a per-lane
-    # constant (oh*sH*W + ow*sW) * 4 -- or, where the tap falls into the zero padding (or the pixel lies beyond the image, or k
-    # beyond K), the offset 0x80000000 that the bounds check rejects, so the load returns 0 without touching memory.  Which of
-    # the two depends on the tap (kh, kw), which is wave-uniform but changes every K-tile: the kH*kW (+1: "nothing") per-lane
-    # offset vectors live in LDS and ds_read_addtid_b32 (address = M0 + 4*lane, no VGPR, no VALU op) fetches the right one -- any
-    # VALU op in the loop costs ~11 cycles of matrix-pipe time (profiles/r03/asm_probe_v4_fillers.jsonl).  Kernel size, strides and
-    # padding are RUN-TIME values (round 6): they only shape the table (built once per tile by a scalar loop over the taps, the
-    # four waves taking every fourth tap) and the scalar tap arithmetic; the loop still has no vector instruction.  Wave w owns
-    # k = 8w .. 8w+7 of every K-tile: pairs (k, k+2) per lane exactly like the GEMM's pair mode.
-    CONV_DELTA = (0, 2, 1, 3, 4, 6, 5, 7)      # piece i = 2*pair + j gathers k = 8w + delta: pairs (0,2) (1,3) (4,6) (5,7)
-
-    def conv_setup(self, again=False):
-        """per tile: the geometry, the lanes' pixels, the tap table, srdB, the tap state; again (Cfg.cpers, the switch to the next unit
-        inside the K loop): the per-lane LDS write addresses -- the same for every tile -- are left alone"""
-        c, p, e, t, st, scr = self.c, self.p, self.p.emit, self.vt, self.s_t, self.s_scr
-        B_ = self.ka0.sub(2, 2)
-        sH, sW, soW, spH, spW, sCin, sNpix, smagic, sgeo, snt = (scr[i] for i in range(10))
-        e("s_load_dwordx8", scr.sub(0, 8), s(0, 2), KA_CONV0)
-        e("s_load_dwordx4", scr.sub(8, 4), s(0, 2), KA_CONV1)
-        e("s_load_dwordx2", scr.sub(12, 2), s(0, 2), KA_CONV2)
-        e("s_waitcnt", lgkmcnt=0)
-        # geometry word: kH | kW << 8 | strideH << 16 | strideW << 24; taps word: kH * kW | ceil(1024 / kW) << 16
-        e("s_bfe_u32", self.s_kW, sgeo, (8 << 16) | 8)
-        e("s_and_b32", self.s_NT, snt, 0xffff)
-        e("s_lshr_b32", self.s_M10, snt, 16)
-        e("s_bfe_u32", scr[14], sgeo, (8 << 16) | 16)         # strideH
-        e("s_lshr_b32", scr[15], sgeo, 24)                    # strideW
-        sSH, sSW = scr[14], scr[15]
-        lane, tab = t[0], t[1]
-        pix = [t[2], t[3]]
-        rowb, colb, base = [self.vT[0][0], self.vT[0][1]], [self.vT[0][2], self.vT[0][3]], [self.vT[0][4], self.vT[0][5]]
-        e("v_and_b32", lane, 63, v(0))
-        e("v_lshlrev_b32", tab, 2, lane)
-        e("s_cmp_eq_u32", smagic, 0)
-        e("s_cselect_b64", self.s_m, -1, 0)
-        for ee in range(2):
-            oh, ow = t[4], t[5]
-            e("v_lshl_add_u32", pix[ee], lane, 1, self.s_n0)      # this lane's output pixel ee: n0 + 2 * lane + ee
-            if ee:
-                e("v_add_u32", pix[ee], 1, pix[ee])
-            e("v_mul_hi_u32", oh, pix[ee], smagic)                # oh = pix / oW (the pair may straddle two output rows: odd widths)
-            e("v_cndmask_b32", oh, oh, pix[ee], self.s_m)         # (oW == 1 travels as magic 0: oh = pix)
-            e("v_mul_lo_u32", t[6], oh, soW)
-            e("v_sub_u32", ow, pix[ee], t[6])                     # ow = pix % oW
-            e("v_mul_lo_u32", t[6], oh, sSH)                      # oh * strideH
-            e("v_mul_lo_u32", t[7], ow, sSW)                      # ow * strideW
-            e("v_subrev_u32", rowb[ee], spH, t[6])                # input row of tap row 0 (as unsigned: negative = huge)
-            e("v_subrev_u32", colb[ee], spW, t[7])
-            e("v_mul_lo_u32", t[6], t[6], sW)
-            e("v_add_u32", t[6], t[6], t[7])
-            e("v_lshlrev_b32", base[ee], 2, t[6])                 # (oh*sH*W + ow*sW) * 4, relative to the window origin of pixel (0, 0)
-            e("v_cmp_gt_u32", self.s_pok[ee], sNpix, pix[ee])     # pixels beyond the image (ragged last tile) gather nothing
-        e("s_nop", 1)
-        # the table: entry r = kh * kW + kw holds, per lane and pixel, the base offset where the tap reads inside the image, the
-        # out-of-bounds offset elsewhere.  The same for the 4 waves (they own different k of the same 128 pixels): wave w writes the
-        # entries w, w + 4, ...; wave 0 also the "nothing" entry (index taps) that channels beyond Cin select
-        L_tap, L_tapd, L_non = p.label("tap"), p.label("tapsdone"), p.label("nonothing")
-        sr, skh, skw, soff = st[0], st[2], st[3], st[4]
-        e("s_mov_b32", sr, self.s_wave)
-        p.place(L_tap)
-        e("s_cmp_ge_u32", sr, self.s_NT)
-        e("s_cbranch_scc1", L_tapd)
-        e("s_mul_i32", skh, sr, self.s_M10)
-        e("s_lshr_b32", skh, skh, 10)                             # kh = r / kW
-        e("s_mul_i32", skw, skh, self.s_kW)
-        e("s_sub_u32", skw, sr, skw)                              # kw = r % kW
-        e("s_lshl_b32", soff, sr, 8)
-        e("v_add_u32", t[6], soff, tab)
-        for ee in range(2):
-            e("v_add_u32", t[4], skh, rowb[ee])
-            e("v_cmp_gt_u32", VCC, sH, t[4])                      # input row oh*sH + kh - pH exists
-            e("v_add_u32", t[5], skw, colb[ee])
-            e("v_cmp_gt_u32", self.s_m, sW, t[5])                 # input column exists
-            e("s_nop", 1)
-            e("s_and_b64", self.s_m, self.s_m, VCC)
-            e("s_and_b64", self.s_m, self.s_m, self.s_pok[ee])
-            e("s_nop", 0)
-            e("v_cndmask_b32", t[7], self.v_oob, base[ee], self.s_m)
-            e("ds_write_b32", t[6], t[7], offset=ee * c.TAB_E1)
-        e("s_add_u32", sr, sr, 4)
-        e("s_branch", L_tap)
-        p.place(L_tapd)
-        e("s_cmp_lg_u32", self.s_wave, 0)
-        e("s_cbranch_scc1", L_non)
-        e("s_lshl_b32", soff, self.s_NT, 8)
-        e("v_add_u32", t[6], soff, tab)
-        e("ds_write_b32", t[6], self.v_oob)
-        e("ds_write_b32", t[6], self.v_oob, offset=c.TAB_E1)
-        p.place(L_non)
-        e("s_waitcnt", lgkmcnt=0)
-        e("s_barrier")
-        # descriptor: base = B + b * bsB - (pH*W + pW) * 4 (the window origin of output pixel (0, 0), kernel tap (0, 0));
-        # every address a valid lane forms lies inside the image -- the bounds field only has to reject v_oob
-        img = self.s_img if c.cpers else s(3)
-        e("s_mul_hi_u32", st[2], img, scr[10])
-        e("s_mul_i32", st[0], img, scr[10])
-        e("s_add_u32", st[0], B_[0], st[0])
-        e("s_addc_u32", st[2], B_[1], st[2])
-        e("s_mul_i32", st[3], spH, sW)
-        e("s_add_u32", st[3], st[3], spW)
-        e("s_lshl_b32", st[3], st[3], 2)
-        e("s_sub_u32", self.srdB[0], st[0], st[3])
-        e("s_subb_u32", self.srdB[1], st[2], 0)
-        e("s_and_b32", self.srdB[1], self.srdB[1], 0xffff)
-        e("s_mov_b32", self.srdB[2], 0x7fffffff)
-        e("s_lshl_b32", self.s_W4, sW, 2)
-        e("s_mul_i32", self.s_HW4, self.s_W4, sH)
-        e("s_mov_b32", self.s_Cin, sCin)
-        # LDS write addresses of pair gi, pixel e: x = 2*lane + e, k = 8w + (0, 1, 4, 5)[gi]: L = 2w + (gi & 1), word = (0,0,2,2)[gi]
-        e("s_mov_b32", st[0], c.LDS0 + c.ROWP * c.BM)
-        for gi in range(0 if again else 4):
-            e("s_lshl_b32", st[3], self.s_wave, 1)
-            e("s_add_u32", st[3], st[3], gi & 1)
-            for ee in range(2):
-                xx, rr, ss = t[4], t[5], t[6]
-                e("v_lshl_add_u32", xx, lane, 1, ee)
-                self.kq_row(rr, xx, t[7])
-                self.kq_swz(ss, xx, t[7])
-                e("v_xor_b32", ss, st[3], ss)
-                e("v_mul_u32_u24", rr, c.ROWP, rr)
-                e("v_lshl_add_u32", rr, ss, 4, rr)
-                e("v_add_u32", rr, 4 * (0, 0, 2, 2)[gi], rr)
-                e("v_add_u32", self.lds_at(self.WB[gi][ee][2])[0], st[0], rr)
-                if c.il:
-                    continue
-                e("v_add_u32", self.WB[gi][ee][0], c.STAGE, self.WB[gi][ee][2])
-                e("v_add_u32", self.WB[gi][ee][1], 2 * c.STAGE, self.WB[gi][ee][2])
-        # running k of this wave: 8w, + BK per K-tile
-        e("s_lshl_b32", self.s_k0, self.s_wave, 3)
-
-    def conv_load_ops(self):
-        """per piece: [scalar tap arithmetic] [SGPR offset, table entry -> M0, the two offset vectors from LDS]; then, for every
-        piece, [the two gathers]; then the state moves on by BK.  Returns a list of op groups (one per MFMA gap).
-        k -> channel c = k / taps (magic multiply: KA_TAB carries floor(2^32 / taps) + 1, 0 for one tap), r = k % taps,
-        kh = r / kW = (r * ceil(1024 / kW)) >> 10 (exact for r < 49), kw = r % kW."""
-        c, st = self.c, self.s_t
-        mgNT = self.ka0[6]
-        groups, loads = [], []
-        for i in range(8):
-            d = self.CONV_DELTA[i]
-            g1 = [("ins", "s_add_u32", (st[0], self.s_k0, d), {}),               # k
-                  ("ins", "s_mul_hi_u32", (st[1], st[0], mgNT), {}),
-                  ("ins", "s_cmp_eq_u32", (mgNT, 0), {}),
-                  ("ins", "s_cselect_b32", (st[1], st[0], st[1]), {}),           # c = k / taps
-                  ("ins", "s_mul_i32", (st[2], st[1], self.s_NT), {}),
-                  ("ins", "s_sub_u32", (st[0], st[0], st[2]), {}),               # r = k % taps
-                  ("ins", "s_mul_i32", (st[2], st[0], self.s_M10), {}),
-                  ("ins", "s_lshr_b32", (st[2], st[2], 10), {}),                 # kh = r / kW
-                  ("ins", "s_mul_i32", (st[3], st[2], self.s_kW), {}),
-                  ("ins", "s_sub_u32", (st[5], st[0], st[3]), {})]               # kw = r % kW
-            g2 = [("ins", "s_mul_i32", (st[3], st[1], self.s_HW4), {}),
-                  ("ins", "s_mul_i32", (st[4], st[2], self.s_W4), {}),
-                  ("ins", "s_add_u32", (st[3], st[3], st[4]), {}),
-                  ("ins", "s_lshl_b32", (st[4], st[5], 2), {}),
-                  ("ins", "s_add_u32", (self.s_koff[i], st[3], st[4]), {}),  # (c*H*W + kh*W + kw) * 4
-                  ("ins", "s_cmp_lt_u32", (st[1], self.s_Cin), {}),
-                  ("ins", "s_cselect_b32", (st[0], st[0], self.s_NT), {}),   # channels beyond Cin (k >= K): the "nothing" entry
-                  ("ins", "s_lshl_b32", (M0, st[0], 8), {}),
-                  ("ins", "s_nop", (0,), {}),                                # (S_MOV to M0 -> LDS add-TID instruction: 1 wait state)
-                  ("ldsr", "ds_read_addtid_b32", (self.vB0[i],), {}, ("T", i)),
-                  ("ldsr", "ds_read_addtid_b32", (self.vB1[i],), {"offset": c.TAB_E1}, ("T", i))]
-            groups += [g1, g2]
-            loads.append([("lgwait", {("T", i)}), ("loadBc", i, 0), ("loadBc", i, 1)])
-        groups += loads
-        groups.append([("ins", "s_add_u32", (self.s_k0, self.s_k0, c.BK), {})])
-        return groups
-
-    def conv_store_ops(self, k):
-        """tile data in the B staging registers -> LDS stage index k; returns op groups"""
-        out = []
-        for gi in range(4):
-            P, Q = self.stB[2 * gi], self.stB[2 * gi + 1]
-            for ee in range(2):
-                g = [("vmwait", ("B", 2 * gi + 1, 1))] if ee == 0 else []
-                g.append(self.w2(self.WB[gi][ee][k], P[ee], Q[ee]))
-                out.append(g)
-        return out
 
     def load_A_piece(self, pi):
         if "loads" in self.c.ablate:
@@ -1454,13 +1217,17 @@ class Gen:
         """descriptors move one K-tile along k: base += step, bytes = max(bytes - step, 0)"""
         e = self.p.emit
         ops = []
-        for srd, step in ((self.srdA, self.c.BK * self.c.ESZ),) + (() if self.c.conv else ((self.srdB, self.b_step()),)):
+        for srd, step in self.k_steps():
             ops += [("s_add_u32", srd[0], srd[0], step), ("s_addc_u32", srd[1], srd[1], 0),
                     ("s_sub_u32", srd[2], srd[2], step), ("s_cselect_b32", srd[2], 0, srd[2])]
         if which is None:
             for o in ops:
                 e(*o)
         return ops
+
+    def k_steps(self):
+        """(descriptor, bytes it moves per K-tile) of the operands whose descriptors walk along k"""
+        return (self.srdA, self.c.BK * self.c.ESZ), (self.srdB, self.b_step())
 
     def b_step(self):
         """bytes B's descriptor moves per K-tile"""
@@ -1488,28 +1255,21 @@ class Gen:
         return ("ldsw", "ds_write2_b32", (reg, d0, d1), {"offset0": off // 4, "offset1": off // 4 + 1})
 
     def store_A_piece(self, pi, ops=None, k=0):
-        """piece = 4 consecutive k (e0 e1 e2 e3) of one row: (e0, e2) -> chunk of MFMA half 0, (e1, e3) -> half 1"""
-        out = []
-        r = self.stA[pi]
-        out.append(("vmwait", ("A", pi)))
-        out += self.pre_op([r[j] for j in range(4)], self.s_preA)
-        # ds_write2_b32 takes its two dwords from two independent registers: no repacking VALU op (a v_swap on freshly
-        # loaded registers cost 16 cycles of matrix-pipe time per piece, profiles/r03/asm_probe_v7.jsonl); the price is one
-        # address register per (piece, half, stage)
-        out.append(self.w2(self.WA[0][pi][k], r[0], r[2]))
-        out.append(self.w2(self.WA[1][pi][k], r[1], r[3]))
-        if ops is None:
-            self.run_ops(out)
-        return out
+        return self.store_kpiece(("A", pi), self.stA[pi], self.s_preA, self.WA, ops, k)
 
     def store_B_kpiece(self, pj, ops=None, k=0):
         """B passed transposed (k-contiguous): the same two ds_write2_b32 per piece as A"""
-        out = []
-        r = self.stB[pj]
-        out.append(("vmwait", ("B", pj)))
-        out += self.pre_op([r[j] for j in range(4)], self.s_preB)
-        out.append(self.w2(self.WB[0][pj][k], r[0], r[2]))
-        out.append(self.w2(self.WB[1][pj][k], r[1], r[3]))
+        return self.store_kpiece(("B", pj), self.stB[pj], self.s_preB, self.WB, ops, k)
+
+    def store_kpiece(self, tag, r, pre, W, ops, k):
+        """piece = 4 consecutive k (e0 e1 e2 e3) of one row: (e0, e2) -> chunk of MFMA half 0, (e1, e3) -> half 1"""
+        out = [("vmwait", tag)]
+        out += self.pre_op([r[j] for j in range(4)], pre)
+        # ds_write2_b32 takes its two dwords from two independent registers: no repacking VALU op (a v_swap on freshly
+        # loaded registers cost 16 cycles of matrix-pipe time per piece, profiles/r03/asm_probe_v7.jsonl); the price is one
+        # address register per (piece, half, stage)
+        out.append(self.w2(W[0][tag[1]][k], r[0], r[2]))
+        out.append(self.w2(W[1][tag[1]][k], r[1], r[3]))
         if ops is None:
             self.run_ops(out)
         return out
@@ -1517,7 +1277,7 @@ class Gen:
     def apply_tail_mask(self):
         """the loads issued from here on fetch the last K-tile: pieces beyond K read as 0"""
         e = self.p.emit
-        regs = list(self.vVA) + (list(self.vVB) if (self.c.b_kcontig and not self.c.conv) else [])
+        regs = list(self.vVA) + (list(self.vVB) if self.c.b_kcontig else [])
         for r in regs:
             e("v_cndmask_b32", r, self.v_oob, r, self.s_tm)
 
@@ -1525,8 +1285,6 @@ class Gen:
         """K % 4 != 0 and `sreg` == value: the staging registers hold the last K-tile (requested one step earlier): wait for it and
         zero the elements beyond K.  ~NPA * 4 v_cndmask once per workgroup; the counted waits that follow are then satisfied early."""
         c, e = self.c, self.p.emit
-        if c.conv:
-            return
         skip = self.p.label("nok4")
         e("s_and_b32", self.s_t[0], self.s_Keff, 3)
         e("s_cmp_eq_u32", self.s_t[0], 0)
@@ -1610,10 +1368,6 @@ class Gen:
             self.load_A_piece(o[1])
         elif kind == "loadB":
             self.load_B_piece(o[1])
-        elif kind == "loadBc":
-            if "loads" not in self.c.ablate:
-                self.p.emit("buffer_load_dword", self.stB[o[1]][o[2]], (self.vB0, self.vB1)[o[2]][o[1]], self.srdB, self.s_koff[o[1]], offen=True)
-                self.vm_issue(("B", o[1], o[2]))
         elif kind == "barrier":
             self.lg_wait(None)
             self.p.emit("s_barrier")
@@ -1645,9 +1399,7 @@ class Gen:
         for pi in range(c.NPA):
             stg += self.store_A_piece(pi, ops=[], k=wr_k)
             stg.append(("loadA", pi))
-        if c.conv:
-            pass
-        elif c.b_kcontig:
+        if c.b_kcontig:
             for pj in range(c.NPB):
                 stg += self.store_B_kpiece(pj, ops=[], k=wr_k)
                 stg.append(("loadB", pj))
@@ -1657,6 +1409,16 @@ class Gen:
                 stg.append(("loadB", 2 * gi))
                 stg.append(("loadB", 2 * gi + 1))
         return stg
+
+    def staging_units(self, wr_k):
+        """staging_ops in units, one per MFMA gap: a wait, and a fused prologue's VALU batch, ride with the op that follows / precedes them"""
+        units = []
+        for op in self.staging_ops(wr_k):
+            if units and (units[-1][-1][0] in ("vmwait",) or (op[0] == "call" and units[-1][-1][0] == "call")):
+                units[-1].append(op)
+            else:
+                units.append([op])
+        return units
 
     # ------------------------------------------------------------------ the matrix instruction and the slice fold
     def emit_mfma(self, b, slot, i, n, u, srcc):
@@ -1717,7 +1479,7 @@ class Gen:
     def fold_after(self, b):
         # run += alpha * slice, unfused (gemm_ukernel_generic.nim:68-76)
         self.alpha_mul_outlined("a")
-        if c_runv(self):
+        if self.c.runv:
             if "foldadds" in self.c.ablate:
                 return
             if "foldscalar" in self.c.ablate:     # (pricing: 16 single adds instead of 8 packed ones -- same result)
@@ -1810,33 +1572,12 @@ class Gen:
         e("s_cmp_lg_u32", st[2], 0)
         e("s_cselect_b32", self.srdCd[2], 0, self.srdCd[2])
 
-    def next_unit(self, L_none):
-        """Cfg.cpers: the workgroup's next unit -> s_img, s_m0, s_n0 (L_none when there is none).  KA_SCHED2 carries, for these kernels,
-        +4 the tiles of one image, +8 their magic number, +12 the stride (= workgroups), +16 the units of the launch (images x tiles).
-        Clobbers s_scr[0..7] (dead outside a tile body's load section) and s_t[0..5]."""
-        c, e, st, sc = self.c, self.p.emit, self.s_t, self.s_sc
-        e("s_load_dwordx8", sc, s(0, 2), KA_SCHED2)
-        e("s_waitcnt", lgkmcnt=0)
-        e("s_cmp_ge_u32", self.s_tcur, sc[4])
-        e("s_cbranch_scc1", L_none)
-        self.udiv(self.s_img, self.s_tcur, sc[2])
-        e("s_mul_i32", st[4], self.s_img, sc[1])
-        e("s_sub_u32", st[4], self.s_tcur, st[4])                     # the tile inside the image
-        e("s_add_u32", self.s_tcur, self.s_tcur, sc[3])
-        e("s_load_dwordx8", sc, s(0, 2), KA_SCHED)
-        e("s_waitcnt", lgkmcnt=0)
-        self.tile_coords(st[4], sc, st[0], st[1], (st[2], st[3], st[5]))
-        e("s_mul_i32", self.s_m0, st[0], c.BM)
-        e("s_mul_i32", self.s_n0, st[1], c.BN)
-
-    def pipe_switch_conv(self, stubs, rets):
-        """pipe_switch of the convolution kernels (Cfg.cpers).  Every wave that gets here has passed the barrier of the tile body it
-        comes from, and a wave only reaches that barrier after its last look at the tap table (the table reads of a body precede its
-        gathers, the gathers the barrier): the table of the tile being finished can be overwritten at once; conv_setup's own barrier
-        stands between the new table's writes and its first reads.  Scalar tap state, srdB and srdC move to the next unit; the C
-        addresses of the tile being finished were put aside first."""
-        c, p = self.c, self.p
-        e, st = p.emit, self.s_t
+    def pipe_switch(self, stubs, rets):
+        """out of line, reached from the tail of the tile body after which TWO K-tiles of the tile are left (every load of the tile has
+        been requested): if the next run of this workgroup is another whole tile of a launch that may pipeline, the C addresses of the
+        tile being finished are put aside, the scheduler moves on and srdA / srdB are pointed at the next tile -- the two tile bodies
+        that follow fetch ITS first two K-tiles where they would have fetched zeros past K (switch_tile).  stubs[site] set the return site."""
+        p, e, st = self.p, self.p.emit, self.s_t
         L_sw, L_out = p.label("switch"), p.label("swout")
         for site, lab in stubs.items():
             p.place(lab)
@@ -1845,14 +1586,7 @@ class Gen:
         p.place(L_sw)
         e("s_bitcmp1_b32", self.s_pipe, 0)
         e("s_cbranch_scc0", L_out)
-        e("s_load_dword", st[0], s(0, 2), KA_SCHED2 + 16)
-        e("s_waitcnt", lgkmcnt=0)
-        e("s_cmp_lt_u32", self.s_tcur, st[0])
-        e("s_cbranch_scc0", L_out)
-        self.pipe_c_addr()
-        self.next_unit(L_out)
-        self.ab_descriptors(again=True)
-        self.c_descriptor()
+        self.switch_tile(L_out)
         e("s_or_b32", self.s_pipe, self.s_pipe, 2)
         p.place(L_out)
         e("s_lshr_b32", st[0], self.s_pipe, 4)
@@ -1863,23 +1597,9 @@ class Gen:
             e("s_cbranch_scc1", rets[site])
         e("s_branch", rets[sites[-1]])
 
-    def pipe_switch(self, stubs, rets):
-        if self.c.cpers:
-            return self.pipe_switch_conv(stubs, rets)
-        """out of line, reached from the tail of the tile body after which TWO K-tiles of the tile are left (every load of the tile has
-        been requested): if the next run of this workgroup is another whole tile of a launch that may pipeline, the C addresses of the
-        tile being finished are put aside, the scheduler moves on and srdA / srdB are pointed at the next tile -- the two tile bodies
-        that follow fetch ITS first two K-tiles where they would have fetched zeros past K.  stubs[site] set the return site."""
-        c, p = self.c, self.p
-        e, st, sc = p.emit, self.s_t, self.s_sc
-        L_sw, L_out = p.label("switch"), p.label("swout")
-        for site, lab in stubs.items():
-            p.place(lab)
-            e("s_or_b32", self.s_pipe, self.s_pipe, site << 4)
-            e("s_branch", L_sw)
-        p.place(L_sw)
-        e("s_bitcmp1_b32", self.s_pipe, 0)
-        e("s_cbranch_scc0", L_out)
+    def switch_tile(self, L_out):
+        """pipe_switch: on to the next whole tile of this workgroup, or to L_out when what follows is something else"""
+        e, st, sc = self.p.emit, self.s_t, self.s_sc
         e("s_cmp_eq_u32", self.s_phase, 1)                  # (the head slices of phase 0 run with s_phase == 1 too: END_SEND tells)
         e("s_cbranch_scc0", L_out)
         e("s_cmp_eq_u32", self.s_end, END_EPI)
@@ -1895,19 +1615,8 @@ class Gen:
         e("s_load_dwordx8", sc, s(0, 2), KA_SCHED)
         e("s_waitcnt", lgkmcnt=0)
         e("s_add_u32", st[4], self.s_tile, self.ka0[6])           # (the launch's first tile: prologue)
-        self.tile_coords(st[4], sc, st[0], st[1], (st[2], st[3], st[5]))
-        e("s_mul_i32", self.s_m0, st[0], c.BM)
-        e("s_mul_i32", self.s_n0, st[1], c.BN)
+        self.tile_origin(st[4])
         self.ab_descriptors()
-        e("s_or_b32", self.s_pipe, self.s_pipe, 2)
-        p.place(L_out)
-        e("s_lshr_b32", st[0], self.s_pipe, 4)
-        e("s_and_b32", self.s_pipe, self.s_pipe, 15)
-        sites = sorted(rets)
-        for site in sites[:-1]:
-            e("s_cmp_eq_u32", st[0], site)
-            e("s_cbranch_scc1", rets[site])
-        e("s_branch", rets[sites[-1]])
 
     # ------------------------------------------------------------------ one K-tile
     def tile_body(self, fold, stage=None, regset=0, trans=False):
@@ -1955,23 +1664,7 @@ class Gen:
         # register of a triple: [0] / [1] = this tile's / the next tile's stage when the triples rotate; with one body per
         # stage, reads of stage k use index k and writes index (k + 2) % 3 (the triples were initialised for stage 0)
         wr_k = ((stage + 1) % 3 + 2) % 3
-        stg = self.staging_ops(wr_k)
-        # waits ride with the op that follows them
-        units = []
-        for op in stg:
-            if units and (units[-1][-1][0] in ("vmwait",) or (op[0] == "call" and units[-1][-1][0] == "call")):
-                units[-1].append(op)        # (a wait, and a fused prologue's VALU batch, ride with the op that follows / precedes them)
-            else:
-                units.append([op])
-        if c.conv:
-            # B first (its gathers were requested a tile ago and are needed soonest): stores, then the scalar tap state and
-            # the offset vectors of tile t+2, its 16 gathers, then A's pieces; one unit per gap
-            cu = self.conv_store_ops(wr_k)
-            a_units = []
-            for pi in range(c.NPA):
-                a = self.store_A_piece(pi, ops=[], k=wr_k)
-                a_units += [a[:2], [a[2]], [("loadA", pi)]]
-            units = cu + self.conv_load_ops() + a_units
+        units = self.staging_units(wr_k)
         w0 = max(c.w_start, first_free + (c.TM + c.TN + 2 if fold else 0))
         if fold and bar - 1 - w0 < 2:         # very few gaps (16 MFMAs per tile): staging shares the gaps of the fragment reads
             w0 = first_free
@@ -2429,7 +2122,7 @@ class Gen:
 
     # ------------------------------------------------------------------ runs that share a tile: workspace, flags, ordered fix-up
     def end_run(self):
-        if self.c.persistent or self.c.cpers:
+        if self.c.loops:
             self.p.emit("s_branch", self.L_run)
         else:
             self.p.emit("s_endpgm")
@@ -2635,7 +2328,7 @@ class Gen:
         for label, fn in self.outlined_blocks:
             self.p.place(label)
             fn()
-        if self.c.persistent or self.c.cpers:
+        if self.c.loops:
             self.p.place(self.L_exit)
             self.p.emit("s_endpgm")
         return self.p
@@ -2644,7 +2337,11 @@ class Gen:
 def make(name, **over):
     kw = dict(CONFIGS[name])
     kw.update(over)
-    return Gen(Cfg(name, **kw))
+    cfg = Cfg(name, **kw)
+    if cfg.conv:
+        from .conv_kernel import ConvGen     # (here: conv_kernel imports this module)
+        return ConvGen(cfg)
+    return Gen(cfg)
 
 
 def kernel_text(gen, symbol):

@@ -140,12 +140,6 @@ class Gen16x16(Gen):
                 self.p.emit("v_mov_b64", self.run[b].sub(2 * j, 2), 0)
 
     # ------------------------------------------------------------------ LDS stores: the family's store_A_piece / store_B_piece
-    def store_tile_to_lds(self, k):
-        for pi in range(self.c.NPA):
-            self.store_A_piece(pi, k=k)
-        for pj in range(self.c.NPB):
-            self.store_B_piece(pj, k=k)
-
     def staging_ops(self, wr_k):
         c, stg = self.c, []
         for pi in range(c.NPA):

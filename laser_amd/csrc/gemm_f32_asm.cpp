@@ -54,7 +54,7 @@ enum Family : uint8_t {
   kF64,        // float64 GEMM (v_mfma_f64_16x16x4_f64; asmgen/f64_kernel.py)
   kI32,        // int32 GEMM via four int8 limb planes (asmgen/i8_kernel.py)
   kI64,        // int64 GEMM via eight int8 limb planes (i8_kernel.py "i64_64x64x32")
-  kConv,       // implicit-GEMM convolution, any kernel size / stride / zero padding (f32_kernel.py)
+  kConv,       // implicit-GEMM convolution, any kernel size / stride / zero padding (conv_kernel.py)
   kConvWalk,   // the same as unit walkers (f32_kernel.py Cfg.cpers): a workgroup runs units (image, tile) g, g + G, g + 2G ... and goes
                // from one to the next inside its K loop (the next unit's first gathers before the old tile's last K-tiles are
                // multiplied, the old tile's C stores from the gaps of the new tile's first K-tile body)
@@ -621,7 +621,7 @@ hipError_t launch_planned(DeviceModule *m, int kern, const Plan &plan_in, KernAr
   }
   unsigned gx = (unsigned)plan.G, gy = (unsigned)batch;
   if (walk_G > 0) {
-    // unit walkers (convolution, f32_kernel.py next_unit): units = images x tiles of one image, workgroup g runs g, g + walk_G, ...;
+    // unit walkers (convolution, conv_kernel.py next_unit): units = images x tiles of one image, workgroup g runs g, g + walk_G, ...;
     // +4 the tiles of an image, +8 their magic number (unit / tiles: exact while units * tiles < 2^32), +12 the stride, +16 the units
     const int64_t units = T * batch;
     if (plan.persistent || plan.P != 1 || walk_G > units || (double)units * (double)T >= 4.0e9) return hipErrorNotSupported;
@@ -1247,7 +1247,7 @@ hipError_t launch_conv_f32_asm(const GemmArgs<float> &a_in, bool laser_order, hi
   ka.A = packed ? packed : a.A;
   ka.B = a.B;
   ka.C = a.C;
-  ka.unused_ = (const uint32_t *)(uintptr_t)magic_u32((uint64_t)taps);   // f32_kernel.py conv_load_ops: k / taps (KA_TAB's low word)
+  ka.unused_ = (const uint32_t *)(uintptr_t)magic_u32((uint64_t)taps);   // conv_kernel.py conv_load_ops: k / taps (KA_TAB's low word)
   ka.lda = (uint32_t)Kp;
   ka.ldb = 0;
   ka.ldc = (uint32_t)npix;
@@ -1264,7 +1264,7 @@ hipError_t launch_conv_f32_asm(const GemmArgs<float> &a_in, bool laser_order, hi
   ka.Cin = (uint32_t)Cin;
   ka.Npix = (uint32_t)npix;
   ka.magic_oW = magic_u32((uint64_t)oW);   // floor(p / oW) = mulhi(p, magic) for p * oW < 2^32; 0 for oW == 1 (the kernel then takes p)
-  ka.shift_oW = (uint32_t)(kH | kW << 8 | sH << 16 | sW << 24);     // geometry word (f32_kernel.py conv_setup)
+  ka.shift_oW = (uint32_t)(kH | kW << 8 | sH << 16 | sW << 24);     // geometry word (conv_kernel.py conv_setup)
   ka.pad_ = (uint32_t)(taps | ((1024 + kW - 1) / kW) << 16);         // taps | ceil(1024 / kW) << 16: kh = (r * that) >> 10
   ka.bsB_bytes = (uint64_t)a.bsB * 4;
   ka.bsC_bytes = (uint64_t)a.bsC * 4;
