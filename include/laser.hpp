@@ -495,6 +495,52 @@ Acc forEachReduce(const std::string &body, const std::string &merge, Acc init, c
   return v;
 }
 
+// ---- exp and row softmax (include/laser_hip.h "exp and row softmax"): simd_math/exp_log_*.nim over device Tensors ---------
+//   laser::exp(y, x);  laser::softmax(y, x);     (asynchronous on `stream`; y may be x)
+// exp: Laser's table-driven exp, bit for bit; x broadcasts against y.  softmax: over the rows of a 2-D Tensor whose last
+// stride is 1, summed in the fixed order of the reductions.
+inline void exp(Tensor<float> &dst, const Tensor<float> &src, void *stream = nullptr) {
+  const int r = dst.rank(), pad = r - src.rank();
+  if (pad < 0) throw Error(LASER_HIP_E_INVALID, "exp: the source has more dimensions than the destination");
+  std::vector<int64_t> ss((size_t)(r > 0 ? r : 1), 0);
+  for (int d = pad; d < r; d++) {  // numpy broadcasting: missing / extent-1 dimensions get stride 0
+    const int64_t e = src.shape[d - pad];
+    if (e != dst.shape[d] && e != 1) throw Error(LASER_HIP_E_INVALID, "exp: the source does not broadcast to the destination");
+    ss[d] = e == 1 ? 0 : src.strides[d - pad];
+  }
+  check(laser_hip_exp_f32_dev(dst.unsafe_raw_data(), dst.strides.data(), src.unsafe_raw_data(), ss.data(), dst.shape.data(), r, stream));
+}
+inline Tensor<float> exp_result_like(const Tensor<float> &src) {  // fresh row-major storage of src's shape
+  Tensor<float> t;
+  t.shape = src.shape;
+  t.strides.resize(src.shape.size());
+  int64_t size = 1;
+  for (int i = t.rank() - 1; i >= 0; i--) {
+    t.strides[i] = size;
+    size *= t.shape[i];
+  }
+  t.storage = std::make_shared<HipStorage<float>>(size);
+  return t;
+}
+inline Tensor<float> exp(const Tensor<float> &src, void *stream = nullptr) {
+  Tensor<float> dst = exp_result_like(src);
+  exp(dst, src, stream);
+  return dst;
+}
+inline void softmax(Tensor<float> &dst, const Tensor<float> &src, void *stream = nullptr) {
+  if (src.rank() != 2 || dst.shape != src.shape) throw Error(LASER_HIP_E_INVALID, "softmax: two 2-D tensors of one shape");
+  if (src.shape[1] < 1 || (src.shape[1] != 1 && (src.strides[1] != 1 || dst.strides[1] != 1)))
+    throw Error(LASER_HIP_E_INVALID, "softmax: the elements of a row must be contiguous");
+  const int64_t rows = src.shape[0], n = src.shape[1];
+  check(laser_hip_softmax_rows_f32_dev(dst.unsafe_raw_data(), rows > 1 ? dst.strides[0] : n, src.unsafe_raw_data(),
+                                       rows > 1 ? src.strides[0] : n, rows, n, stream));
+}
+inline Tensor<float> softmax(const Tensor<float> &src, void *stream = nullptr) {
+  Tensor<float> dst = exp_result_like(src);
+  softmax(dst, src, stream);
+  return dst;
+}
+
 #undef LASER_DISPATCH
 #undef LASER_GEMM_DISPATCH
 }  // namespace laser

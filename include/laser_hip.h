@@ -585,6 +585,47 @@ int laser_hip_reduce_sum_f32(const float *data, int64_t len, float *out);
 int laser_hip_reduce_min_f32(const float *data, int64_t len, float *out);
 int laser_hip_reduce_max_f32(const float *data, int64_t len, float *out);
 
+/* ---- exp and row softmax (f32): laser/primitives/simd_math/exp_log_{sse2,avx2,avx512}.nim --------------------------
+ * lexp(x) is Laser's table-driven exp, bit for bit the exported SIMD `exp*` (not the unexported scalar fallback, which
+ * truncates where the SIMD forms round).  One definition, laser_amd/csrc/exp_core.h, shared by every kernel below and by
+ * the forEach bodies.  For a float32 x, every operation rounded to float32 on its own (no fused multiply-add anywhere):
+ *   1. NaN gives NaN (payload unspecified; the one deviation: x86 minps turns NaN into 88).  c = max(min(x, 88), -88);
+ *      +-Inf clamp like any other value.
+ *   2. r = int32(round-to-nearest-even(c * ExpA)),  ExpA = bits 0x44b8aa3b = float32(1024 / ln 2).
+ *   3. t = (c - float(r) * ExpB) + 1,  ExpB = bits 0x3a317218 = float32(ln 2 / 1024): a multiply, a subtract, an add.
+ *   4. v = r & 1023;  u = ((r + (127 << 10)) >> 10) << 23  (r + (127 << 10) is never negative).
+ *   5. lexp(x) = t * bitcast<float>(LUT[v] | u), one multiply.  LUT[i] = the low 23 bits of the correctly rounded float32
+ *      of 2^(i/1024), i = 0..1023 (as little-endian uint32 words the table has CRC-32 0x0c4cd4ff).
+ * For x below about -87.3369 the exponent field u is 0, the second factor is subnormal and the product is not an
+ * exponential any more -- exactly as in Laser; no denormal is flushed.  Relative error elsewhere: about 1e-6 on [-30, 0],
+ * 4e-6 on [-87, 88].
+ * laser_hip_exp_f32_dev: dst[idx] = lexp(src[idx]) for every index of `shape`; rank <= 6, ELEMENT strides, negative
+ *   strides allowed, stride 0 (broadcast) on src only, dst == src with equal strides allowed (any other overlap is not).
+ *   Asynchronous on `stream`.  C-contiguous and 16-byte aligned on both sides: one 16-byte vector per lane and step.
+ * laser_hip_exp_f32: host pointers, `len` contiguous elements, synchronous (the reference's benchmark loop).
+ * laser_exp(x) is callable in forEach / forEachReduce bodies: the prelude of their generated source embeds exp_core.h
+ *   (laser_hip_foreach_source shows it).  The name is reserved like the lh_ names.
+ * laser_hip_softmax_rows_f32_dev: for each of `rows` rows x[0..n) at d_src + row * src_row_stride (elements of a row
+ *   contiguous, row strides in elements and >= n):
+ *   1. m = the maximum of the row under the rule of reduce_max ("Reductions": any NaN gives NaN).
+ *   2. e[j] = lexp(x[j] - m), one rounded subtract.
+ *   3. s = the sum of e[0..n) in the order of "Reductions" applied to the row as a 1-D array of n float32 (E = 4,
+ *      init +0): s is reduce_sum of e.
+ *   4. y[j] = e[j] / s, a correctly rounded division; y goes to d_dst + row * dst_row_stride.
+ *   So a row's result is a function of its values and n alone, never of rows, the strides, the base alignment, the
+ *   grid or the stream.  A NaN in a row makes the whole output row NaN; so does a row of all -Inf (x - m = NaN) and a
+ *   row whose maximum is +Inf.  1 <= n <= 2^26, rows >= 0 (rows = 0: nothing happens), any base alignment, dst == src
+ *   with equal row strides allowed; anything else LASER_HIP_E_INVALID.  Asynchronous on `stream`.
+ *   get_option "last_softmax_kernel": 0 = one wave per row (n <= 1024), 1 = one workgroup per row (n <= 8192), 2 = long
+ *   rows; + 4 when a base or a row stride is off its 16-byte alignment (single-element accesses) -- same bits all six.
+ * No gfx950 device: LASER_HIP_E_NODEVICE. */
+#define LASER_HIP_SOFTMAX_MAX_N (1ll << 26)
+int laser_hip_exp_f32_dev(float *d_dst, const int64_t *dst_strides, const float *d_src, const int64_t *src_strides,
+                          const int64_t *shape, int rank, void *stream);
+int laser_hip_exp_f32(float *dst, const float *src, int64_t len);
+int laser_hip_softmax_rows_f32_dev(float *d_dst, int64_t dst_row_stride, const float *d_src, int64_t src_row_stride,
+                                   int64_t rows, int64_t n, void *stream);
+
 /* ---- forEachReduce: forEach with a private accumulator per lane, merged at the end ---------------------------------
  * The device form of forEachStaged (laser/strided_iteration/foreach_staged.nim:318), e.g. a dot product:
  *   forEachReduce acc (f64) in x, y:  body "acc += x * y",  merge "acc += other",  init 0

@@ -1528,6 +1528,7 @@ int laser_hip_get_option(const char *name, int64_t *value) {
   else if (n == "foreach_compiles") *value = api_foreach_compiles();
   else if (n == "last_foreach_variant") *value = api_last_foreach_variant();
   else if (n == "last_reduce_variant") *value = g_last_reduce_variant;
+  else if (n == "last_softmax_kernel") *value = g_last_softmax_kernel;
   else if (n == "conv_implicit") *value = g_ctx.conv_implicit;
   else if (n == "conv_patch") *value = g_conv_patch;
   else if (n == "conv_direct") *value = g_conv_direct;
@@ -2126,6 +2127,53 @@ LH_DEF_REDUCE(i64, int64_t)
 int laser_hip_reduce_sum_f32(const float *data, int64_t len, float *out) { return reduce_host_f32(0, data, len, out); }
 int laser_hip_reduce_min_f32(const float *data, int64_t len, float *out) { return reduce_host_f32(1, data, len, out); }
 int laser_hip_reduce_max_f32(const float *data, int64_t len, float *out) { return reduce_host_f32(2, data, len, out); }
+
+// ---- lexp and the row softmax: laser/primitives/simd_math/exp_log_*.nim (exp_core.h, exp_softmax.hip) -----------------
+int laser_hip_exp_f32_dev(float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
+                          void *stream) {
+  if (rank < 0 || rank > kMaxRank) return fail(LASER_HIP_E_INVALID, "exp: rank %d outside 0..%d (LASER_MAXRANK)", rank, kMaxRank);
+  if (rank > 0 && (!ds || !ss || !shape)) return fail(LASER_HIP_E_INVALID, "exp: null shape / strides");
+  int64_t total = 1;
+  for (int d = 0; d < rank; d++) {
+    if (shape[d] < 0) return fail(LASER_HIP_E_INVALID, "exp: negative extent");
+    if (shape[d] > 1 && ds[d] == 0) return fail(LASER_HIP_E_INVALID, "exp: stride 0 on the destination (dimension %d)", d);
+    total *= shape[d];
+  }
+  if (int rc = ensure_init()) return rc;
+  if (total == 0) return LASER_HIP_OK;
+  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "exp: null buffer");
+  HIP_TRY(launch_exp_f32(dst, ds, src, ss, shape, rank, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+// the host-pointer form: through device scratch, in place there, synchronous; the same kernel as the _dev form
+int laser_hip_exp_f32(float *dst, const float *src, int64_t len) {
+  if (len < 0 || (len > 0 && (!dst || !src))) return fail(LASER_HIP_E_INVALID, "exp: bad argument");
+  if (int rc = ensure_init()) return rc;
+  if (len == 0) return LASER_HIP_OK;
+  HostCall hc;
+  if (hc.rc) return hc.rc;
+  void *d_buf;
+  if (int rc = scratch_get(0, (size_t)len * sizeof(float), &d_buf)) return rc;
+  HIP_TRY(hipMemcpy(d_buf, src, (size_t)len * sizeof(float), hipMemcpyHostToDevice));
+  const int64_t stride = 1;
+  HIP_TRY(launch_exp_f32((float *)d_buf, &stride, (const float *)d_buf, &stride, &len, 1, nullptr));
+  HIP_TRY(hipMemcpy(dst, d_buf, (size_t)len * sizeof(float), hipMemcpyDeviceToHost));
+  return LASER_HIP_OK;
+}
+int laser_hip_softmax_rows_f32_dev(float *dst, int64_t dst_row_stride, const float *src, int64_t src_row_stride, int64_t rows,
+                                   int64_t n, void *stream) {
+  if (n < 1 || n > LASER_HIP_SOFTMAX_MAX_N) return fail(LASER_HIP_E_INVALID, "softmax: row length %lld outside 1..2^26", (long long)n);
+  if (rows < 0) return fail(LASER_HIP_E_INVALID, "softmax: negative row count");
+  if (dst_row_stride < n || src_row_stride < n)
+    return fail(LASER_HIP_E_INVALID, "softmax: row strides %lld / %lld below the row length %lld", (long long)dst_row_stride,
+                (long long)src_row_stride, (long long)n);
+  if (dst == src && dst_row_stride != src_row_stride) return fail(LASER_HIP_E_INVALID, "softmax: in place needs equal row strides");
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0) return LASER_HIP_OK;
+  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "softmax: null buffer");
+  HIP_TRY(launch_softmax_rows_f32(dst, dst_row_stride, src, src_row_stride, rows, n, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
 
 // ---- pinned host memory for the host-pointer entry points -----------------------------------------------------------
 // Laser leaves buffer management to the caller ("creating or reusing buffers is left at the discretion of the

@@ -284,6 +284,12 @@ typedef std::function<hipError_t(int64_t blocks, void *dst)> ReduceLevel0;
 typedef std::function<hipError_t(const void *in, int64_t count, int64_t blocks, void *dst)> ReducePartials;
 hipError_t reduce_levels(int64_t n, int e0, int acc_size, void *out, hipStream_t s, const ReduceLevel0 &level0,
                          const ReducePartials &partials);
+// lexp over strided views and the deterministic row softmax (exp_softmax.hip; exp_core.h is the definition of lexp)
+hipError_t launch_exp_f32(float *dst, const int64_t *dstrides, const float *src, const int64_t *sstrides, const int64_t *shape,
+                          int rank, hipStream_t s);
+hipError_t launch_softmax_rows_f32(float *dst, int64_t dstride, const float *src, int64_t sstride, int64_t rows, int64_t n,
+                                   hipStream_t s);
+extern std::atomic<int> g_last_softmax_kernel;  // 0 wave per row, 1 workgroup per row, 2 long rows; + 4: the scalar-access instance
 template <typename T>
 hipError_t launch_pack_pad(T *dst, int64_t Rpad, int64_t Cpad, const T *src, int64_t R,
                            int64_t Ccols, int64_t rs, int64_t cs, hipStream_t s, int relu = 0);

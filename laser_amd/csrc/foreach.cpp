@@ -8,7 +8,7 @@
 // template's three kernels (contiguous vectorised / contiguous scalar / strided) and launches it.
 //
 // forEachReduce (laser_hip_foreach_reduce_*) is the same machinery with an accumulator: its spec adds the accumulator's
-// name and type and a merge statement, its source is forEach's prelude + reduce_core.h + the spec + the kernels of
+// name and type and a merge statement, its source is forEach's prelude + exp_core.h + reduce_core.h + the spec + the kernels of
 // foreach_reduce_kernel.hip.in, and laser_hip_foreach_reduce_dev runs the levels of reduce_levels (reduce.hip).  Its
 // modules are cached under keys of their own and counted in foreach_compiles.
 #include <dlfcn.h>
@@ -27,8 +27,8 @@
 #include "../../include/laser_hip.h"
 #include "capi_internal.h"
 #include "common.h"
-#include "foreach_template.h"  // generated from foreach_kernel.hip.in, foreach_reduce_kernel.hip.in and reduce_core.h:
-                                // lh_foreach_template, lh_foreach_reduce_template, lh_reduce_core
+#include "foreach_template.h"  // generated from foreach_kernel.hip.in, foreach_reduce_kernel.hip.in, reduce_core.h and
+                                // exp_core.h: lh_foreach_template, lh_foreach_reduce_template, lh_reduce_core, lh_exp_core
 
 using namespace laser_hip;
 
@@ -94,6 +94,7 @@ int check_name(const char *what, int i, const char *name) {
   if (is_keyword(s)) return api_fail(LASER_HIP_E_INVALID, "foreach: %s name '%s' is a C++ keyword", what, name);
   if (s.rfind("lh_", 0) == 0 || s.rfind("__", 0) == 0)
     return api_fail(LASER_HIP_E_INVALID, "foreach: %s name '%s' is reserved (lh_ and __ prefixes)", what, name);
+  if (s == "laser_exp") return api_fail(LASER_HIP_E_INVALID, "foreach: %s name 'laser_exp' is reserved (exp_core.h)", what);
   return LASER_HIP_OK;
 }
 
@@ -187,8 +188,9 @@ std::string generate(const Spec &sp) {
          sp.merge + "\n;\n}\n";
   const std::string tpl = lh_foreach_template, mark = "\n@LH_SPEC@\n";
   const size_t at = tpl.find(mark) + 1;
-  // forEachReduce: forEach's prelude, then the order (reduce_core.h), then the spec, then the reduce kernels
-  const std::string head = tpl.substr(0, at) + (sp.reduce ? std::string(lh_reduce_core) : std::string());
+  // forEach's prelude, then lexp (exp_core.h: laser_exp for the bodies); forEachReduce: then the order (reduce_core.h); then
+  // the spec and the kernels
+  const std::string head = tpl.substr(0, at) + lh_exp_core + (sp.reduce ? std::string(lh_reduce_core) : std::string());
   // the lines after the body report their line in the generated source again
   const size_t line = std::count(head.begin(), head.end(), '\n') + std::count(s.begin(), s.end(), '\n') + 2;
   s += "#line " + std::to_string(line) + (sp.reduce ? " \"foreach_reduce.hip\"\n" : " \"foreach.hip\"\n");

@@ -635,6 +635,21 @@ proc reduce_max*(data: ptr (float32 or UncheckedArray[float32]), len: Natural): 
   ## reductions.nim:105-110 (-Inf when len = 0)
   check laser_hip_reduce_max_f32(cast[ptr float32](data), int64(len), result.addr)
 
+# ---- exp and row softmax (include/laser_hip.h "exp and row softmax"): simd_math/exp_log_*.nim ---------------------------
+# exp is Laser's table-driven exp, bit for bit the exported SIMD forms; softmax sums in the fixed order of the reductions.
+proc laser_hip_exp_f32(dst: ptr float32, src: ptr float32, len: int64): cint {.lh, importc: "laser_hip_exp_f32".}
+# device views (asynchronous on `stream`): element strides, rank <= 6; dst may be src
+proc laser_hip_exp_f32_dev*(dst: ptr float32, dstStrides: ptr int64, src: ptr float32, srcStrides: ptr int64, shape: ptr int64, rank: cint, stream: pointer): cint {.lh, importc: "laser_hip_exp_f32_dev".}
+proc laser_hip_softmax_rows_f32_dev*(dst: ptr float32, dstRowStride: int64, src: ptr float32, srcRowStride: int64, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_softmax_rows_f32_dev".}
+
+proc exp*(dst, src: ptr (float32 or UncheckedArray[float32]), len: Natural) =
+  ## exp_log_avx2.nim:49-65 over a contiguous range of float32 (host memory; the GPU computes it): dst[i] = exp(src[i])
+  check laser_hip_exp_f32(cast[ptr float32](dst), cast[ptr float32](src), int64(len))
+
+proc softmax*(dst: DevicePtr[float32], dstRowStride: int, src: DevicePtr[float32], srcRowStride: int, rows, n: Natural, stream: pointer = nil) =
+  ## softmax over the rows of a device matrix (row elements contiguous, row strides in elements); dst may be src
+  check laser_hip_softmax_rows_f32_dev(cast[ptr float32](dst), int64(dstRowStride), cast[ptr float32](src), int64(srcRowStride), int64(rows), int64(n), stream)
+
 # ---- forEachReduce (include/laser_hip.h "forEachReduce"): foreach_staged.nim:318 on device buffers ------------------------
 proc laser_hip_foreach_reduce_source(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, accName: cstring, accDtype: cint, merge: cstring, buf: pointer, cap: int64, len: ptr int64): cint {.lh, importc: "laser_hip_foreach_reduce_source".}
 proc laser_hip_foreach_reduce_code(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, accName: cstring, accDtype: cint, merge: cstring, arch: cstring, buf: pointer, cap: int64, len: ptr int64): cint {.lh, importc: "laser_hip_foreach_reduce_code".}
