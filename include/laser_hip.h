@@ -164,7 +164,9 @@ int laser_hip_f32_config_count(void);
  *   "foreach_compiles" hiprtc compiles of forEach and forEachReduce bodies made by this process
  *   "last_foreach_variant"  kernel of the last laser_hip_foreach_dev / foreach_reduce_dev launch: 0 contiguous vectorised, 1 contiguous
  *                      scalar, 2 strided
- *   "last_reduce_variant"  traversal of the last laser_hip_reduce_* call: 0 contiguous vectorised, 1 contiguous scalar, 2 strided */
+ *   "last_reduce_variant"  traversal of the last laser_hip_reduce_* call: 0 contiguous vectorised, 1 contiguous scalar, 2 strided
+ *   "last_softmax_kernel"  kernel of the last laser_hip_softmax_rows_f32_dev call (see the softmax section below)
+ *   "shard_rccl_ranks" ranks of the RCCL communicator the last GATHER_RCCL sharded call used, as the communicator reports it; 0 = none yet */
 int laser_hip_set_option(const char *name, int value);
 int laser_hip_get_option(const char *name, int64_t *value);
 const char *laser_hip_f32_config_name(int cfg);

@@ -5,8 +5,6 @@
 // path that benchmarks and multi-GPU code use.  No CPU compute fallback exists anywhere in this
 // library: without a usable gfx950 device every compute entry point returns LASER_HIP_E_NODEVICE.
 #include <hip/hip_runtime.h>
-#include <pthread.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <cstdarg>
@@ -23,16 +21,14 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/laser_hip.h"
 #include "capi_internal.h"
-#include "common.h"
 
 using namespace laser_hip;
 
-namespace {
-
-thread_local std::string g_err;
-std::mutex g_mu;  // guards initialisation and the registries (pre-pack handles, storage free list, host-range registry)
+namespace laser_hip {
+std::mutex g_mu;
+Context g_ctx;
+static thread_local std::string g_err;
 
 int fail(int code, const char *fmt, ...) {
   char buf[512];
@@ -43,45 +39,15 @@ int fail(int code, const char *fmt, ...) {
   g_err = buf;
   return code;
 }
-
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      const char *why_ = asm_error_detail();                                                  \
-      return fail(LASER_HIP_E_HIP, "%s failed: %s%s%s (%s:%d)", #expr, hipGetErrorString(e_), \
-                  why_[0] ? ": " : "", why_, __FILE__, __LINE__);                             \
-    }                                                                                         \
-  } while (0)
-
-struct Context {
-  std::atomic<bool> ready{false};  // read lock-free on every call, written once under g_mu
-  int device = -1;
-  std::string arch;
-  // run-time knobs: set by one thread, read by every call on every thread -> relaxed atomics (a knob flipped while a
-  // call is in flight applies to that call or the next, never tears)
-  std::atomic<int> float_mode{LASER_HIP_F32_LASER_ORDER};
-  std::atomic<int> f32_cfg{-1};
-  std::atomic<bool> f64_mfma{true};       // float64 GEMM on the f64 matrix cores (false: VALU kernel)
-  std::atomic<bool> i32_mfma{true};       // int32 GEMM on the int8 matrix cores (false: VALU kernel)
-  std::atomic<bool> i64_mfma{true};       // int64 GEMM on the int8 matrix cores (false: VALU kernel)
-  std::atomic<bool> narrow_mfma{true};    // int8 / int16 GEMM on the int8 matrix cores (false: VALU / skinny kernels)
-  std::atomic<bool> zc_poll{true};           // small host-pointer calls: poll completion flags in mapped memory (false: synchronise the stream)
-  std::atomic<bool> host_pipeline_2d{true};  // large row-major host-pointer calls: row panels x column panels (false: row panels only)
-  std::atomic<int> slice_parallel_min{2};        // (tuning override only) fewest kc slices worth splitting
-  std::atomic<int64_t> slice_parallel_tiles{0};  // tuning override of the tile-count limit of the slice-parallel form (0 = built-in rule)
-  std::atomic<bool> slice_parallel{true}; // few tiles x long K: kc slices as one batched launch + ordered combine
-  std::atomic<bool> skinny{true};         // M <= 8 or N <= 8: the streaming kernel (false: always the tiled kernels)
-  std::atomic<bool> conv_implicit{true};  // fuse im2col into the GEMM's B loader (false: explicit workspace)
-  std::atomic<int> shard_devices{1};      // host-pointer gemm_strided: row panels over this many GPUs (1 = off; laser_hip_set_shard_devices)
-};
-Context g_ctx;
+int fail_text(int code, const std::string &text) {
+  g_err = text;
+  return code;
+}
 
 // Per-DEVICE state of the host-pointer paths: cached scratch (one growing buffer per role), the streams of the
 // upload / compute / download pipeline, and a mutex that serialises the host-pointer calls using THIS device.  One
 // process may drive every GPU of the node (the sharded entry points run one host thread per device), so none of this
 // is per process.
-constexpr int kMaxDevices = 16;
 struct DeviceCtx {
   int device = -1;
   std::mutex mu;
@@ -92,12 +58,13 @@ struct DeviceCtx {
   void *zc = nullptr;  // pinned host buffer mapped into the device: zero-copy staging of the small-problem host path
   size_t zc_sz = 0;
 };
+namespace {
+constexpr int kMaxDevices = 16;
 DeviceCtx g_dev[kMaxDevices];
 // The device a host-pointer call on this thread uses: -1 = the library's default device (laser_hip_init); the
 // sharded entry points set it in their per-device worker threads.
 thread_local int tl_device = -1;
 thread_local int tl_f32_cfg = -2;  // per-thread override of g_ctx.f32_cfg (-2 = none), api_set_thread_f32_config
-inline int f32_cfg_now() { return tl_f32_cfg >= -1 ? tl_f32_cfg : g_ctx.f32_cfg.load(); }
 thread_local DeviceCtx *tl_dev = nullptr;  // valid while a HostCall guard is alive
 
 int ensure_init_locked(int device) {
@@ -127,6 +94,13 @@ int ensure_init_locked(int device) {
   g_ctx.ready = true;
   return LASER_HIP_OK;
 }
+}  // namespace
+
+int f32_cfg_now() { return tl_f32_cfg >= -1 ? tl_f32_cfg : g_ctx.f32_cfg.load(); }
+void api_set_thread_device(int device) { tl_device = device; }
+void api_set_thread_f32_config(int cfg) { tl_f32_cfg = cfg; }
+void api_set_thread_asm_tile(int tile_class) { asm_set_thread_tile(tile_class); }
+int api_thread_device() { return tl_device; }
 
 int ensure_init() {
   if (g_ctx.ready) return LASER_HIP_OK;
@@ -134,43 +108,31 @@ int ensure_init() {
   return ensure_init_locked(-1);
 }
 
-// RAII guard of a host-pointer entry point: makes its device current for the calling thread (another host thread
-// using the host-pointer API would otherwise run on device 0 with this device's buffers), serialises on that device's
-// mutex and publishes its DeviceCtx in tl_dev.
-struct HostCall {
-  int rc = LASER_HIP_OK;
-  DeviceCtx *d = nullptr;
-  DeviceCtx *prev = nullptr;
-  int caller_dev = -1;  // the caller's current device, restored on exit: an application thread driving another GPU must
-                        // not find itself on the library's device after a host-pointer call
-  HostCall() {
-    if (hipGetDevice(&caller_dev) != hipSuccess) caller_dev = -1;
-    const int dev = tl_device >= 0 ? tl_device : g_ctx.device;
-    if (dev < 0 || dev >= kMaxDevices) {
-      rc = fail(LASER_HIP_E_INVALID, "device %d outside 0..%d", dev, kMaxDevices - 1);
-      return;
-    }
-    const hipError_t e = hipSetDevice(dev);
-    if (e != hipSuccess) {
-      rc = fail(LASER_HIP_E_HIP, "hipSetDevice(%d): %s", dev, hipGetErrorString(e));
-      return;
-    }
-    d = &g_dev[dev];
-    d->mu.lock();
-    d->device = dev;
-    prev = tl_dev;
-    tl_dev = d;
+HostCall::HostCall() {
+  if (hipGetDevice(&caller_dev) != hipSuccess) caller_dev = -1;
+  const int dev = tl_device >= 0 ? tl_device : g_ctx.device;
+  if (dev < 0 || dev >= kMaxDevices) {
+    rc = fail(LASER_HIP_E_INVALID, "device %d outside 0..%d", dev, kMaxDevices - 1);
+    return;
   }
-  ~HostCall() {
-    if (d) {
-      tl_dev = prev;
-      d->mu.unlock();
-    }
-    if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
+  const hipError_t e = hipSetDevice(dev);
+  if (e != hipSuccess) {
+    rc = fail(LASER_HIP_E_HIP, "hipSetDevice(%d): %s", dev, hipGetErrorString(e));
+    return;
   }
-  HostCall(const HostCall &) = delete;
-  HostCall &operator=(const HostCall &) = delete;
-};
+  d = &g_dev[dev];
+  d->mu.lock();
+  d->device = dev;
+  prev = tl_dev;
+  tl_dev = d;
+}
+HostCall::~HostCall() {
+  if (d) {
+    tl_dev = prev;
+    d->mu.unlock();
+  }
+  if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
+}
 
 int scratch_get(int slot, size_t bytes, void **out) {
   DeviceCtx &D = *tl_dev;
@@ -186,6 +148,9 @@ int scratch_get(int slot, size_t bytes, void **out) {
   *out = D.scratch[slot];
   return LASER_HIP_OK;
 }
+}  // namespace laser_hip
+
+namespace {
 
 // Pinned, device-mapped host staging for small host-pointer problems (<= kZeroCopyMax bytes of operands): the kernel
 // reads A and B from it and writes C into it across PCIe -- one round trip, because the small-matrix kernel issues all
@@ -216,343 +181,6 @@ int pipeline_streams() {
   return LASER_HIP_OK;
 }
 
-// Lowest / highest element offset touched by an R x C strided view (strides may be negative).
-void view_span(int64_t R, int64_t C, int64_t rs, int64_t cs, int64_t *lo, int64_t *hi) {
-  const int64_t r = (R - 1) * rs, c = (C - 1) * cs;
-  *lo = std::min<int64_t>(0, r) + std::min<int64_t>(0, c);
-  *hi = std::max<int64_t>(0, r) + std::max<int64_t>(0, c);
-}
-
-hipError_t launch_tiled(const GemmArgs<float> &a, hipStream_t s) {
-  if (f32_cfg_now() < 0) {   // (batched: the hand-scheduled kernels take the batch index as grid y)
-    const hipError_t e = launch_gemm_f32_asm(a, g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, s);
-    if (e != hipErrorNotSupported) return e;
-  }
-  return launch_gemm_f32(a, f32_cfg_now(), g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, s);
-}
-hipError_t launch_tiled(const GemmArgs<double> &a, hipStream_t s) {
-  if (g_ctx.f64_mfma) {
-    const hipError_t e = launch_gemm_f64_asm(a, g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, s);
-    if (e != hipErrorNotSupported) return e;
-  }
-  return launch_gemm_f64(a, g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, s);
-}
-
-// Slice-parallel GEMM for problems with few output tiles and a long K (tall-skinny products, small M x N with a huge
-// K): Laser's kc slices are independent chains from +0 -- only their sums are added in order (gemm.nim:150-158) -- so
-// the slices are computed as ONE batched launch (batch = slice, K = kc, each a single-chain product into a workspace
-// W[p][M][N]) and folded by an ordered combine pass.  Same fused multiply-adds in the same order, same unfused
-// alpha / beta arithmetic => bit-identical to the sequential kernel, with ceil(K / kc) times the workgroups.
-// Returns hipErrorNotSupported when the shape does not call for it.
-template <typename T>
-hipError_t gemm_slice_parallel(const GemmArgs<T> &a, int kc, hipStream_t s) {
-  if (!g_ctx.slice_parallel || a.batch != 1 || a.bias != nullptr || a.act != 0) return hipErrorNotSupported;
-  if (a.M <= 0 || a.N <= 0 || a.K <= kc) return hipErrorNotSupported;
-  const int64_t tiles64 = ((a.M + 63) / 64) * ((a.N + 63) / 64);
-  const int64_t nfull = a.K / kc, nsl = (a.K + kc - 1) / kc;
-  const double ws_bytes = (double)nsl * (double)a.M * (double)a.N * sizeof(T);
-  // measured boundary (scripts/slice_parallel_threshold_probe.py, slice_parallel_min_probe.py): the fewer the tiles the
-  // fewer slices it takes to pay -- up to ~150 tiles of 64x64 from two slices on (768^2 x 1536: +20 %), up to ~400 from
-  // five (1280^2 x 2560: +17 %; 1024^2 x 2048 with four: -3 %), up to ~600 from six (1536^2 x 6144: +24 %); from ~1000
-  // tiles on the sequential loop wins (2048^3: -14 %)
-  int64_t need = tiles64 <= 150 ? 2 : tiles64 <= 400 ? 5 : tiles64 <= 600 ? 6 : (int64_t)1 << 40;
-  if (a.K % kc != 0 && need < 3) need = 3;  // a ragged last slice is a launch of its own: 768^3 (512 + 256) loses
-  if (g_ctx.slice_parallel_tiles > 0) need = tiles64 <= g_ctx.slice_parallel_tiles.load() ? (int64_t)g_ctx.slice_parallel_min.load() : (int64_t)1 << 40;  // tuning override
-  if (nsl < need || nsl > 65535 || ws_bytes > 1.5e9) return hipErrorNotSupported;
-  T *W = nullptr;
-  hipError_t e = scratch_alloc_async((void **)&W, (size_t)ws_bytes, s);
-  if (e != hipSuccess) return e;
-  const int64_t mn = a.M * a.N;
-  GemmArgs<T> b = a;
-  b.alpha = (T)1; b.beta = (T)0;
-  b.C = W; b.rsC = a.N; b.csC = 1; b.bsC = mn;
-  b.K = kc; b.Kext = kc;
-  b.batch = (int32_t)nfull;
-  b.bsA = (int64_t)kc * a.csA;  // slice p starts kc columns of A / rows of B further on
-  b.bsB = (int64_t)kc * a.rsB;
-  e = launch_tiled(b, s);
-  if (e == hipSuccess && nsl > nfull) {  // the ragged last slice
-    GemmArgs<T> c = b;
-    c.batch = 1;
-    c.K = a.K - nfull * kc; c.Kext = c.K;
-    c.A = a.A + nfull * b.bsA;
-    c.B = a.B + nfull * b.bsB;
-    c.C = W + nfull * mn;
-    e = launch_tiled(c, s);
-  }
-  if (e == hipSuccess) e = launch_combine_slices<T>(a.C, a.rsC, a.csC, W, a.M, a.N, (int)nsl, a.alpha, a.beta, s);
-  const hipError_t e2 = hipFreeAsync(W, s);
-  return e != hipSuccess ? e : e2;
-}
-
-template <typename T>
-hipError_t run_gemm(const GemmArgs<T> &a, hipStream_t s);
-template <typename T>
-hipError_t run_gemm_core(const GemmArgs<T> &a, hipStream_t s);
-template <>
-hipError_t run_gemm_core<float>(const GemmArgs<float> &a, hipStream_t s);
-template <>
-hipError_t run_gemm_core<double>(const GemmArgs<double> &a, hipStream_t s);
-
-// Ragged-by-a-few problems (4100^3, 4095 x 4097 x 4099): 1..8 rows / columns past a multiple of 64 cost a whole extra row /
-// column of tiles (4100 = 16 x 256 + 4: 17 tile rows for 16.02 tile rows of work).  Elements of C are independent and the
-// streaming kernel for M <= 8 or N <= 8 (gemm_skinny.hip) runs the same k-ascending, kc-sliced chain per element as the tiled
-// kernels, so those few rows / columns are peeled off and streamed (HBM-bound, ~20 us each at 4100^3), and the tiled
-// launch sees whole tiles: bit-identical to the single launch.  Laser-order arithmetic only (the streaming kernel always
-// restarts its chain every kc), i.e. laser-order mode or K <= kc; plain (unfused, unbatched, not pre-packed) problems.
-template <typename T>
-hipError_t run_gemm_peeled(const GemmArgs<T> &a, int kc, bool laser, bool *taken, hipStream_t s) {
-  *taken = false;
-  if (!g_ctx.skinny || !g_split_tail || a.batch != 1 || a.bias != nullptr || a.act != 0) return hipSuccess;
-  if (!(laser || a.K <= kc) || a.Mext != a.M || a.Next != a.N || a.K < 256) return hipSuccess;
-  const int64_t rM = a.M % 64, rN = a.N % 64;
-  const bool peel_m = rM >= 1 && rM <= 8 && a.M >= 1024 && a.N >= 512;
-  const bool peel_n = rN >= 1 && rN <= 8 && a.N >= 1024 && a.M - (peel_m ? rM : 0) >= 512;
-  if (!peel_m && !peel_n) return hipSuccess;
-  *taken = true;
-  const int64_t M1 = peel_m ? a.M - rM : a.M, N1 = peel_n ? a.N - rN : a.N;
-  GemmArgs<T> m = a;  // whole tiles
-  m.M = M1; m.Mext = M1; m.N = N1; m.Next = N1;
-  hipError_t e = run_gemm_core<T>(m, s);
-  if (e == hipSuccess && peel_n) {  // columns [N1, N) of rows [0, M1)
-    GemmArgs<T> r = a;
-    r.M = M1; r.Mext = M1; r.N = rN; r.Next = rN;
-    r.B = a.B + N1 * a.csB;
-    r.C = a.C + N1 * a.csC;
-    e = launch_gemm_skinny<T>(r, true, kc, s);
-  }
-  if (e == hipSuccess && peel_m) {  // rows [M1, M), every column
-    GemmArgs<T> b = a;
-    b.M = rM; b.Mext = rM;
-    b.A = a.A + M1 * a.rsA;
-    b.C = a.C + M1 * a.rsC;
-    e = launch_gemm_skinny<T>(b, true, kc, s);
-  }
-  return e == hipErrorNotSupported ? hipErrorInvalidValue : e;
-}
-
-// Fused prologue on a path that has no kernel for it: the operand is materialised once (relu applied while it is copied into a
-// dense row-major scratch matrix -- "during the prepacking", README.md:243-244) and the plain problem runs on it.
-template <typename T>
-hipError_t run_gemm_prologue_materialised(const GemmArgs<T> &a, hipStream_t s) {
-  if (a.batch != 1 || a.Mext != a.M || a.Next != a.N || a.Kext != a.K) return hipErrorInvalidValue;
-  const size_t nA = a.preA ? (size_t)a.M * a.K : 0, nB = a.preB ? (size_t)a.K * a.N : 0;
-  if (nA + nB == 0) return hipErrorInvalidValue;
-  T *scratch = nullptr;
-  hipError_t e = scratch_alloc_async((void **)&scratch, (nA + nB) * sizeof(T), s);
-  if (e != hipSuccess) return e;
-  GemmArgs<T> b = a;
-  b.preA = b.preB = 0;
-  if (a.preA) {
-    e = launch_pack_pad<T>(scratch, a.M, a.K, a.A, a.M, a.K, a.rsA, a.csA, s, 1);
-    b.A = scratch; b.rsA = a.K; b.csA = 1;
-  }
-  if (e == hipSuccess && a.preB) {
-    e = launch_pack_pad<T>(scratch + nA, a.K, a.N, a.B, a.K, a.N, a.rsB, a.csB, s, 1);
-    b.B = scratch + nA; b.rsB = a.N; b.csB = 1;
-  }
-  if (e == hipSuccess) e = run_gemm<T>(b, s);
-  const hipError_t e2 = hipFreeAsync(scratch, s);
-  return e != hipSuccess ? e : e2;
-}
-
-template <>
-hipError_t run_gemm<float>(const GemmArgs<float> &a, hipStream_t s) {
-  if (a.preA || a.preB) {      // the `_pre` assembly kernels (relu in the staging registers), else one materialising pass
-    if (f32_cfg_now() < 0) {
-      const hipError_t e = launch_gemm_f32_asm(a, g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, s);
-      if (e != hipErrorNotSupported) return e;
-    }
-    g_last_f32_asm = 0;
-    return run_gemm_prologue_materialised<float>(a, s);
-  }
-  if (f32_cfg_now() < 0) {
-    bool taken;
-    const hipError_t e = run_gemm_peeled<float>(a, 512, g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, &taken, s);
-    if (taken) return e;
-  }
-  return run_gemm_core<float>(a, s);
-}
-template <>
-hipError_t run_gemm<double>(const GemmArgs<double> &a, hipStream_t s) {
-  if (a.preA || a.preB) return run_gemm_prologue_materialised<double>(a, s);
-  if (g_ctx.f64_mfma) {
-    bool taken;
-    const hipError_t e = run_gemm_peeled<double>(a, 256, g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, &taken, s);
-    if (taken) return e;
-  }
-  return run_gemm_core<double>(a, s);
-}
-template <>
-hipError_t run_gemm_core<float>(const GemmArgs<float> &a, hipStream_t s) {
-  if (f32_cfg_now() < 0 && g_ctx.skinny) {  // matrix-vector-like shapes: an HBM stream, not a tile problem
-    const hipError_t e = launch_gemm_skinny<float>(a, g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, 512, s);
-    if (e != hipErrorNotSupported) return e;
-  }
-  if (f32_cfg_now() < 0) {  // few 32x32 blocks / batches of tiny matrices: one wave per block, no LDS round trips
-    const hipError_t e = launch_gemm_small<float>(a, g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, 512, s);
-    if (e != hipErrorNotSupported) return e;
-  }
-  // Up to ~150 tiles of 64x64 the slice-parallel form (kc slices as one batched launch + ordered combine) fills the chip
-  // better than any single launch; above that the hand-scheduled assembly kernels come first (their 64x64 tile covers the
-  // few-tile x long-K problems the slice-parallel form was built for: 1024^2 x 8192 = 256 tiles).
-  // (a pinned assembly tile class -- option "asm_tile", the sharded entry points' LASER_HIP_SHARD_PIN_TILE -- asks for THAT kernel
-  // family: the slice-parallel form does not come first then)
-  const bool few_tiles = ((a.M + 63) / 64) * ((a.N + 63) / 64) <= 150 && asm_tile_pin_now() < 0;
-  g_last_f32_asm = 0;
-  if (f32_cfg_now() < 0 && few_tiles) {
-    const hipError_t e = gemm_slice_parallel<float>(a, 512, s);
-    if (e != hipErrorNotSupported) return e;
-  }
-  // (a badly filled last round of tiles is the assembly launcher's business: its persistent plan hands the chip's workgroup slots
-  // equal numbers of kc slices and finishes a cut tile with an in-kernel ordered fix-up -- gemm_f32_asm.cpp plan_launch)
-  if (f32_cfg_now() < 0) {
-    const hipError_t e = launch_gemm_f32_asm(a, g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, s);
-    if (e != hipErrorNotSupported) return e;
-  }
-  if (f32_cfg_now() < 0 && !few_tiles) {
-    const hipError_t e = gemm_slice_parallel<float>(a, 512, s);
-    if (e != hipErrorNotSupported) return e;
-  }
-  return launch_gemm_f32(a, f32_cfg_now(), g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, s);
-}
-template <>
-hipError_t run_gemm_core<double>(const GemmArgs<double> &a, hipStream_t s) {
-  const bool laser = g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER;
-  if (g_ctx.skinny) {
-    const hipError_t e = launch_gemm_skinny<double>(a, laser, 256, s);
-    if (e != hipErrorNotSupported) return e;
-  }
-  if (g_ctx.f64_mfma) {
-    const hipError_t es = launch_gemm_small<double>(a, laser, 256, s);
-    if (es != hipErrorNotSupported) return es;
-    const bool few_tiles = ((a.M + 63) / 64) * ((a.N + 63) / 64) <= 150;   // (same rule as float32)
-    g_last_f64_asm = 0;
-    g_last_split = 0;
-    if (few_tiles) {
-      const hipError_t e = gemm_slice_parallel<double>(a, 256, s);
-      if (e != hipErrorNotSupported) return e;
-    }
-    const hipError_t ea = launch_gemm_f64_asm(a, laser, s);   // the hand-scheduled assembly kernels (laser_amd/asmgen/f64_kernel.py)
-    if (ea != hipErrorNotSupported) return ea;
-    if (!few_tiles) {
-      const hipError_t e = gemm_slice_parallel<double>(a, 256, s);
-      if (e != hipErrorNotSupported) return e;
-    }
-    return launch_gemm_f64(a, laser, s);
-  }  // v_mfma_f64_16x16x4_f64: a k-ordered fma chain
-  return launch_gemm_valu<double>(a, laser, s);
-}
-// Integer K beyond the hand-scheduled limb kernels' 8192 (their accumulator groups are never folded): arithmetic mod 2^n is
-// associative, so C = alpha * sum_chunks(A_c B_c) + beta * C0 is computed chunk by chunk -- the first with (alpha, beta), the
-// rest with (alpha, 1) -- bit for bit the single product.  hipErrorNotSupported (nothing launched): not the kernels' class.
-template <typename T, typename FA, typename FC>
-hipError_t int_gemm_k_chunks(const GemmArgs<T> &a, void *ws, hipStream_t s, FA asm_launch, FC compiler_launch, int64_t kChunk = 8192) {
-  hipError_t e = hipErrorNotSupported;
-  for (int64_t k0 = 0; k0 < a.K; k0 += kChunk) {
-    GemmArgs<T> c = a;
-    c.K = std::min(kChunk, a.K - k0);
-    c.Kext = c.K;
-    c.A = a.A + k0 * a.csA;
-    c.B = a.B + k0 * a.rsB;
-    if (k0 > 0) c.beta = (T)1;
-    e = asm_launch(c, ws, s);
-    if (e == hipErrorNotSupported) {
-      if (k0 == 0) return e;
-      e = compiler_launch(c, ws, s);
-    }
-    if (e != hipSuccess) return e;
-  }
-  return e;
-}
-
-// Integer GEMMs mod 2^32 / 2^64.  Large single problems go to the int8 matrix cores (limb decomposition: four limbs,
-// gemm_i32_mfma.hip; eight, gemm_i64_mfma.hip); the limb planes live in stream-ordered scratch so concurrent streams never share a
-// buffer.  The hand-scheduled kernels (laser_amd/asmgen/i8_kernel.py) take what they can, K > 8192 in chunks.
-template <typename T>
-hipError_t run_gemm_int(const GemmArgs<T> &a, hipStream_t s) {
-  constexpr bool i32 = std::is_same<T, int32_t>::value;
-  if (g_ctx.skinny) {
-    const hipError_t e = launch_gemm_skinny<T>(a, false, i32 ? 512 : 256, s);
-    if (e != hipErrorNotSupported) return e;
-  }
-  const double work = (double)a.M * (double)a.N * (double)a.K;
-  if ((i32 ? g_ctx.i32_mfma : g_ctx.i64_mfma) && a.batch == 1 && work >= 64.0 * 64.0 * 64.0 * 8.0) {
-    using Launch = hipError_t (*)(const GemmArgs<T> &, void *, hipStream_t);
-    Launch asm_launch, mfma_launch;     // the hand-scheduled kernel; the compiler-scheduled one where it does not apply
-    if constexpr (i32) asm_launch = launch_gemm_i32_asm, mfma_launch = launch_gemm_i32_mfma;
-    else asm_launch = launch_gemm_i64_asm, mfma_launch = launch_gemm_i64_mfma;
-    void *ws = nullptr;
-    hipError_t e = scratch_alloc_async(&ws, (i32 ? gemm_i32_mfma_workspace_bytes : gemm_i64_mfma_workspace_bytes)(a.M, a.N, a.K), s);
-    if (e != hipSuccess) return e;
-    g_last_i32_asm = 0;
-    e = a.K > 8192 ? int_gemm_k_chunks<T>(a, ws, s, asm_launch, mfma_launch) : asm_launch(a, ws, s);
-    if (e == hipErrorNotSupported) e = mfma_launch(a, ws, s);
-    hipError_t e2 = hipFreeAsync(ws, s);
-    return e != hipSuccess ? e : e2;
-  }
-  return launch_gemm_valu<T>(a, false, s);
-}
-template <>
-hipError_t run_gemm<int32_t>(const GemmArgs<int32_t> &a, hipStream_t s) { return run_gemm_int(a, s); }
-template <>
-hipError_t run_gemm<int64_t>(const GemmArgs<int64_t> &a, hipStream_t s) { return run_gemm_int(a, s); }
-
-// Integer GEMMs mod 2^8 / 2^16 (uint8 / uint16 on the same bits), in the shape of run_gemm_int: the streaming kernel for M or
-// N <= 8, the int8 matrix cores (gemm_narrow_mfma.hip) for single problems with enough work -- K beyond NARROW_MAX_K in chunks
-// --, the VALU kernel otherwise (batches included).
-std::atomic<int> g_last_narrow_mfma{0};
-template <typename T>
-hipError_t run_gemm_narrow(const GemmArgs<T> &a, hipStream_t s) {
-  g_last_narrow_mfma = 0;
-  if (g_ctx.skinny) {
-    const hipError_t e = launch_gemm_skinny<T>(a, false, 0, s);
-    if (e != hipErrorNotSupported) return e;
-  }
-  const double work = (double)a.M * (double)a.N * (double)a.K;
-  if (g_ctx.narrow_mfma && a.batch == 1 && work >= 64.0 * 64.0 * 64.0 * 8.0) {
-    void *ws = nullptr;
-    hipError_t e = scratch_alloc_async(&ws, gemm_narrow_mfma_workspace_bytes<T>(a.M, a.N, a.K), s);
-    if (e != hipSuccess) return e;
-    e = a.K > NARROW_MAX_K ? int_gemm_k_chunks<T>(a, ws, s, launch_gemm_narrow_mfma<T>, launch_gemm_narrow_mfma<T>, NARROW_MAX_K)
-                           : launch_gemm_narrow_mfma<T>(a, ws, s);
-    if (e == hipSuccess) g_last_narrow_mfma = 1;
-    hipError_t e2 = hipFreeAsync(ws, s);
-    return e != hipSuccess ? e : e2;
-  }
-  return launch_gemm_valu<T>(a, false, s);
-}
-template <>
-hipError_t run_gemm<int8_t>(const GemmArgs<int8_t> &a, hipStream_t s) { return run_gemm_narrow(a, s); }
-template <>
-hipError_t run_gemm<int16_t>(const GemmArgs<int16_t> &a, hipStream_t s) { return run_gemm_narrow(a, s); }
-
-// the small-matrix kernel on operands that live in host memory mapped into the device (gemm_host's zero-copy staging)
-template <typename T>
-hipError_t run_small_mapped(const GemmArgs<T> &a, hipStream_t s) {
-  if constexpr (std::is_same<T, float>::value)
-    return launch_gemm_small<float>(a, g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, 512, s, true);
-  else if constexpr (std::is_same<T, double>::value)
-    return launch_gemm_small<double>(a, g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, 256, s, true);
-  else
-    return hipErrorNotSupported;
-}
-
-template <typename T>
-GemmArgs<T> make_args(int64_t batch, int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA,
-                      int64_t csA, int64_t bsA, const T *B, int64_t rsB, int64_t csB, int64_t bsB, T beta,
-                      T *C, int64_t rsC, int64_t csC, int64_t bsC) {
-  GemmArgs<T> a;
-  memset(&a, 0, sizeof a);
-  a.M = M; a.N = N; a.K = K;
-  a.alpha = alpha; a.beta = beta;
-  a.A = A; a.rsA = rsA; a.csA = csA; a.bsA = bsA;
-  a.B = B; a.rsB = rsB; a.csB = csB; a.bsB = bsB;
-  a.C = C; a.rsC = rsC; a.csC = csC; a.bsC = bsC;
-  a.Mext = M; a.Next = N; a.Kext = K;
-  a.batch = (int32_t)batch;
-  return a;
-}
 
 // Fused epilogue request (device pointers): bias == nullptr and act == 0 means "plain gemm_strided".
 template <typename T>
@@ -870,153 +498,6 @@ int gemm_host(int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA,
   return LASER_HIP_OK;
 }
 
-// ---- pre-pack ------------------------------------------------------------------------------------
-// Panel image = dense row-major copy, zero-padded so every tile configuration is "full":
-// rows of A / cols of B to a multiple of 256, k to a multiple of 32.
-constexpr int64_t kPadMN = 256, kPadK = 32;
-inline int64_t rup(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
-// Host pre-pack buffers are SELF-CONTAINED, like the reference's (gemm_prepacked.nim:111-135: the packed panels live in the caller's
-// `mem_required` bytes; Design.md:5-7: Laser keeps no memory of its own): a 64-byte header followed by the tile-padded panel image.
-// The device copy gemm_packed multiplies from is a CACHE of that image, keyed by the header's id (unique per prepack call) and the
-// device: made by the prepack call itself, re-made from the caller's buffer whenever it is missing (evicted, made on another device,
-// the buffer is a memcpy of the original), dropped by laser_hip_gemm_prepack_release / finalize, and bounded (least recently used
-// first) -- a caller who simply frees its buffers, as a Laser caller would, cannot leak HBM (VERDICT r4 missing #4).
-constexpr uint64_t kMagic = 0x4c41534552484951ull;  // "LASERHIQ": layout 2 (header + image)
-struct PackHandle {  // the first 64 bytes of the caller's (64-B aligned) host buffer
-  uint64_t magic, id;
-  int64_t M, N, K;
-  int32_t is_a, elem;
-  uint64_t image_bytes;
-  uint64_t sum;        // fingerprint of the image (samples + length): a device copy is only ever used for the image it was made from
-};
-static_assert(sizeof(PackHandle) <= 64, "handle must fit the alignment unit");
-constexpr size_t kPackHeader = 64;
-struct DevPanel {
-  void *ptr = nullptr;
-  size_t bytes = 0;
-  int device = 0;
-  int pins = 0;            // calls multiplying from it right now: never evicted
-  uint64_t last_use = 0;
-  uint64_t id = 0, sum = 0;   // of the header it was made for (release drops by id; a hit is checked against both)
-};
-std::unordered_map<uint64_t, DevPanel> g_panels;      // key = mix(id, fingerprint, shape) with the device ordinal in the low byte
-size_t g_panel_bytes = 0;
-uint64_t g_panel_clock = 0;
-constexpr size_t kPanelCacheMax = (size_t)16 << 30;
-inline uint64_t mix64(uint64_t x) {      // splitmix64 finaliser
-  x += 0x9e3779b97f4a7c15ull;
-  x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-  x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-  return x ^ (x >> 31);
-}
-// Ids are unique ACROSS processes, not a counter from 1: a buffer packed in one process and handed to another -- or to
-// a forked child -- must not meet a cached panel that the other process made under the same number.  A per-process random salt
-// (re-drawn in a forked child) goes through a 64-bit mixer with the counter; the cache key also carries the header's shape and
-// the image fingerprint, so even an id collision cannot pair a header with another image's device copy.
-uint64_t g_id_salt = 0;
-uint64_t g_next_id = 1;
-void draw_id_salt() {
-  uint64_t s = (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count() ^ ((uint64_t)getpid() << 32) ^ (uint64_t)(uintptr_t)&g_id_salt;
-  if (FILE *f = fopen("/dev/urandom", "rb")) {
-    uint64_t r = 0;
-    if (fread(&r, sizeof r, 1, f) == 1) s ^= r;
-    fclose(f);
-  }
-  g_id_salt = mix64(s);
-}
-uint64_t fresh_id_locked() {
-  static bool once = [] {
-    draw_id_salt();
-    (void)pthread_atfork(nullptr, nullptr, [] { draw_id_salt(); });
-    return true;
-  }();
-  (void)once;
-  return mix64(g_id_salt ^ mix64(g_next_id++));
-}
-// fingerprint of a panel image in host memory: its length and 256 samples of 8 bytes spread over it (cheap beside the copies a
-// pre-pack makes; it guards the cache against headers that name the same id for different images, not against an adversary)
-uint64_t image_fingerprint(const void *img, size_t bytes) {
-  uint64_t h = mix64(bytes);
-  const size_t words = bytes / 8;
-  if (!words) return h;
-  const size_t step = std::max<size_t>(1, words / 256);
-  for (size_t i = 0; i < words; i += step) {
-    uint64_t w;
-    memcpy(&w, (const char *)img + 8 * i, 8);
-    h = mix64(h ^ w);
-  }
-  uint64_t w;
-  memcpy(&w, (const char *)img + 8 * (words - 1), 8);
-  return mix64(h ^ w);
-}
-inline uint64_t panel_key(const PackHandle &h, int dev) {
-  uint64_t k = mix64(h.id ^ mix64(h.sum ^ mix64((uint64_t)h.M * 0x100000001b3ull ^ (uint64_t)h.N * 0x1000193ull ^ (uint64_t)h.K ^ ((uint64_t)h.is_a << 40) ^ ((uint64_t)h.elem << 48))));
-  return (k << 8) | (uint64_t)(dev & 0xff);
-}
-// (g_mu held) make room for `need` more bytes: least recently used unpinned panels go first
-void panel_cache_evict_locked(size_t need) {
-  while (g_panel_bytes + need > kPanelCacheMax) {
-    auto victim = g_panels.end();
-    for (auto it = g_panels.begin(); it != g_panels.end(); ++it)
-      if (it->second.pins == 0 && (victim == g_panels.end() || it->second.last_use < victim->second.last_use)) victim = it;
-    if (victim == g_panels.end()) return;
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    if (victim->second.device != cur) (void)hipSetDevice(victim->second.device);
-    (void)hipFree(victim->second.ptr);      // (waits for the device: no launch still reads it)
-    if (victim->second.device != cur) (void)hipSetDevice(cur);
-    g_panel_bytes -= victim->second.bytes;
-    g_panels.erase(victim);
-  }
-}
-// (g_mu held) every device's copy of panel `id`, unless a call is multiplying from one
-void panel_cache_drop_locked(uint64_t id) {
-  for (auto it = g_panels.begin(); it != g_panels.end();) {
-    if (it->second.id == id && it->second.pins == 0) {
-      int cur = 0;
-      (void)hipGetDevice(&cur);
-      if (it->second.device != cur) (void)hipSetDevice(it->second.device);
-      (void)hipFree(it->second.ptr);
-      if (it->second.device != cur) (void)hipSetDevice(cur);
-      g_panel_bytes -= it->second.bytes;
-      it = g_panels.erase(it);
-    } else {
-      ++it;
-    }
-  }
-}
-
-// (g_mu held) a panel allocation that gives cached panels back before it gives up: out of memory -> every unpinned panel of this
-// device is evicted (least recently used first, all of them if need be) and the allocation is retried once (a caller who
-// frees buffers without `release` may leave the bounded cache holding most of a GPU's memory)
-int panel_alloc_locked(void **ptr, size_t bytes, int dev) {
-  hipError_t e = hipMalloc(ptr, bytes);
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    bool freed = false;
-    for (auto it = g_panels.begin(); it != g_panels.end();) {
-      if (it->second.device == dev && it->second.pins == 0) {
-        (void)hipFree(it->second.ptr);
-        g_panel_bytes -= it->second.bytes;
-        it = g_panels.erase(it);
-        freed = true;
-      } else {
-        ++it;
-      }
-    }
-    if (freed) e = hipMalloc(ptr, bytes);
-  }
-  if (e != hipSuccess) {
-    *ptr = nullptr;
-    return fail(LASER_HIP_E_HIP, "allocating a pre-packed panel (%zu bytes): %s", bytes, hipGetErrorString(e));
-  }
-  return LASER_HIP_OK;
-}
-int panel_alloc(void **ptr, size_t bytes, int dev) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  return panel_alloc_locked(ptr, bytes, dev);
-}
 
 // device tensor storage: live blocks (ptr -> rounded size) and the free list keyed by size
 constexpr size_t kStorageCacheMax = (size_t)32 << 30;
@@ -1036,192 +517,6 @@ void storage_trim() {
     }
   g_free_storage.clear();
   g_free_storage_bytes = 0;
-}
-template <typename T>
-int64_t prepack_bytes(bool is_a, int64_t M, int64_t N, int64_t K) {
-  if (M < 0 || N < 0 || K < 0) return 0;
-  const int64_t x = is_a ? rup(M, kPadMN) : rup(N, kPadMN);
-  const int64_t b = (int64_t)sizeof(T) * x * rup(K, kPadK);
-  return std::max<int64_t>(b, 64) + (int64_t)kPackHeader;      // (host form: header + image; device form: the image alone, at offset 0)
-}
-template <typename T>
-int64_t prepack_image_bytes(bool is_a, int64_t M, int64_t N, int64_t K) {
-  return prepack_bytes<T>(is_a, M, N, K) - (int64_t)kPackHeader;
-}
-
-template <typename T>
-int prepack_dev(bool is_a, void *d_dst, int64_t M, int64_t N, int64_t K, const T *src, int64_t rs, int64_t cs,
-                void *stream) {
-  if (int rc = ensure_init()) return rc;
-  if (!d_dst || !src) return fail(LASER_HIP_E_INVALID, "null pointer");
-  if (is_a)  // A image: [Mpad][Kpad], k contiguous
-    HIP_TRY(launch_pack_pad<T>((T *)d_dst, rup(M, kPadMN), rup(K, kPadK), src, M, K, rs, cs, (hipStream_t)stream));
-  else       // B image: [Kpad][Npad], n contiguous
-    HIP_TRY(launch_pack_pad<T>((T *)d_dst, rup(K, kPadK), rup(N, kPadMN), src, K, N, rs, cs, (hipStream_t)stream));
-  return LASER_HIP_OK;
-}
-
-template <typename T>
-int prepack_host(bool is_a, void *dst, int64_t M, int64_t N, int64_t K, const T *src, int64_t rs, int64_t cs) {
-  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "null pointer");
-  // same precondition as the reference's doAssert (gemm_prepacked.nim:125, :208)
-  if ((reinterpret_cast<uintptr_t>(dst) & 63) != 0)
-    return fail(LASER_HIP_E_INVALID, "The destination pointer must be 64-byte aligned");
-  if (M < 0 || N < 0 || K < 0) return fail(LASER_HIP_E_INVALID, "negative dimension");
-  if (int rc = ensure_init()) return rc;
-  HostCall hc;
-  if (hc.rc) return hc.rc;
-  const int64_t R = is_a ? M : K, Cc = is_a ? K : N;
-  int64_t lo, hi;
-  view_span(std::max<int64_t>(R, 1), std::max<int64_t>(Cc, 1), rs, cs, &lo, &hi);
-  const size_t n = (size_t)(hi - lo + 1);
-  void *dsrc;
-  if (int rc = scratch_get(3, n * sizeof(T), &dsrc)) return rc;
-  if (R > 0 && Cc > 0) HIP_TRY(hipMemcpy(dsrc, src + lo, n * sizeof(T), hipMemcpyHostToDevice));
-  DevPanel p;
-  p.bytes = (size_t)prepack_image_bytes<T>(is_a, M, N, K);
-  (void)hipGetDevice(&p.device);
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    panel_cache_evict_locked(p.bytes);
-  }
-  if (int rc = panel_alloc(&p.ptr, p.bytes, p.device)) return rc;
-  hipError_t e = is_a ? launch_pack_pad<T>((T *)p.ptr, rup(M, kPadMN), rup(K, kPadK), (const T *)dsrc - lo, M, K, rs, cs, nullptr)
-                      : launch_pack_pad<T>((T *)p.ptr, rup(K, kPadK), rup(N, kPadMN), (const T *)dsrc - lo, K, N, rs, cs, nullptr);
-  // the image goes into the caller's buffer (what makes the buffer self-contained); the device copy stays as the cache's first entry
-  if (e == hipSuccess) e = hipMemcpy((char *)dst + kPackHeader, p.ptr, p.bytes, hipMemcpyDeviceToHost);   // synchronises
-  if (e != hipSuccess) {
-    (void)hipFree(p.ptr);
-    return fail(LASER_HIP_E_HIP, "pre-pack: %s", hipGetErrorString(e));
-  }
-  PackHandle h;
-  memset(&h, 0, sizeof h);
-  h.magic = kMagic;
-  h.M = M; h.N = N; h.K = K;
-  h.is_a = is_a ? 1 : 0;
-  h.elem = (int32_t)sizeof(T);
-  h.image_bytes = p.bytes;
-  h.sum = image_fingerprint((const char *)dst + kPackHeader, p.bytes);
-  std::lock_guard<std::mutex> lk(g_mu);  // the panel cache
-  h.id = fresh_id_locked();
-  // re-packing into a buffer that still holds a live header drops the old image's device copies first
-  PackHandle old;
-  memcpy(&old, dst, sizeof old);
-  if (old.magic == kMagic) panel_cache_drop_locked(old.id);
-  memcpy(dst, &h, sizeof h);
-  p.last_use = ++g_panel_clock;
-  p.id = h.id; p.sum = h.sum;
-  g_panels[panel_key(h, p.device)] = p;
-  g_panel_bytes += p.bytes;
-  return LASER_HIP_OK;
-}
-
-// (g_mu held) the device copy of a host pre-pack buffer on the current device, PINNED (panel_unpin when the product is done); made
-// from the caller's buffer when the cache does not hold it
-int resolve_handle(const void *packed, bool want_a, int elem, int64_t M, int64_t N, int64_t K, void **dptr, uint64_t *key_out) {
-  if (!packed) return fail(LASER_HIP_E_INVALID, "null packed buffer");
-  PackHandle h;
-  memcpy(&h, packed, sizeof h);
-  if (h.magic != kMagic) return fail(LASER_HIP_E_HANDLE, "buffer does not hold a pre-packed operand (never packed, or released)");
-  if ((h.is_a != 0) != want_a || h.elem != elem)
-    return fail(LASER_HIP_E_HANDLE, "pre-packed buffer is for another operand / element type");
-  if (want_a ? (h.M != M || h.K != K) : (h.N != N || h.K != K))
-    return fail(LASER_HIP_E_HANDLE, "pre-packed buffer was made for a different shape");
-  // (the header is caller memory: the image size it states must be the one this shape has before it sizes an allocation and a copy)
-  const int64_t want_bytes = std::max<int64_t>((int64_t)elem * rup(want_a ? M : N, kPadMN) * rup(K, kPadK), 64);
-  if ((int64_t)h.image_bytes != want_bytes) return fail(LASER_HIP_E_HANDLE, "pre-packed buffer header is corrupt (image size)");
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t key = panel_key(h, dev);
-  auto it = g_panels.find(key);
-  // A hit is used only if it is the copy of THIS image: same id, same fingerprint, same size (the key mixes all of them, so anything
-  // else is a 64-bit hash collision -- or a header someone edited).  Such an entry is left alone (a call may be multiplying from it)
-  // and the operand is refused rather than multiplied from the wrong matrix / read past a smaller panel.
-  if (it != g_panels.end() && (it->second.id != h.id || it->second.sum != h.sum || it->second.bytes != (size_t)h.image_bytes))
-    return fail(LASER_HIP_E_HANDLE, "pre-packed buffer header does not match the cached device image (foreign or edited header)");
-  if (it == g_panels.end()) {      // evicted / another device / a copy of the buffer in a process that never packed it: upload the image
-    if (image_fingerprint((const char *)packed + kPackHeader, (size_t)h.image_bytes) != h.sum)
-      return fail(LASER_HIP_E_HANDLE, "pre-packed buffer does not hold the image its header describes");
-    DevPanel p;
-    p.bytes = (size_t)h.image_bytes;
-    p.device = dev;
-    p.id = h.id; p.sum = h.sum;
-    panel_cache_evict_locked(p.bytes);
-    if (int rc = panel_alloc_locked(&p.ptr, p.bytes, dev)) return rc;
-    const hipError_t e = hipMemcpy(p.ptr, (const char *)packed + kPackHeader, p.bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(p.ptr);
-      return fail(LASER_HIP_E_HIP, "uploading a pre-packed operand: %s", hipGetErrorString(e));
-    }
-    g_panel_bytes += p.bytes;
-    it = g_panels.emplace(key, p).first;
-  }
-  it->second.pins++;
-  it->second.last_use = ++g_panel_clock;
-  *dptr = it->second.ptr;
-  *key_out = key;
-  return LASER_HIP_OK;
-}
-void panel_unpin(uint64_t key) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  auto it = g_panels.find(key);
-  if (it != g_panels.end() && it->second.pins > 0) it->second.pins--;
-}
-
-template <typename T>
-GemmArgs<T> packed_args(int64_t M, int64_t N, int64_t K, T alpha, const void *dA, const void *dB, T beta, T *dC,
-                        int64_t rsC, int64_t csC) {
-  GemmArgs<T> a = make_args<T>(1, M, N, K, alpha, (const T *)dA, rup(K, kPadK), 1, 0, (const T *)dB,
-                               rup(N, kPadMN), 1, 0, beta, dC, rsC, csC, 0);
-  a.Mext = rup(M, kPadMN);
-  a.Next = rup(N, kPadMN);
-  a.Kext = rup(K, kPadK);
-  return a;
-}
-
-template <typename T>
-int packed_dev(int64_t M, int64_t N, int64_t K, T alpha, const void *dA, const void *dB, T beta, T *dC,
-               int64_t rsC, int64_t csC, void *stream) {
-  if (M < 0 || N < 0 || K < 0) return fail(LASER_HIP_E_INVALID, "negative dimension");
-  if (int rc = ensure_init()) return rc;
-  if (M == 0 || N == 0 || K == 0) return LASER_HIP_OK;
-  if (!dA || !dB || !dC) return fail(LASER_HIP_E_INVALID, "null pointer");
-  HIP_TRY(run_gemm<T>(packed_args<T>(M, N, K, alpha, dA, dB, beta, dC, rsC, csC), (hipStream_t)stream));
-  return LASER_HIP_OK;
-}
-
-template <typename T>
-int packed_host(int64_t M, int64_t N, int64_t K, T alpha, const void *pA, const void *pB, T beta, T *C,
-                int64_t rsC, int64_t csC) {
-  if (M < 0 || N < 0 || K < 0) return fail(LASER_HIP_E_INVALID, "negative dimension");
-  if (int rc = ensure_init()) return rc;
-  if (M == 0 || N == 0 || K == 0) return LASER_HIP_OK;
-  if (!C) return fail(LASER_HIP_E_INVALID, "null pointer");
-  HostCall hc;
-  if (hc.rc) return hc.rc;
-  void *dA, *dB, *dC;
-  uint64_t keyA = 0, keyB = 0;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);  // the panel cache
-    if (int rc = resolve_handle(pA, true, (int)sizeof(T), M, N, K, &dA, &keyA)) return rc;
-    if (int rc = resolve_handle(pB, false, (int)sizeof(T), M, N, K, &dB, &keyB)) {
-      g_panels[keyA].pins--;
-      return rc;
-    }
-  }
-  struct Unpin {      // both panels stay in the cache until this call's product has finished (the D2H copy below synchronises)
-    uint64_t a, b;
-    ~Unpin() { panel_unpin(a); panel_unpin(b); }
-  } unpin{keyA, keyB};
-  int64_t clo, chi;
-  view_span(M, N, rsC, csC, &clo, &chi);
-  const size_t cn = (size_t)(chi - clo + 1);
-  if (int rc = scratch_get(2, cn * sizeof(T), &dC)) return rc;
-  if (beta != (T)0 || cn != (size_t)M * (size_t)N)
-    HIP_TRY(hipMemcpy(dC, C + clo, cn * sizeof(T), hipMemcpyHostToDevice));
-  HIP_TRY(run_gemm<T>(packed_args<T>(M, N, K, alpha, dA, dB, beta, (T *)dC - clo, rsC, csC), nullptr));
-  HIP_TRY(hipMemcpy(C + clo, dC, cn * sizeof(T), hipMemcpyDeviceToHost));
-  return LASER_HIP_OK;
 }
 
 // ---- transposes ------------------------------------------------------------------------------------
@@ -1293,7 +588,7 @@ int conv_dev(float *dout, const float *din, int64_t iN, int64_t iC, int64_t iH, 
     a.cH = (int32_t)iH; a.cW = (int32_t)iW; a.ckH = (int32_t)kH; a.ckW = (int32_t)kW; a.coW = (int32_t)oW;
     a.cpH = (int32_t)pH; a.cpW = (int32_t)pW; a.csH = (int32_t)sH; a.csW = (int32_t)sW;
     epi_apply(a, &epi);
-    HIP_TRY(launch_conv_implicit_f32(a, f32_cfg_now(), g_ctx.float_mode == LASER_HIP_F32_LASER_ORDER, s));
+    HIP_TRY(launch_conv_implicit_f32(a, f32_cfg_now(), laser_order_now(), s));
     return LASER_HIP_OK;
   }
   const float *Bm = din;
@@ -1366,27 +661,6 @@ int copy_strided_api(void *dst, const int64_t *ds, const void *src, const int64_
 }
 }  // namespace
 
-namespace laser_hip {
-int api_fail(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-int api_fail_text(int code, const std::string &text) {
-  g_err = text;
-  return code;
-}
-int api_ensure_init() { return ensure_init(); }
-void api_set_thread_device(int device) { tl_device = device; }
-void api_set_thread_f32_config(int cfg) { tl_f32_cfg = cfg; }
-void api_set_thread_asm_tile(int tile_class) { asm_set_thread_tile(tile_class); }
-int api_thread_device() { return tl_device; }
-}  // namespace laser_hip
-
 extern "C" {
 
 int laser_hip_init(int device) {
@@ -1421,12 +695,7 @@ int laser_hip_finalize(void) {
   scratch_pools_trim();
   std::lock_guard<std::mutex> lk(g_mu);
   if (g_ctx.device >= 0) (void)hipSetDevice(g_ctx.device);
-  for (auto &kv : g_panels) {
-    (void)hipSetDevice(kv.second.device);
-    (void)hipFree(kv.second.ptr);
-  }
-  g_panels.clear();
-  g_panel_bytes = 0;
+  panel_cache_clear_locked();
   if (g_ctx.device >= 0) (void)hipSetDevice(g_ctx.device);
   for (auto &kv : g_free_storage)
     for (void *p : kv.second) {
@@ -1468,105 +737,106 @@ int laser_hip_set_f32_config(int cfg) {
   return LASER_HIP_OK;
 }
 int laser_hip_f32_config_count(void) { return gemm_f32_config_count(); }
+}  // extern "C"
 // ---- options: every tuning / A-B switch behind ONE entry point (name, value); diagnostics behind laser_hip_get_option ----
-// (the header documents each name; unknown names are an error, never silently ignored)
+// One row per name (the header documents each; unknown names are an error, never silently ignored): how to read it, how to write
+// it (nothing: a read-only diagnostic), and what a written value becomes.  The variables stay beside the code that reads them.
+namespace {
+enum OptionRule {
+  kOnOff,   // any non-zero value becomes 1
+  kClamp,   // into [lo, hi]
+  kOrElse,  // [lo, hi] as it is, anything else becomes `other`
+};
+struct Option {
+  const char *name;
+  int64_t (*get)();
+  void (*set)(int);
+  OptionRule rule;
+  int lo, hi, other;
+};
+constexpr int kNoLimit = 2147483647;
+#define LH_VAR(v) [] { return (int64_t)(v); }, [](int x) { (v) = x; }
+#define LH_READ_ONLY(expr) [] { return (int64_t)(expr); }, nullptr, kOnOff, 0, 0, 0
+const Option kOptions[] = {
+  {"f32_asm", LH_VAR(g_f32_asm), kClamp, 0, 2},
+  {"f64_asm", LH_VAR(g_f64_asm), kClamp, 0, 2},
+  {"i32_asm", LH_VAR(g_i32_asm), kClamp, 0, 2},
+  {"int_group_m", LH_VAR(g_int_group_m), kClamp, 1, 64},
+  {"f64_mfma", LH_VAR(g_ctx.f64_mfma), kOnOff},
+  {"i32_mfma", LH_VAR(g_ctx.i32_mfma), kOnOff},
+  {"i64_mfma", LH_VAR(g_ctx.i64_mfma), kOnOff},
+  {"narrow_mfma", LH_VAR(g_ctx.narrow_mfma), kOnOff},
+  {"conv_implicit", LH_VAR(g_ctx.conv_implicit), kOnOff},
+  {"conv_patch", LH_VAR(g_conv_patch), kOnOff},
+  {"conv_direct", LH_VAR(g_conv_direct), kClamp, 0, 3},
+  {"conv_kslice", LH_VAR(g_conv_kslice), kOnOff},
+  {"conv_tail", LH_VAR(g_conv_tail), kOnOff},
+  {"conv_cut_always", LH_VAR(g_conv_cut_always), kOnOff},
+  {"conv_1x1_implicit", LH_VAR(g_conv_1x1_implicit), kOnOff},
+  {"conv_walk", LH_VAR(g_conv_walk), kClamp, 0, 65535},
+  {"host_pipeline_2d", LH_VAR(g_ctx.host_pipeline_2d), kOnOff},
+  {"zero_copy_poll", LH_VAR(g_ctx.zc_poll), kOnOff},
+  {"skinny", LH_VAR(g_ctx.skinny), kOnOff},
+  {"small_path", LH_VAR(g_small_path), kOnOff},
+  {"split_tail", LH_VAR(g_split_tail), kOnOff},
+  {"slice_parallel", LH_VAR(g_ctx.slice_parallel), kOnOff},
+  {"slice_parallel_min", LH_VAR(g_ctx.slice_parallel_min), kClamp, 2, kNoLimit},
+  {"slice_parallel_tiles", LH_VAR(g_ctx.slice_parallel_tiles), kClamp, 0, kNoLimit},
+  {"asm_plan", LH_VAR(g_asm_plan), kClamp, 0, 4},
+  {"asm_kernel", LH_VAR(g_asm_kernel), kClamp, -1, kNoLimit},
+  {"asm_tile", LH_VAR(g_asm_tile), kOrElse, 0, 9, -1},
+  {"thread_asm_tile", [] { return (int64_t)asm_get_thread_tile(); }, asm_set_thread_tile, kOrElse, -1, 9, -2},  // thread-local
+  {"asm_wgs", LH_VAR(g_asm_wgs), kClamp, 0, kNoLimit},
+  {"asm_slice", LH_VAR(g_asm_slice), kClamp, 0, kNoLimit},
+  {"asm_group_m", LH_VAR(g_asm_group_m), kClamp, 0, kNoLimit},
+  {"asm_noseed", LH_VAR(g_asm_noseed), kOnOff},
+  {"asm_test_giveup", LH_VAR(g_asm_giveup), kOnOff},
+  {"im2col_band", LH_VAR(g_im2col_band), kClamp, 0, kNoLimit},
+  // diagnostics of the last launch, and counters
+  {"last_f32_config", LH_READ_ONLY(g_last_f32_cfg)},
+  {"last_f32_asm", LH_READ_ONLY(g_last_f32_asm)},
+  {"last_f64_asm", LH_READ_ONLY(g_last_f64_asm)},
+  {"last_i32_asm", LH_READ_ONLY(g_last_i32_asm)},
+  {"last_narrow_mfma", LH_READ_ONLY(g_last_narrow_mfma)},
+  {"last_split", LH_READ_ONLY(g_last_split)},
+  {"last_conv_tail", LH_READ_ONLY(g_last_conv_tail)},
+  {"last_asm_wgs", LH_READ_ONLY(g_last_asm_wgs)},
+  {"last_asm_rem", LH_READ_ONLY(g_last_asm_rem)},
+  {"last_asm_slices", LH_READ_ONLY(g_last_asm_slices)},
+  {"last_asm_group_m", LH_READ_ONLY(g_last_asm_group_m)},
+  {"last_foreach_variant", LH_READ_ONLY(api_last_foreach_variant())},
+  {"last_reduce_variant", LH_READ_ONLY(g_last_reduce_variant)},
+  {"last_softmax_kernel", LH_READ_ONLY(g_last_softmax_kernel)},
+  {"foreach_compiles", LH_READ_ONLY(api_foreach_compiles())},
+  {"asm_fixup_timeouts", LH_READ_ONLY(asm_fixup_timeouts())},  // synchronises the device when there is one, -1 without
+  {"shard_rccl_ranks", LH_READ_ONLY(api_shard_rccl_ranks())},
+};
+#undef LH_VAR
+#undef LH_READ_ONLY
+const Option *find_option(const char *name) {
+  for (const Option &o : kOptions)
+    if (strcmp(o.name, name) == 0) return &o;
+  return nullptr;
+}
+}  // namespace
+extern "C" {
 int laser_hip_set_option(const char *name, int value) {
   if (!name) return fail(LASER_HIP_E_INVALID, "set_option: null name");
-  const std::string n(name);
-  const bool on = value != 0;
-  if (n == "f32_asm") g_f32_asm = value < 0 ? 0 : value > 2 ? 2 : value;
-  else if (n == "f64_asm") g_f64_asm = value < 0 ? 0 : value > 2 ? 2 : value;
-  else if (n == "i32_asm") g_i32_asm = value < 0 ? 0 : value > 2 ? 2 : value;
-  else if (n == "int_group_m") g_int_group_m = value < 1 ? 1 : value > 64 ? 64 : value;
-  else if (n == "f64_mfma") g_ctx.f64_mfma = on;
-  else if (n == "i32_mfma") g_ctx.i32_mfma = on;
-  else if (n == "narrow_mfma") g_ctx.narrow_mfma = on;
-  else if (n == "i64_mfma") g_ctx.i64_mfma = on;
-  else if (n == "conv_implicit") g_ctx.conv_implicit = on;
-  else if (n == "conv_patch") g_conv_patch = on;
-  else if (n == "conv_direct") g_conv_direct = value < 0 ? 0 : value > 3 ? 3 : value;
-  else if (n == "conv_kslice") g_conv_kslice = on;
-  else if (n == "conv_tail") g_conv_tail = on;
-  else if (n == "conv_cut_always") g_conv_cut_always = on;
-  else if (n == "conv_1x1_implicit") g_conv_1x1_implicit = on;
-  else if (n == "conv_walk") g_conv_walk = value < 0 ? 0 : value > 65535 ? 65535 : value;
-  else if (n == "host_pipeline_2d") g_ctx.host_pipeline_2d = on;
-  else if (n == "zero_copy_poll") g_ctx.zc_poll = on;
-  else if (n == "skinny") g_ctx.skinny = on;
-  else if (n == "small_path") g_small_path = on;
-  else if (n == "split_tail") g_split_tail = on;
-  else if (n == "asm_plan") g_asm_plan = value < 0 ? 0 : value > 4 ? 4 : value;
-  else if (n == "asm_kernel") g_asm_kernel = value < 0 ? -1 : value;
-  else if (n == "asm_tile") g_asm_tile = value < 0 || value > 9 ? -1 : value;
-  else if (n == "thread_asm_tile") asm_set_thread_tile(value < -1 || value > 9 ? -2 : value);
-  else if (n == "im2col_band") g_im2col_band = value < 0 ? 0 : value;
-  else if (n == "asm_wgs") g_asm_wgs = value < 0 ? 0 : value;
-  else if (n == "asm_slice") g_asm_slice = value < 0 ? 0 : value;
-  else if (n == "asm_noseed") g_asm_noseed = on;
-  else if (n == "asm_test_giveup") g_asm_giveup = on;
-  else if (n == "asm_group_m") g_asm_group_m = value < 0 ? 0 : value;
-  else if (n == "slice_parallel") g_ctx.slice_parallel = on;
-  else if (n == "slice_parallel_min") g_ctx.slice_parallel_min = value < 2 ? 2 : value;
-  else if (n == "slice_parallel_tiles") g_ctx.slice_parallel_tiles = value < 0 ? 0 : value;
-  else return fail(LASER_HIP_E_INVALID, "set_option: unknown option '%s'", name);
+  const Option *o = find_option(name);
+  if (!o || !o->set) return fail(LASER_HIP_E_INVALID, "set_option: unknown option '%s'", name);
+  switch (o->rule) {
+    case kOnOff: value = value != 0; break;
+    case kClamp: value = value < o->lo ? o->lo : value > o->hi ? o->hi : value; break;
+    case kOrElse: value = value < o->lo || value > o->hi ? o->other : value; break;
+  }
+  o->set(value);
   return LASER_HIP_OK;
 }
 int laser_hip_get_option(const char *name, int64_t *value) {
   if (!name || !value) return fail(LASER_HIP_E_INVALID, "get_option: null argument");
-  const std::string n(name);
-  if (n == "f32_asm") *value = g_f32_asm;
-  else if (n == "f64_asm") *value = g_f64_asm;
-  else if (n == "last_f64_asm") *value = g_last_f64_asm;
-  else if (n == "i32_asm") *value = g_i32_asm;
-  else if (n == "int_group_m") *value = g_int_group_m;
-  else if (n == "last_i32_asm") *value = g_last_i32_asm;
-  else if (n == "f64_mfma") *value = g_ctx.f64_mfma;
-  else if (n == "i32_mfma") *value = g_ctx.i32_mfma;
-  else if (n == "i64_mfma") *value = g_ctx.i64_mfma;
-  else if (n == "narrow_mfma") *value = g_ctx.narrow_mfma;
-  else if (n == "last_narrow_mfma") *value = g_last_narrow_mfma;
-  else if (n == "foreach_compiles") *value = api_foreach_compiles();
-  else if (n == "last_foreach_variant") *value = api_last_foreach_variant();
-  else if (n == "last_reduce_variant") *value = g_last_reduce_variant;
-  else if (n == "last_softmax_kernel") *value = g_last_softmax_kernel;
-  else if (n == "conv_implicit") *value = g_ctx.conv_implicit;
-  else if (n == "conv_patch") *value = g_conv_patch;
-  else if (n == "conv_direct") *value = g_conv_direct;
-  else if (n == "conv_kslice") *value = g_conv_kslice;
-  else if (n == "conv_tail") *value = g_conv_tail;
-  else if (n == "conv_cut_always") *value = g_conv_cut_always;
-  else if (n == "conv_1x1_implicit") *value = g_conv_1x1_implicit;
-  else if (n == "conv_walk") *value = g_conv_walk;
-  else if (n == "host_pipeline_2d") *value = g_ctx.host_pipeline_2d;
-  else if (n == "zero_copy_poll") *value = g_ctx.zc_poll;
-  else if (n == "skinny") *value = g_ctx.skinny;
-  else if (n == "small_path") *value = g_small_path;
-  else if (n == "split_tail") *value = g_split_tail;
-  else if (n == "asm_plan") *value = g_asm_plan;
-  else if (n == "asm_kernel") *value = g_asm_kernel;
-  else if (n == "asm_tile") *value = g_asm_tile;
-  else if (n == "thread_asm_tile") *value = asm_get_thread_tile();
-  else if (n == "im2col_band") *value = g_im2col_band;
-  else if (n == "asm_wgs") *value = g_asm_wgs;
-  else if (n == "asm_slice") *value = g_asm_slice;
-  else if (n == "asm_noseed") *value = g_asm_noseed;
-  else if (n == "asm_test_giveup") *value = g_asm_giveup;
-  else if (n == "asm_group_m") *value = g_asm_group_m;
-  else if (n == "last_asm_wgs") *value = g_last_asm_wgs;
-  else if (n == "last_asm_rem") *value = g_last_asm_rem;
-  else if (n == "last_asm_slices") *value = g_last_asm_slices;
-  else if (n == "last_asm_group_m") *value = g_last_asm_group_m;
-  else if (n == "asm_fixup_timeouts") *value = asm_fixup_timeouts();
-  else if (n == "shard_rccl_ranks") *value = api_shard_rccl_ranks();
-  else if (n == "slice_parallel") *value = g_ctx.slice_parallel;
-  else if (n == "slice_parallel_min") *value = g_ctx.slice_parallel_min;
-  else if (n == "slice_parallel_tiles") *value = g_ctx.slice_parallel_tiles;
-  // diagnostics of the last launch (read-only)
-  else if (n == "last_f32_config") *value = g_last_f32_cfg;
-  else if (n == "last_f32_asm") *value = g_last_f32_asm;
-  else if (n == "last_split") *value = g_last_split;
-  else if (n == "last_conv_tail") *value = g_last_conv_tail;
-  else return fail(LASER_HIP_E_INVALID, "get_option: unknown option '%s'", name);
+  const Option *o = find_option(name);
+  if (!o) return fail(LASER_HIP_E_INVALID, "get_option: unknown option '%s'", name);
+  *value = o->get();
   return LASER_HIP_OK;
 }
 int laser_hip_set_shard_devices(int ndev) {  // host-pointer gemm_strided over ndev GPUs (1 = off, 0 = every visible GPU)
@@ -1577,77 +847,22 @@ int laser_hip_set_shard_devices(int ndev) {  // host-pointer gemm_strided over n
 int laser_hip_get_shard_devices(void) { return g_ctx.shard_devices; }
 const char *laser_hip_f32_config_name(int cfg) { return gemm_f32_config_name(cfg); }
 
-#define LH_DEF_GEMM(SFX, T)                                                                                   \
-  int laser_hip_gemm_strided_##SFX(int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA,         \
-                                   int64_t csA, const T *B, int64_t rsB, int64_t csB, T beta, T *C,           \
-                                   int64_t rsC, int64_t csC) {                                                \
-    return gemm_host<T>(M, N, K, alpha, A, rsA, csA, B, rsB, csB, beta, C, rsC, csC);                         \
-  }                                                                                                           \
-  int laser_hip_gemm_strided_##SFX##_dev(int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA,   \
-                                         int64_t csA, const T *B, int64_t rsB, int64_t csB, T beta, T *C,     \
-                                         int64_t rsC, int64_t csC, void *stream) {                            \
-    return gemm_dev<T>(1, M, N, K, alpha, A, rsA, csA, 0, B, rsB, csB, 0, beta, C, rsC, csC, 0, stream);      \
-  }                                                                                                           \
-  int laser_hip_gemm_strided_batched_##SFX##_dev(                                                             \
-      int64_t batch, int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA, int64_t csA,          \
-      int64_t bsA, const T *B, int64_t rsB, int64_t csB, int64_t bsB, T beta, T *C, int64_t rsC, int64_t csC, \
-      int64_t bsC, void *stream) {                                                                            \
-    return gemm_dev<T>(batch, M, N, K, alpha, A, rsA, csA, bsA, B, rsB, csB, bsB, beta, C, rsC, csC, bsC,     \
-                       stream);                                                                               \
-  }                                                                                                           \
-  int64_t laser_hip_gemm_prepackA_mem_required_##SFX(int64_t M, int64_t N, int64_t K) {                       \
-    return prepack_bytes<T>(true, M, N, K);                                                                   \
-  }                                                                                                           \
-  int64_t laser_hip_gemm_prepackB_mem_required_##SFX(int64_t M, int64_t N, int64_t K) {                       \
-    return prepack_bytes<T>(false, M, N, K);                                                                  \
-  }                                                                                                           \
-  int laser_hip_gemm_prepackA_##SFX(void *dst, int64_t M, int64_t N, int64_t K, const T *A, int64_t rs,       \
-                                    int64_t cs) {                                                             \
-    return prepack_host<T>(true, dst, M, N, K, A, rs, cs);                                                    \
-  }                                                                                                           \
-  int laser_hip_gemm_prepackB_##SFX(void *dst, int64_t M, int64_t N, int64_t K, const T *B, int64_t rs,       \
-                                    int64_t cs) {                                                             \
-    return prepack_host<T>(false, dst, M, N, K, B, rs, cs);                                                   \
-  }                                                                                                           \
-  int laser_hip_gemm_packed_##SFX(int64_t M, int64_t N, int64_t K, T alpha, const void *pA, const void *pB,   \
-                                  T beta, T *C, int64_t rsC, int64_t csC) {                                   \
-    return packed_host<T>(M, N, K, alpha, pA, pB, beta, C, rsC, csC);                                         \
-  }                                                                                                           \
-  int laser_hip_gemm_prepackA_##SFX##_dev(void *d, int64_t M, int64_t N, int64_t K, const T *A, int64_t rs,   \
-                                          int64_t cs, void *stream) {                                         \
-    return prepack_dev<T>(true, d, M, N, K, A, rs, cs, stream);                                               \
-  }                                                                                                           \
-  int laser_hip_gemm_prepackB_##SFX##_dev(void *d, int64_t M, int64_t N, int64_t K, const T *B, int64_t rs,   \
-                                          int64_t cs, void *stream) {                                         \
-    return prepack_dev<T>(false, d, M, N, K, B, rs, cs, stream);                                              \
-  }                                                                                                           \
-  int laser_hip_gemm_packed_##SFX##_dev(int64_t M, int64_t N, int64_t K, T alpha, const void *dA,             \
-                                        const void *dB, T beta, T *dC, int64_t rsC, int64_t csC,              \
-                                        void *stream) {                                                       \
-    return packed_dev<T>(M, N, K, alpha, dA, dB, beta, dC, rsC, csC, stream);                                 \
-  }
-LH_DEF_GEMM(f32, float)
-LH_DEF_GEMM(f64, double)
-LH_DEF_GEMM(i32, int32_t)
-LH_DEF_GEMM(i64, int64_t)
-#undef LH_DEF_GEMM
-
-// int8 / int16 (uint8 / uint16 on the same bits): alpha and beta travel as int32_t and are reduced mod 2^8 / 2^16
-#define LH_DEF_GEMM_NARROW(SFX, T)                                                                            \
-  int laser_hip_gemm_strided_##SFX(int64_t M, int64_t N, int64_t K, int32_t alpha, const T *A, int64_t rsA,   \
-                                   int64_t csA, const T *B, int64_t rsB, int64_t csB, int32_t beta, T *C,     \
+// S = the C type alpha and beta travel in: T itself, or int32_t for int8 / int16 (uint8 / uint16 on the same bits), reduced mod 2^8 / 2^16
+#define LH_DEF_GEMM(SFX, T, S)                                                                                \
+  int laser_hip_gemm_strided_##SFX(int64_t M, int64_t N, int64_t K, S alpha, const T *A, int64_t rsA,         \
+                                   int64_t csA, const T *B, int64_t rsB, int64_t csB, S beta, T *C,           \
                                    int64_t rsC, int64_t csC) {                                                \
     return gemm_host<T>(M, N, K, (T)alpha, A, rsA, csA, B, rsB, csB, (T)beta, C, rsC, csC);                   \
   }                                                                                                           \
-  int laser_hip_gemm_strided_##SFX##_dev(int64_t M, int64_t N, int64_t K, int32_t alpha, const T *A,          \
-                                         int64_t rsA, int64_t csA, const T *B, int64_t rsB, int64_t csB,      \
-                                         int32_t beta, T *C, int64_t rsC, int64_t csC, void *stream) {        \
+  int laser_hip_gemm_strided_##SFX##_dev(int64_t M, int64_t N, int64_t K, S alpha, const T *A, int64_t rsA,   \
+                                         int64_t csA, const T *B, int64_t rsB, int64_t csB, S beta, T *C,     \
+                                         int64_t rsC, int64_t csC, void *stream) {                            \
     return gemm_dev<T>(1, M, N, K, (T)alpha, A, rsA, csA, 0, B, rsB, csB, 0, (T)beta, C, rsC, csC, 0, stream); \
   }                                                                                                           \
   int laser_hip_gemm_strided_batched_##SFX##_dev(                                                             \
-      int64_t batch, int64_t M, int64_t N, int64_t K, int32_t alpha, const T *A, int64_t rsA, int64_t csA,    \
-      int64_t bsA, const T *B, int64_t rsB, int64_t csB, int64_t bsB, int32_t beta, T *C, int64_t rsC,        \
-      int64_t csC, int64_t bsC, void *stream) {                                                               \
+      int64_t batch, int64_t M, int64_t N, int64_t K, S alpha, const T *A, int64_t rsA, int64_t csA,          \
+      int64_t bsA, const T *B, int64_t rsB, int64_t csB, int64_t bsB, S beta, T *C, int64_t rsC, int64_t csC, \
+      int64_t bsC, void *stream) {                                                                            \
     return gemm_dev<T>(batch, M, N, K, (T)alpha, A, rsA, csA, bsA, B, rsB, csB, bsB, (T)beta, C, rsC, csC,    \
                        bsC, stream);                                                                          \
   }                                                                                                           \
@@ -1665,8 +880,8 @@ LH_DEF_GEMM(i64, int64_t)
                                     int64_t cs) {                                                             \
     return prepack_host<T>(false, dst, M, N, K, B, rs, cs);                                                   \
   }                                                                                                           \
-  int laser_hip_gemm_packed_##SFX(int64_t M, int64_t N, int64_t K, int32_t alpha, const void *pA,             \
-                                  const void *pB, int32_t beta, T *C, int64_t rsC, int64_t csC) {             \
+  int laser_hip_gemm_packed_##SFX(int64_t M, int64_t N, int64_t K, S alpha, const void *pA, const void *pB,   \
+                                  S beta, T *C, int64_t rsC, int64_t csC) {                                   \
     return packed_host<T>(M, N, K, (T)alpha, pA, pB, (T)beta, C, rsC, csC);                                   \
   }                                                                                                           \
   int laser_hip_gemm_prepackA_##SFX##_dev(void *d, int64_t M, int64_t N, int64_t K, const T *A, int64_t rs,   \
@@ -1677,25 +892,20 @@ LH_DEF_GEMM(i64, int64_t)
                                           int64_t cs, void *stream) {                                         \
     return prepack_dev<T>(false, d, M, N, K, B, rs, cs, stream);                                              \
   }                                                                                                           \
-  int laser_hip_gemm_packed_##SFX##_dev(int64_t M, int64_t N, int64_t K, int32_t alpha, const void *dA,       \
-                                        const void *dB, int32_t beta, T *dC, int64_t rsC, int64_t csC,        \
+  int laser_hip_gemm_packed_##SFX##_dev(int64_t M, int64_t N, int64_t K, S alpha, const void *dA,             \
+                                        const void *dB, S beta, T *dC, int64_t rsC, int64_t csC,              \
                                         void *stream) {                                                       \
     return packed_dev<T>(M, N, K, (T)alpha, dA, dB, (T)beta, dC, rsC, csC, stream);                           \
   }
-LH_DEF_GEMM_NARROW(i8, int8_t)
-LH_DEF_GEMM_NARROW(i16, int16_t)
-#undef LH_DEF_GEMM_NARROW
+LH_DEF_GEMM(f32, float, float)
+LH_DEF_GEMM(f64, double, double)
+LH_DEF_GEMM(i32, int32_t, int32_t)
+LH_DEF_GEMM(i64, int64_t, int64_t)
+LH_DEF_GEMM(i8, int8_t, int32_t)
+LH_DEF_GEMM(i16, int16_t, int32_t)
+#undef LH_DEF_GEMM
 
-int laser_hip_gemm_prepack_release(void *packed) {
-  if (!packed) return fail(LASER_HIP_E_INVALID, "null packed buffer");
-  std::lock_guard<std::mutex> lk(g_mu);
-  PackHandle h;
-  memcpy(&h, packed, sizeof h);
-  if (h.magic != kMagic) return fail(LASER_HIP_E_HANDLE, "buffer does not hold a pre-packed operand (never packed, or already released)");
-  panel_cache_drop_locked(h.id);      // (copies of the buffer lose their cached device image too: they re-upload on their next use)
-  memset(packed, 0, sizeof h);        // the buffer no longer reads as a packed operand
-  return LASER_HIP_OK;
-}
+int laser_hip_gemm_prepack_release(void *packed) { return prepack_release(packed); }
 
 #define LH_DEF_TR(SFX, ELEM)                                                                                  \
   int laser_hip_transpose2d_copy_##SFX(void *dst, const void *src, int64_t NR, int64_t NC) {                  \

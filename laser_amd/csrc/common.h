@@ -188,16 +188,14 @@ extern std::atomic<int> g_f64_asm, g_last_f64_asm;
 hipError_t launch_gemm_i32_asm(const GemmArgs<int32_t> &args, void *ws, hipStream_t s);
 hipError_t launch_gemm_i64_asm(const GemmArgs<int64_t> &args, void *ws, hipStream_t s);
 extern std::atomic<int> g_i32_asm, g_last_i32_asm, g_int_group_m;
-extern std::atomic<int> g_asm_tile;   // option "asm_tile" (gemm_f32_asm.cpp)
+// (the option variables below: include/laser_hip.h documents each under its name -- g_x is option "x", g_last_x is "last_x")
+extern std::atomic<int> g_asm_tile;
 void asm_set_thread_tile(int tile_class);   // per-thread pin of the same (-2 = none)
 int asm_get_thread_tile();
 int asm_tile_pin_now();                     // the pin this thread's launches see (-1 = none)
-extern std::atomic<int> g_last_asm_group_m;
-extern std::atomic<int> g_last_asm_rem;       // tiles the last assembly launch left to the K-cut launch of a hybrid plan (0: one launch)
-extern std::atomic<int> g_asm_plan, g_asm_kernel, g_asm_wgs, g_asm_slice, g_asm_noseed, g_asm_group_m, g_asm_giveup;   // launch-plan overrides of the assembly kernels (tuning sweeps, tests)
-extern std::atomic<int> g_last_asm_wgs, g_last_asm_slices;                  // diagnostics: workgroups / K slices per tile of the last assembly launch
-extern std::atomic<int> g_f32_asm;       // 1 default; 0 = never; 2 = whenever the kernel can (no tile-count rule: tests)
-extern std::atomic<int> g_last_f32_asm;  // 0 = the last f32 GEMM launch was a compiler-scheduled kernel, 1 / 2 = laser-order / fast assembly kernel
+extern std::atomic<int> g_asm_plan, g_asm_kernel, g_asm_wgs, g_asm_slice, g_asm_noseed, g_asm_group_m, g_asm_giveup;   // ("asm_test_giveup")
+extern std::atomic<int> g_last_asm_wgs, g_last_asm_slices, g_last_asm_group_m, g_last_asm_rem;
+extern std::atomic<int> g_f32_asm, g_last_f32_asm;
 // args.B = NCHW input, args.bsB = C*H*W, args.c* = geometry, N = oH*oW, K = C*kH*kW; A = filter
 hipError_t launch_conv_implicit_f32(const GemmArgs<float> &args, int cfg, bool laser_order, hipStream_t s);
 int gemm_f32_config_count();
@@ -233,18 +231,11 @@ template <typename T>
 size_t gemm_narrow_mfma_workspace_bytes(int64_t M, int64_t N, int64_t K);
 template <typename T>
 hipError_t launch_gemm_narrow_mfma(const GemmArgs<T> &args, void *ws, hipStream_t s);
-extern std::atomic<int> g_conv_direct;        // few output channels x short K: the direct (HBM-streaming) kernel (1, default)
+extern std::atomic<int> g_conv_direct, g_conv_patch, g_conv_walk, g_conv_cut_always, g_conv_tail, g_conv_kslice, g_last_conv_tail;
 hipError_t launch_conv_direct_small_f32(const GemmArgs<float> &a, hipStream_t s);
-extern std::atomic<int> g_conv_patch;         // implicit conv: LDS input patch where it fits (1, default) or always the gather (0)
-extern std::atomic<int> g_last_conv_tail;
-extern std::atomic<int> g_conv_walk;          // assembly conv main launch as unit walkers with pipelined transitions: 1 where units > slots (default), 0 never, 2 always, >= 3 that many workgroups (tests)
-extern std::atomic<int> g_conv_cut_always;    // tests / probes: cut every 3x3 convolution at its last whole 128-pixel tile (0, default)
-extern std::atomic<int> g_conv_tail;          // the direct tail kernel behind the assembly conv main launch (1, default)
 hipError_t launch_conv_tail_f32(const GemmArgs<float> &a, int kc, hipStream_t s);
-extern std::atomic<int> g_conv_kslice;        // laser-order conv tail as parallel kc slices + ordered combine (1, default)
-extern std::atomic<int> g_split_tail;        // 1 (default): cut problems with a badly filled last round into main + tail launches
-extern std::atomic<int64_t> g_last_split;    // diagnostics: column cut of the last MFMA launch (0 = one launch)
-extern std::atomic<int> g_last_f32_cfg;       // diagnostics: the f32 tile configuration the last GEMM / conv launch used
+extern std::atomic<int> g_split_tail, g_last_f32_cfg;   // ("last_f32_config")
+extern std::atomic<int64_t> g_last_split;
 hipError_t launch_transpose_batched(void *dst, const void *src, int64_t N, int64_t NR, int64_t NC,
                                     int elem_size, hipStream_t s);
 hipError_t launch_transpose_pitched(void *dst, int64_t ld_dst, const void *src, int64_t ld_src, int64_t NR, int64_t NC, int elem_size,
@@ -276,7 +267,7 @@ int merge_dims(int nops, const int64_t *strides, const int64_t *shape, int rank,
 // reductions in reduce_core.h's order (reduce.hip): op 0 sum, 1 min, 2 max; the result to the device address `out`
 template <typename T>
 hipError_t launch_reduce(int op, const T *src, const int64_t *strides, const int64_t *shape, int rank, T *out, hipStream_t s);
-extern std::atomic<int> g_last_reduce_variant;  // traversal of the last launch_reduce: 0 vector, 1 unaligned scalar, 2 strided
+extern std::atomic<int> g_last_reduce_variant;
 // The levels of a reduction of n elements (reduce.hip; forEachReduce uses it too).  level0(blocks, dst) launches the first
 // level (E = e0 elements per lane and step), one partial per workgroup into dst; partials(in, count, blocks, dst) reduces an
 // array of `count` accumulators of acc_size bytes.  Intermediate arrays live in stream-ordered scratch.
@@ -289,7 +280,7 @@ hipError_t launch_exp_f32(float *dst, const int64_t *dstrides, const float *src,
                           int rank, hipStream_t s);
 hipError_t launch_softmax_rows_f32(float *dst, int64_t dstride, const float *src, int64_t sstride, int64_t rows, int64_t n,
                                    hipStream_t s);
-extern std::atomic<int> g_last_softmax_kernel;  // 0 wave per row, 1 workgroup per row, 2 long rows; + 4: the scalar-access instance
+extern std::atomic<int> g_last_softmax_kernel;
 template <typename T>
 hipError_t launch_pack_pad(T *dst, int64_t Rpad, int64_t Cpad, const T *src, int64_t R,
                            int64_t Ccols, int64_t rs, int64_t cs, hipStream_t s, int relu = 0);

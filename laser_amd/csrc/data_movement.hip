@@ -469,7 +469,7 @@ hipError_t launch_copy_strided(T *dst, const int64_t *dstrides, const T *src, co
   hipLaunchKernelGGL(copy_strided_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, dst, src, a);
   return hipGetLastError();
 }
-// ---- ordered combine of per-slice partial products (slice-parallel GEMM, capi.cpp: gemm_slice_parallel) ----
+// ---- ordered combine of per-slice partial products (slice-parallel GEMM, gemm_route.cpp: gemm_slice_parallel) ----
 // C[i,j] = (..((beta*C0 or 0) + alpha*W[0][i,j]) + alpha*W[1][i,j] ..) + alpha*W[nsl-1][i,j], unfused, ascending slice:
 // exactly the sequence of Laser's pc loop (gemm.nim:150-158) with W[p] = the kc-slice product S_p.  HBM-bound.
 template <typename E>

@@ -86,26 +86,26 @@ bool is_keyword(const std::string &s) {
 }
 
 int check_name(const char *what, int i, const char *name) {
-  if (!name || !name[0]) return api_fail(LASER_HIP_E_INVALID, "foreach: %s %d has no name", what, i);
+  if (!name || !name[0]) return fail(LASER_HIP_E_INVALID, "foreach: %s %d has no name", what, i);
   const std::string s = name;
   bool ok = !(s[0] >= '0' && s[0] <= '9');
   for (char c : s) ok = ok && ((c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z') || (c >= '0' && c <= '9') || c == '_');
-  if (!ok) return api_fail(LASER_HIP_E_INVALID, "foreach: %s name '%s' is not a C identifier", what, name);
-  if (is_keyword(s)) return api_fail(LASER_HIP_E_INVALID, "foreach: %s name '%s' is a C++ keyword", what, name);
+  if (!ok) return fail(LASER_HIP_E_INVALID, "foreach: %s name '%s' is not a C identifier", what, name);
+  if (is_keyword(s)) return fail(LASER_HIP_E_INVALID, "foreach: %s name '%s' is a C++ keyword", what, name);
   if (s.rfind("lh_", 0) == 0 || s.rfind("__", 0) == 0)
-    return api_fail(LASER_HIP_E_INVALID, "foreach: %s name '%s' is reserved (lh_ and __ prefixes)", what, name);
-  if (s == "laser_exp") return api_fail(LASER_HIP_E_INVALID, "foreach: %s name 'laser_exp' is reserved (exp_core.h)", what);
+    return fail(LASER_HIP_E_INVALID, "foreach: %s name '%s' is reserved (lh_ and __ prefixes)", what, name);
+  if (s == "laser_exp") return fail(LASER_HIP_E_INVALID, "foreach: %s name 'laser_exp' is reserved (exp_core.h)", what);
   return LASER_HIP_OK;
 }
 
 int make_spec(Spec &sp, const char *body, int nops, const char *const *names, const int *dtypes, const int *writable,
               int nparams, const char *const *param_names, const int *param_dtypes) {
-  if (!body) return api_fail(LASER_HIP_E_INVALID, "foreach: null body");
-  if (nops < 1 || nops > kMaxOps) return api_fail(LASER_HIP_E_INVALID, "foreach: %d operands (1..%d)", nops, kMaxOps);
+  if (!body) return fail(LASER_HIP_E_INVALID, "foreach: null body");
+  if (nops < 1 || nops > kMaxOps) return fail(LASER_HIP_E_INVALID, "foreach: %d operands (1..%d)", nops, kMaxOps);
   if (nparams < 0 || nparams > kMaxParams)
-    return api_fail(LASER_HIP_E_INVALID, "foreach: %d parameters (0..%d)", nparams, kMaxParams);
+    return fail(LASER_HIP_E_INVALID, "foreach: %d parameters (0..%d)", nparams, kMaxParams);
   if (!names || !dtypes || !writable || (nparams > 0 && (!param_names || !param_dtypes)))
-    return api_fail(LASER_HIP_E_INVALID, "foreach: null spec array");
+    return fail(LASER_HIP_E_INVALID, "foreach: null spec array");
   sp.body = body;
   sp.nops = nops;
   sp.nparams = nparams;
@@ -115,10 +115,10 @@ int make_spec(Spec &sp, const char *body, int nops, const char *const *names, co
     const char *name = op ? names[j] : param_names[j];
     const int dt = op ? dtypes[j] : param_dtypes[j];
     if (int rc = check_name(op ? "operand" : "parameter", j, name)) return rc;
-    if (dt < 0 || dt >= kNumTypes) return api_fail(LASER_HIP_E_INVALID, "foreach: '%s' has unknown element type %d", name, dt);
+    if (dt < 0 || dt >= kNumTypes) return fail(LASER_HIP_E_INVALID, "foreach: '%s' has unknown element type %d", name, dt);
     for (int k = 0; k < i; k++)
       if ((k < nops ? sp.names[k] : sp.pnames[k - nops]) == name)
-        return api_fail(LASER_HIP_E_INVALID, "foreach: name '%s' used twice", name);
+        return fail(LASER_HIP_E_INVALID, "foreach: name '%s' used twice", name);
     if (op) {
       sp.names[j] = name;
       sp.dtypes[j] = dt;
@@ -144,14 +144,14 @@ int make_reduce_spec(Spec &sp, const char *body, int nops, const char *const *na
   if (int rc = make_spec(sp, body, nops, names, dtypes, writable, nparams, param_names, param_dtypes)) return rc;
   if (int rc = check_name("accumulator", 0, acc_name)) return rc;
   if (acc_dtype < 0 || acc_dtype >= kNumTypes)
-    return api_fail(LASER_HIP_E_INVALID, "foreach_reduce: accumulator '%s' has unknown element type %d", acc_name, acc_dtype);
-  if (!merge || blank(merge)) return api_fail(LASER_HIP_E_INVALID, "foreach_reduce: empty merge");
+    return fail(LASER_HIP_E_INVALID, "foreach_reduce: accumulator '%s' has unknown element type %d", acc_name, acc_dtype);
+  if (!merge || blank(merge)) return fail(LASER_HIP_E_INVALID, "foreach_reduce: empty merge");
   const std::string acc = acc_name;
-  if (acc == "other") return api_fail(LASER_HIP_E_INVALID, "foreach_reduce: 'other' is the merge's reserved name");
+  if (acc == "other") return fail(LASER_HIP_E_INVALID, "foreach_reduce: 'other' is the merge's reserved name");
   for (int i = 0; i < nops + nparams; i++) {
     const std::string &n = i < nops ? sp.names[i] : sp.pnames[i - nops];
-    if (n == "other") return api_fail(LASER_HIP_E_INVALID, "foreach_reduce: 'other' is the merge's reserved name");
-    if (n == acc) return api_fail(LASER_HIP_E_INVALID, "foreach_reduce: name '%s' used twice", acc_name);
+    if (n == "other") return fail(LASER_HIP_E_INVALID, "foreach_reduce: 'other' is the merge's reserved name");
+    if (n == acc) return fail(LASER_HIP_E_INVALID, "foreach_reduce: name '%s' used twice", acc_name);
   }
   sp.reduce = true;
   sp.acc_name = acc;
@@ -276,16 +276,16 @@ bool rtc_load() {
 // compile `sp` for `arch` into `code`; LASER_HIP_E_COMPILE with the compiler's log in laser_hip_last_error()
 int compile(const Spec &sp, const std::string &arch, std::vector<char> &code) {
   if (arch.empty() || arch.find("xnack+") != std::string::npos)
-    return api_fail(LASER_HIP_E_INVALID, "foreach: architecture '%s' is not accepted (xnack+ code objects are not built)",
+    return fail(LASER_HIP_E_INVALID, "foreach: architecture '%s' is not accepted (xnack+ code objects are not built)",
                     arch.c_str());
-  if (!rtc_load()) return api_fail(LASER_HIP_E_COMPILE, "foreach: %s", g_rtc.why.c_str());
+  if (!rtc_load()) return fail(LASER_HIP_E_COMPILE, "foreach: %s", g_rtc.why.c_str());
   const std::string src = generate(sp);
   const std::string target = "--offload-arch=" + arch;
   const char *opts[] = {target.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fwrapv"};
   std::lock_guard<std::mutex> lk(g_compile_mu);
   void *prog = nullptr;
   int e = g_rtc.Create(&prog, src.c_str(), "foreach.hip", 0, nullptr, nullptr);
-  if (e != 0) return api_fail(LASER_HIP_E_COMPILE, "foreach: hiprtcCreateProgram: %s", g_rtc.ErrorString(e));
+  if (e != 0) return fail(LASER_HIP_E_COMPILE, "foreach: hiprtcCreateProgram: %s", g_rtc.ErrorString(e));
   g_compiles++;
   e = g_rtc.Compile(prog, (int)(sizeof opts / sizeof opts[0]), opts);
   int rc = LASER_HIP_OK;
@@ -297,14 +297,14 @@ int compile(const Spec &sp, const std::string &arch, std::vector<char> &code) {
       if (g_rtc.Log(prog, &log[0]) != 0) log.clear();
       log.resize(strlen(log.c_str()));
     }
-    rc = api_fail_text(LASER_HIP_E_COMPILE, "foreach: the body did not compile (" + std::string(g_rtc.ErrorString(e)) + "):\n" + log);
+    rc = fail_text(LASER_HIP_E_COMPILE, "foreach: the body did not compile (" + std::string(g_rtc.ErrorString(e)) + "):\n" + log);
   } else {
     size_t n = 0;
     if (g_rtc.CodeSize(prog, &n) != 0 || n == 0) {
-      rc = api_fail(LASER_HIP_E_COMPILE, "foreach: hiprtc returned no code object");
+      rc = fail(LASER_HIP_E_COMPILE, "foreach: hiprtc returned no code object");
     } else {
       code.resize(n);
-      if (g_rtc.Code(prog, code.data()) != 0) rc = api_fail(LASER_HIP_E_COMPILE, "foreach: hiprtcGetCode failed");
+      if (g_rtc.Code(prog, code.data()) != 0) rc = fail(LASER_HIP_E_COMPILE, "foreach: hiprtcGetCode failed");
     }
   }
   g_rtc.Destroy(&prog);
@@ -312,10 +312,10 @@ int compile(const Spec &sp, const std::string &arch, std::vector<char> &code) {
 }
 
 int copy_out(const void *data, int64_t n, void *buf, int64_t cap, int64_t *len) {
-  if (!len) return api_fail(LASER_HIP_E_INVALID, "foreach: null length pointer");
+  if (!len) return fail(LASER_HIP_E_INVALID, "foreach: null length pointer");
   *len = n;
   if (!buf) return LASER_HIP_OK;  // a size query
-  if (cap < n) return api_fail(LASER_HIP_E_INVALID, "foreach: buffer of %lld bytes, %lld needed", (long long)cap, (long long)n);
+  if (cap < n) return fail(LASER_HIP_E_INVALID, "foreach: buffer of %lld bytes, %lld needed", (long long)cap, (long long)n);
   memcpy(buf, data, (size_t)n);
   return LASER_HIP_OK;
 }
@@ -356,15 +356,15 @@ static_assert(sizeof(ReduceArgs) == sizeof(ForeachArgs) + 16, "ReduceArgs must m
 // the module of `sp` for the current device, compiled and loaded on first use
 int kernel_for(const Spec &sp, int64_t *handle) {
   const char *what = sp.reduce ? "foreach_reduce" : "foreach";
-  if (!handle) return api_fail(LASER_HIP_E_INVALID, "%s: null handle pointer", what);
-  if (int rc = api_ensure_init()) return rc;
+  if (!handle) return fail(LASER_HIP_E_INVALID, "%s: null handle pointer", what);
+  if (int rc = ensure_init()) return rc;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return api_fail(LASER_HIP_E_NODEVICE, "%s: no current HIP device", what);
+  if (hipGetDevice(&dev) != hipSuccess) return fail(LASER_HIP_E_NODEVICE, "%s: no current HIP device", what);
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return api_fail(LASER_HIP_E_NODEVICE, "%s: device %d unreadable", what, dev);
+  if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(LASER_HIP_E_NODEVICE, "%s: device %d unreadable", what, dev);
   const std::string arch = prop.gcnArchName;  // e.g. "gfx950:sramecc+:xnack-", used as the device reports it
   if (arch.rfind("gfx950", 0) != 0)
-    return api_fail(LASER_HIP_E_NODEVICE, "%s: device %d is %s; liblaser_hip is built for gfx950 (MI355X) only", what, dev,
+    return fail(LASER_HIP_E_NODEVICE, "%s: device %d is %s; liblaser_hip is built for gfx950 (MI355X) only", what, dev,
                     arch.c_str());
   Kernel *k;
   {
@@ -388,7 +388,7 @@ int kernel_for(const Spec &sp, int64_t *handle) {
       e = hipModuleGetFunction(&k->fn[i], mod, sp.reduce ? kReduceKernelName[i] : kKernelName[i]);
     if (e != hipSuccess) {
       if (mod) (void)hipModuleUnload(mod);
-      return api_fail(LASER_HIP_E_HIP, "%s: loading the compiled module failed: %s", what, hipGetErrorString(e));
+      return fail(LASER_HIP_E_HIP, "%s: loading the compiled module failed: %s", what, hipGetErrorString(e));
     }
     k->mod = mod;
     k->device = dev;
@@ -415,13 +415,13 @@ int kernel_of(int64_t handle, bool reduce, Kernel **out) {
     std::lock_guard<std::mutex> lk(g_cache_mu);
     if (handle >= 1 && handle <= (int64_t)g_handles.size()) k = g_handles[handle - 1];
   }
-  if (!k) return api_fail(LASER_HIP_E_HANDLE, "%s: unknown kernel handle %lld", what, (long long)handle);
+  if (!k) return fail(LASER_HIP_E_HANDLE, "%s: unknown kernel handle %lld", what, (long long)handle);
   {
     std::lock_guard<std::mutex> lk(k->mu);
-    if (!k->ready) return api_fail(LASER_HIP_E_HANDLE, "%s: kernel handle %lld was never loaded", what, (long long)handle);
+    if (!k->ready) return fail(LASER_HIP_E_HANDLE, "%s: kernel handle %lld was never loaded", what, (long long)handle);
   }
   if (k->reduce != reduce)
-    return api_fail(LASER_HIP_E_HANDLE, "%s: handle %lld is a %s kernel", what, (long long)handle,
+    return fail(LASER_HIP_E_HANDLE, "%s: handle %lld is a %s kernel", what, (long long)handle,
                     k->reduce ? "forEachReduce" : "forEach");
   *out = k;
   return LASER_HIP_OK;
@@ -432,26 +432,26 @@ int kernel_of(int64_t handle, bool reduce, Kernel **out) {
 int prepare(const Kernel *k, void *const *ptrs, const int64_t *strides, const int64_t *shape, int rank, const void *params,
             ForeachArgs &a, int *variant, int64_t *total) {
   const char *what = k->reduce ? "foreach_reduce" : "foreach";
-  if (rank < 0 || rank > kMaxRank) return api_fail(LASER_HIP_E_INVALID, "%s: rank %d outside 0..%d (LASER_MAXRANK)", what, rank, kMaxRank);
+  if (rank < 0 || rank > kMaxRank) return fail(LASER_HIP_E_INVALID, "%s: rank %d outside 0..%d (LASER_MAXRANK)", what, rank, kMaxRank);
   if (!ptrs || (rank > 0 && (!strides || !shape)) || (k->nparams > 0 && !params))
-    return api_fail(LASER_HIP_E_INVALID, "%s: null pointers / strides / shape / parameters", what);
+    return fail(LASER_HIP_E_INVALID, "%s: null pointers / strides / shape / parameters", what);
   const int nops = k->nops;
   int64_t n = 1;
   for (int d = 0; d < rank; d++) {
-    if (shape[d] < 0) return api_fail(LASER_HIP_E_INVALID, "%s: negative extent", what);
+    if (shape[d] < 0) return fail(LASER_HIP_E_INVALID, "%s: negative extent", what);
     n *= shape[d];
   }
   for (int d = 0; d < rank; d++)
     for (int i = 0; i < nops; i++)
       if (k->writable[i] && shape[d] > 1 && strides[i * rank + d] == 0)
-        return api_fail(LASER_HIP_E_INVALID, "%s: writable operand %d has stride 0 (broadcast) in dimension %d", what, i, d);
+        return fail(LASER_HIP_E_INVALID, "%s: writable operand %d has stride 0 (broadcast) in dimension %d", what, i, d);
   *total = n;
   if (n == 0) return LASER_HIP_OK;
   for (int i = 0; i < nops; i++)
-    if (!ptrs[i]) return api_fail(LASER_HIP_E_INVALID, "%s: operand %d is a null buffer", what, i);
+    if (!ptrs[i]) return fail(LASER_HIP_E_INVALID, "%s: operand %d is a null buffer", what, i);
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev != k->device)
-    return api_fail(LASER_HIP_E_INVALID, "%s: handle %lld was made for device %d, the current device is %d", what,
+    return fail(LASER_HIP_E_INVALID, "%s: handle %lld was made for device %d, the current device is %d", what,
                     (long long)k->handle, k->device, dev);
   const int r = merge_dims(nops, strides, shape, rank, a.st, a.shape);
   for (int i = 0; i < nops; i++) a.p[i] = ptrs[i];
@@ -490,7 +490,7 @@ int laser_hip_foreach_code(const char *body, int nops, const char *const *names,
                            int64_t cap, int64_t *len) {
   Spec sp;
   if (int rc = make_spec(sp, body, nops, names, dtypes, writable, nparams, param_names, param_dtypes)) return rc;
-  if (!arch) return api_fail(LASER_HIP_E_INVALID, "foreach: null architecture");
+  if (!arch) return fail(LASER_HIP_E_INVALID, "foreach: null architecture");
   std::vector<char> code;
   if (int rc = compile(sp, arch, code)) return rc;
   return copy_out(code.data(), (int64_t)code.size(), buf, cap, len);
@@ -532,12 +532,12 @@ int laser_hip_foreach_dev(int64_t handle, void *const *ptrs, const int64_t *stri
       a.chunks = (a.inner + 1023) / 1024;
       blocks = a.rows * a.chunks;
     }
-    if (blocks > 0x7fffffffLL) return api_fail(LASER_HIP_E_INVALID, "foreach: %lld workgroups (too many)", (long long)blocks);
+    if (blocks > 0x7fffffffLL) return fail(LASER_HIP_E_INVALID, "foreach: %lld workgroups (too many)", (long long)blocks);
   }
   size_t sz = sizeof a;
   void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   const hipError_t e = hipModuleLaunchKernel(k->fn[variant], (unsigned)blocks, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, nullptr, extra);
-  if (e != hipSuccess) return api_fail(LASER_HIP_E_HIP, "foreach: launch of %s failed: %s", kKernelName[variant], hipGetErrorString(e));
+  if (e != hipSuccess) return fail(LASER_HIP_E_HIP, "foreach: launch of %s failed: %s", kKernelName[variant], hipGetErrorString(e));
   g_last_variant = variant;
   return LASER_HIP_OK;
 }
@@ -563,7 +563,7 @@ int laser_hip_foreach_reduce_code(const char *body, int nops, const char *const 
   if (int rc = make_reduce_spec(sp, body, nops, names, dtypes, writable, nparams, param_names, param_dtypes, acc_name,
                                 acc_dtype, merge))
     return rc;
-  if (!arch) return api_fail(LASER_HIP_E_INVALID, "foreach_reduce: null architecture");
+  if (!arch) return fail(LASER_HIP_E_INVALID, "foreach_reduce: null architecture");
   std::vector<char> code;
   if (int rc = compile(sp, arch, code)) return rc;
   return copy_out(code.data(), (int64_t)code.size(), buf, cap, len);
@@ -584,7 +584,7 @@ int laser_hip_foreach_reduce_dev(int64_t handle, void *const *ptrs, const int64_
                                  int rank, const void *params, const void *init, void *d_out, void *stream) {
   Kernel *k = nullptr;
   if (int rc = kernel_of(handle, true, &k)) return rc;
-  if (!init || !d_out) return api_fail(LASER_HIP_E_INVALID, "foreach_reduce: null init / output");
+  if (!init || !d_out) return fail(LASER_HIP_E_INVALID, "foreach_reduce: null init / output");
   ReduceArgs r = {};
   int variant = 0;
   int64_t total = 0;
@@ -592,7 +592,7 @@ int laser_hip_foreach_reduce_dev(int64_t handle, void *const *ptrs, const int64_
   if (total == 0) {  // no operand is read: a launch of the partials kernel over nothing writes init
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev != k->device)
-      return api_fail(LASER_HIP_E_INVALID, "foreach_reduce: handle %lld was made for device %d, the current device is %d",
+      return fail(LASER_HIP_E_INVALID, "foreach_reduce: handle %lld was made for device %d, the current device is %d",
                       (long long)handle, k->device, dev);
     variant = 3;
   }
@@ -616,7 +616,7 @@ int laser_hip_foreach_reduce_dev(int64_t handle, void *const *ptrs, const int64_
     return launch(3, p, blocks);
   };
   const hipError_t e = reduce_levels(total, total ? k->vec : 16 / k->acc_size, k->acc_size, d_out, s, level0, partials);
-  if (e != hipSuccess) return api_fail(LASER_HIP_E_HIP, "foreach_reduce: launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(LASER_HIP_E_HIP, "foreach_reduce: launch failed: %s", hipGetErrorString(e));
   if (total) g_last_variant = variant;
   return LASER_HIP_OK;
 }

@@ -53,7 +53,7 @@ constexpr int kMaxRanks = 16;
   do {                                                                                                                \
     hipError_t e_ = (expr);                                                                                           \
     if (e_ != hipSuccess)                                                                                             \
-      return api_fail(LASER_HIP_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);    \
+      return fail(LASER_HIP_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);    \
   } while (0)
 
 struct Plan {
@@ -201,13 +201,13 @@ int rank_setup(int r, int device, int ndev, int nev) {
 
 int device_list(int ndev, const int *devices, std::vector<int> *out) {
   int have = 0;
-  if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) return api_fail(LASER_HIP_E_NODEVICE, "no HIP device available");
+  if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) return fail(LASER_HIP_E_NODEVICE, "no HIP device available");
   if (ndev <= 0) ndev = have;  // "all of them"
-  if (ndev > kMaxRanks) return api_fail(LASER_HIP_E_INVALID, "more than %d devices", kMaxRanks);
+  if (ndev > kMaxRanks) return fail(LASER_HIP_E_INVALID, "more than %d devices", kMaxRanks);
   out->resize(ndev);
   for (int g = 0; g < ndev; g++) {
     const int d = devices ? devices[g] : g;
-    if (d < 0 || d >= have) return api_fail(LASER_HIP_E_INVALID, "device %d out of range (%d devices)", d, have);
+    if (d < 0 || d >= have) return fail(LASER_HIP_E_INVALID, "device %d out of range (%d devices)", d, have);
     (*out)[g] = d;
   }
   return LASER_HIP_OK;
@@ -251,10 +251,10 @@ int rccl_load() {
   void *h = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
   if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
   if (!h) h = dlopen("/opt/rocm/lib/librccl.so", RTLD_NOW | RTLD_LOCAL);
-  if (!h) return api_fail(LASER_HIP_E_INVALID, "gather mode RCCL: cannot load librccl.so (%s)", dlerror());
+  if (!h) return fail(LASER_HIP_E_INVALID, "gather mode RCCL: cannot load librccl.so (%s)", dlerror());
 #define LD(field, name)                                                                          \
   *(void **)(&g_rccl.field) = dlsym(h, name);                                                    \
-  if (!g_rccl.field) return api_fail(LASER_HIP_E_INVALID, "librccl.so has no symbol %s", name);
+  if (!g_rccl.field) return fail(LASER_HIP_E_INVALID, "librccl.so has no symbol %s", name);
   LD(CommInitAll, "ncclCommInitAll")
   LD(CommDestroy, "ncclCommDestroy")
   LD(CommAbort, "ncclCommAbort")
@@ -277,7 +277,7 @@ int rccl_comms(const std::vector<int> &dev) {
   const int r = g_rccl.CommInitAll(g_rccl.comms.data(), (int)dev.size(), dev.data());
   if (r != 0) {
     g_rccl.comms.clear();
-    return api_fail(LASER_HIP_E_HIP, "ncclCommInitAll over %d devices failed: %s", (int)dev.size(), g_rccl.GetErrorString(r));
+    return fail(LASER_HIP_E_HIP, "ncclCommInitAll over %d devices failed: %s", (int)dev.size(), g_rccl.GetErrorString(r));
   }
   g_rccl.devs = dev;
   return LASER_HIP_OK;
@@ -355,19 +355,19 @@ template <typename T>
 int sharded_dev(int ndev_in, const int *devices, int64_t M, int64_t N, int64_t K, T alpha, const T *const *dA,
                 int64_t rsA, int64_t csA, const T *const *dB, int64_t rsB, int64_t csB, T beta, T *const *dC,
                 int64_t rsC, int panels_per_dev, int gather, int flags) {
-  if (M < 0 || N < 0 || K < 0) return api_fail(LASER_HIP_E_INVALID, "negative dimension");
-  if (gather < LASER_HIP_GATHER_NONE || gather > LASER_HIP_GATHER_RCCL) return api_fail(LASER_HIP_E_INVALID, "unknown gather mode %d", gather);
-  if (!dA || !dB || !dC) return api_fail(LASER_HIP_E_INVALID, "null pointer table");
-  if (int rc = api_ensure_init()) return rc;
+  if (M < 0 || N < 0 || K < 0) return fail(LASER_HIP_E_INVALID, "negative dimension");
+  if (gather < LASER_HIP_GATHER_NONE || gather > LASER_HIP_GATHER_RCCL) return fail(LASER_HIP_E_INVALID, "unknown gather mode %d", gather);
+  if (!dA || !dB || !dC) return fail(LASER_HIP_E_INVALID, "null pointer table");
+  if (int rc = ensure_init()) return rc;
   std::vector<int> dev;
   if (int rc = device_list(ndev_in, devices, &dev)) return rc;
   const int ndev = (int)dev.size();
   if (M == 0 || N == 0 || K == 0) return LASER_HIP_OK;  // K == 0: C untouched (gemm.nim:150)
-  if (rsC < N) return api_fail(LASER_HIP_E_INVALID, "sharded C is row-major: rowStrideC (%lld) < N (%lld)", (long long)rsC, (long long)N);
+  if (rsC < N) return fail(LASER_HIP_E_INVALID, "sharded C is row-major: rowStrideC (%lld) < N (%lld)", (long long)rsC, (long long)N);
   if (gather == LASER_HIP_GATHER_RCCL && rsC != N)
-    return api_fail(LASER_HIP_E_INVALID, "gather mode RCCL needs a dense C (rowStrideC == N): slabs are sent as flat buffers");
+    return fail(LASER_HIP_E_INVALID, "gather mode RCCL needs a dense C (rowStrideC == N): slabs are sent as flat buffers");
   for (int g = 0; g < ndev; g++)
-    if (!dA[g] || !dB[g] || !dC[g]) return api_fail(LASER_HIP_E_INVALID, "null operand pointer for device slot %d", g);
+    if (!dA[g] || !dB[g] || !dC[g]) return fail(LASER_HIP_E_INVALID, "null operand pointer for device slot %d", g);
   const Plan plan = make_plan(M, ndev, panels_per_dev);
   std::lock_guard<std::mutex> lk(g_shard_mu);
   int prev_dev = 0;
@@ -408,7 +408,7 @@ int sharded_dev(int ndev_in, const int *devices, int64_t M, int64_t N, int64_t K
     RankCtx &R = g_rank[g];
     hipError_t e = hipSetDevice(dev[g]);
     const bool no_device = e != hipSuccess;      // then no stream / event call below may run (it would land on whatever device is current)
-    if (no_device) bail(api_fail(LASER_HIP_E_HIP, "hipSetDevice(%d): %s", dev[g], hipGetErrorString(e)));
+    if (no_device) bail(fail(LASER_HIP_E_HIP, "hipSetDevice(%d): %s", dev[g], hipGetErrorString(e)));
     if (pin) api_set_thread_asm_tile(pin_tile);
     // one device and nothing to exchange: the panels are one contiguous matrix -- one product, no per-panel launch boundary
     const bool whole = ndev == 1 && gather != LASER_HIP_GATHER_RCCL && !no_device;
@@ -432,7 +432,7 @@ int sharded_dev(int ndev_in, const int *devices, int64_t M, int64_t N, int64_t K
       }
       if (gather == LASER_HIP_GATHER_NONE || (ndev == 1 && gather != LASER_HIP_GATHER_RCCL)) continue;
       e = hipEventRecord(R.ev[s], R.comp);
-      if (e != hipSuccess) bail(api_fail(LASER_HIP_E_HIP, "hipEventRecord: %s", hipGetErrorString(e)));
+      if (e != hipSuccess) bail(fail(LASER_HIP_E_HIP, "hipEventRecord: %s", hipGetErrorString(e)));
       if (gather == LASER_HIP_GATHER_PEER) {
         if (valid <= 0 || rc[g] != LASER_HIP_OK) continue;
         for (int p = 0; p < ndev; p++) {
@@ -447,18 +447,18 @@ int sharded_dev(int ndev_in, const int *devices, int64_t M, int64_t N, int64_t K
                                    (size_t)N * sizeof(T), (size_t)valid, hipMemcpyDeviceToDevice, R.peer[p]);
           }
           if (e != hipSuccess) {
-            bail(api_fail(LASER_HIP_E_HIP, "peer copy %d -> %d: %s", dev[g], dev[p], hipGetErrorString(e)));
+            bail(fail(LASER_HIP_E_HIP, "peer copy %d -> %d: %s", dev[g], dev[p], hipGetErrorString(e)));
             break;
           }
         }
       } else {  // RCCL: in-place all-gather of slab s (sub-panel s of every rank = one contiguous block of C)
         e = hipStreamWaitEvent(R.comm, R.ev[s], 0);
-        if (e != hipSuccess) bail(api_fail(LASER_HIP_E_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) bail(fail(LASER_HIP_E_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e)));
         T *slab = dC[g] + (int64_t)s * ndev * plan.rows * N;
         const int r = g_rccl.AllGather(slab + (int64_t)g * plan.rows * N, slab, (size_t)plan.rows * N, NcclType<T>::v,
                                        g_rccl.comms[g], R.comm);
         if (r != 0) {  // the collective itself is broken: nobody may wait for it
-          bail(api_fail(LASER_HIP_E_HIP, "ncclAllGather (rank %d): %s", g, g_rccl.GetErrorString(r)));
+          bail(fail(LASER_HIP_E_HIP, "ncclAllGather (rank %d): %s", g, g_rccl.GetErrorString(r)));
           break;
         }
       }
@@ -472,7 +472,7 @@ int sharded_dev(int ndev_in, const int *devices, int64_t M, int64_t N, int64_t K
       for (int p = 0; p < ndev && e == hipSuccess; p++)
         if (p != g) e = sync_bounded(R.peer[p], false);
     if (e == hipSuccess && gather == LASER_HIP_GATHER_RCCL) e = sync_bounded(R.comm, coll);
-    if (e != hipSuccess) bail(api_fail(LASER_HIP_E_HIP, "synchronising device %d: %s", dev[g], hipGetErrorString(e)));
+    if (e != hipSuccess) bail(fail(LASER_HIP_E_HIP, "synchronising device %d: %s", dev[g], hipGetErrorString(e)));
   };
   pool().run(ndev, worker);
   if (failed) {
@@ -483,7 +483,7 @@ int sharded_dev(int ndev_in, const int *devices, int64_t M, int64_t N, int64_t K
   }
   (void)hipSetDevice(prev_dev);
   for (int g = 0; g < ndev; g++)
-    if (rc[g] != LASER_HIP_OK) return api_fail(rc[g], "device slot %d: %s", g, msg[g].c_str());
+    if (rc[g] != LASER_HIP_OK) return fail(rc[g], "device slot %d: %s", g, msg[g].c_str());
   return LASER_HIP_OK;
 }
 
@@ -491,12 +491,12 @@ int sharded_dev(int ndev_in, const int *devices, int64_t M, int64_t N, int64_t K
 template <typename T>
 int sharded_host(int ndev_in, const int *devices, int64_t M, int64_t N, int64_t K, T alpha, const T *A, int64_t rsA,
                  int64_t csA, const T *B, int64_t rsB, int64_t csB, T beta, T *C, int64_t rsC, int64_t csC) {
-  if (M < 0 || N < 0 || K < 0) return api_fail(LASER_HIP_E_INVALID, "negative dimension");
-  if (int rc = api_ensure_init()) return rc;
+  if (M < 0 || N < 0 || K < 0) return fail(LASER_HIP_E_INVALID, "negative dimension");
+  if (int rc = ensure_init()) return rc;
   std::vector<int> dev;
   if (int rc = device_list(ndev_in, devices, &dev)) return rc;
   if (M == 0 || N == 0 || K == 0) return LASER_HIP_OK;
-  if (!A || !B || !C) return api_fail(LASER_HIP_E_INVALID, "null operand pointer");
+  if (!A || !B || !C) return fail(LASER_HIP_E_INVALID, "null operand pointer");
   int ndev = (int)dev.size();
   // Every worker stages the memory SPAN of its share of C (upload when the span has gaps it does not own, copy the
   // whole span back): two workers' spans must therefore never overlap.  Row ranges are disjoint in memory only when the
@@ -530,7 +530,7 @@ int sharded_host(int ndev_in, const int *devices, int64_t M, int64_t N, int64_t 
     pool().run(ndev, worker);
   }
   for (int g = 0; g < ndev; g++)
-    if (rc[g] != LASER_HIP_OK) return api_fail(rc[g], "device %d: %s", dev[g], msg[g].c_str());
+    if (rc[g] != LASER_HIP_OK) return fail(rc[g], "device %d: %s", dev[g], msg[g].c_str());
   return LASER_HIP_OK;
 }
 
@@ -557,7 +557,7 @@ extern "C" {
 
 int laser_hip_shard_plan(int64_t M, int ndev, int panels_per_dev, int64_t *rows_per_panel, int *panels_per_dev_used,
                          int64_t *padded_M) {
-  if (M < 0 || ndev < 1 || ndev > kMaxRanks) return api_fail(LASER_HIP_E_INVALID, "shard_plan: bad argument");
+  if (M < 0 || ndev < 1 || ndev > kMaxRanks) return fail(LASER_HIP_E_INVALID, "shard_plan: bad argument");
   const Plan p = make_plan(M, ndev, panels_per_dev);
   if (rows_per_panel) *rows_per_panel = p.rows;
   if (panels_per_dev_used) *panels_per_dev_used = p.ppd;

@@ -26,12 +26,12 @@ every digit product is +2^14 and G_{L-1} (L = n / 8 digits) is L * K * 2^14: exa
 import numpy as np
 
 # K summed into one int32 accumulator group between two folds
-CHUNK = {8: 16384,      # gemm_narrow_mfma.hip:25 NARROW_MAX_K (capi.cpp run_gemm_narrow cuts longer K with int_gemm_k_chunks)
+CHUNK = {8: 16384,      # gemm_narrow_mfma.hip:25 NARROW_MAX_K (gemm_route.cpp run_gemm_int cuts longer K with int_gemm_k_chunks)
          16: 16384,
          32: 8192,      # gemm_i32_mfma.hip:49 IFOLD_K (folded inside the kernel); asmgen/i8_kernel.py:18 K <= 8192 per launch
-         64: 8192}      # gemm_i64_mfma.hip:13-14 (chunks cut by the launcher); capi.cpp int_gemm_k_chunks kChunk
+         64: 8192}      # gemm_i64_mfma.hip:13-14 (chunks cut by the launcher); gemm_route.cpp int_gemm_k_chunks kChunk
 BOUND = {8: 2 ** 28, 16: 2 ** 29, 32: 2 ** 29, 64: 2 ** 30}      # L * CHUNK * 2^14
-M = N = 160     # ragged against the 128 and 64 tiles; 160 * 160 * K is above the matrix-core work threshold (capi.cpp: 64^3 * 8)
+M = N = 160     # ragged against the 128 and 64 tiles; 160 * 160 * K is above the matrix-core work threshold (gemm_route.cpp: 64^3 * 8)
 DTYPES = [np.int8, np.uint8, np.int16, np.uint16, np.int32, np.uint32, np.int64, np.uint64]
 
 
