@@ -496,7 +496,7 @@ Acc forEachReduce(const std::string &body, const std::string &merge, Acc init, c
 }
 
 // ---- exp and row softmax (include/laser_hip.h "exp and row softmax"): simd_math/exp_log_*.nim over device Tensors ---------
-//   laser::exp(y, x);  laser::softmax(y, x);     (asynchronous on `stream`; y may be x)
+//   laser::exp(y, x);  laser::softmax(y, x);  laser::softmax_axis(y, x, axis);     (asynchronous on `stream`; y may be x)
 // exp: Laser's table-driven exp, bit for bit; x broadcasts against y.  softmax: over the rows of a 2-D Tensor whose last
 // stride is 1, summed in the fixed order of the reductions.
 inline void exp(Tensor<float> &dst, const Tensor<float> &src, void *stream = nullptr) {
@@ -538,6 +538,50 @@ inline void softmax(Tensor<float> &dst, const Tensor<float> &src, void *stream =
 inline Tensor<float> softmax(const Tensor<float> &src, void *stream = nullptr) {
   Tensor<float> dst = exp_result_like(src);
   softmax(dst, src, stream);
+  return dst;
+}
+// softmax along `axis` (negative counts from the end) of a Tensor of rank 1 .. 6: every 1-D slice along the axis exactly as a
+// row of softmax above.  In dst and in src the dims before the axis must collapse into one stride and the dims after it into
+// one unit-stride run (any row-major Tensor does).  (Not an overload of softmax: a literal 0 stream would turn into an axis.)
+namespace detail {
+// the (extent, stride) pairs [first, last) as one dimension: false when they do not collapse; extent-1 dims do not count
+inline bool collapse(const std::vector<int64_t> &shape, const std::vector<int64_t> &strides, int first, int last, int64_t &count,
+                     int64_t &stride) {
+  count = 1;
+  stride = 0;
+  bool any = false;
+  int64_t below = 0;  // extent * stride of the dimension before
+  for (int d = last - 1; d >= first; d--) {
+    if (shape[d] == 1) continue;
+    if (any && strides[d] != below) return false;
+    if (!any) stride = strides[d];
+    any = true;
+    below = strides[d] * shape[d];
+    count *= shape[d];
+  }
+  return true;
+}
+}  // namespace detail
+inline void softmax_axis(Tensor<float> &dst, const Tensor<float> &src, int axis, void *stream = nullptr) {
+  const int r = src.rank();
+  if (r < 1 || r > 6 || dst.shape != src.shape) throw Error(LASER_HIP_E_INVALID, "softmax_axis: two tensors of one shape, rank 1 .. 6");
+  if (axis < -r || axis >= r) throw Error(LASER_HIP_E_INVALID, "softmax_axis: axis outside the rank");
+  if (axis < 0) axis += r;
+  const int64_t n = src.shape[axis];
+  int64_t outer, inner, d_os, s_os, d_in, s_in, c2;
+  if (!detail::collapse(src.shape, src.strides, 0, axis, outer, s_os) || !detail::collapse(dst.shape, dst.strides, 0, axis, c2, d_os) ||
+      !detail::collapse(src.shape, src.strides, axis + 1, r, inner, s_in) || !detail::collapse(dst.shape, dst.strides, axis + 1, r, c2, d_in) ||
+      (inner > 1 && (s_in != 1 || d_in != 1)))
+    throw Error(LASER_HIP_E_INVALID, "softmax_axis: the dims before the axis must collapse into one stride, the dims after it into one "
+                                     "unit-stride run (make the tensor contiguous)");
+  if (n < 1) throw Error(LASER_HIP_E_INVALID, "softmax_axis: empty axis");
+  if (inner == 0) return;
+  const int64_t d_as = n > 1 ? dst.strides[axis] : inner, s_as = n > 1 ? src.strides[axis] : inner;
+  check(laser_hip_softmax_axis_f32_dev(dst.unsafe_raw_data(), d_os, d_as, src.unsafe_raw_data(), s_os, s_as, outer, n, inner, stream));
+}
+inline Tensor<float> softmax_axis(const Tensor<float> &src, int axis, void *stream = nullptr) {
+  Tensor<float> dst = exp_result_like(src);
+  softmax_axis(dst, src, axis, stream);
   return dst;
 }
 

@@ -165,7 +165,8 @@ int laser_hip_f32_config_count(void);
  *   "last_foreach_variant"  kernel of the last laser_hip_foreach_dev / foreach_reduce_dev launch: 0 contiguous vectorised, 1 contiguous
  *                      scalar, 2 strided
  *   "last_reduce_variant"  traversal of the last laser_hip_reduce_* call: 0 contiguous vectorised, 1 contiguous scalar, 2 strided
- *   "last_softmax_kernel"  kernel of the last laser_hip_softmax_rows_f32_dev call (see the softmax section below)
+ *   "last_softmax_kernel"  kernel of the last laser_hip_softmax_rows_f32_dev / _axis_f32_dev call (0 - 2 rows, 8 - 9 column
+ *                          strips, + 4 single-element accesses; see the softmax section below)
  *   "shard_rccl_ranks" ranks of the RCCL communicator the last GATHER_RCCL sharded call used, as the communicator reports it; 0 = none yet */
 int laser_hip_set_option(const char *name, int value);
 int laser_hip_get_option(const char *name, int64_t *value);
@@ -620,13 +621,44 @@ int laser_hip_reduce_max_f32(const float *data, int64_t len, float *out);
  *   with equal row strides allowed; anything else LASER_HIP_E_INVALID.  Asynchronous on `stream`.
  *   get_option "last_softmax_kernel": 0 = one wave per row (n <= 1024), 1 = one workgroup per row (n <= 8192), 2 = long
  *   rows; + 4 when a base or a row stride is off its 16-byte alignment (single-element accesses) -- same bits all six.
+ * laser_hip_softmax_axis_f32_dev: the same softmax along any axis.  The operand is viewed as (outer, n, inner): element
+ *   x[o, k, i] is at d_src + o * src_outer_stride + k * src_axis_stride + i (ELEMENT strides; the inner index has stride 1),
+ *   and for every (o, i) the 1-D array x[o, 0..n, i] gets exactly steps 1-4 above, the sum in the order of "Reductions"
+ *   applied to that array as a 1-D array of n float32.  Bit for bit (any NaN equals any NaN)
+ *     softmax_axis(X, axis) == moveaxis(softmax_rows(moveaxis(X, axis, -1) made contiguous), -1, axis):
+ *   a column's bits never depend on its neighbours, on outer, inner, the strides, the base alignment, the strip width, the
+ *   grid or the stream; a NaN column, an all -Inf column or a +Inf maximum makes that column NaN and no other.
+ *   The sum tree in terms of k: within a chunk of 8192 elements, element k goes to leaf a = k mod 1024; a leaf starts at +0
+ *   and takes its up to 8 elements in ascending k; the 1024 leaves are folded by adding the higher index into the lower for
+ *   index pairs that differ in bit 1, then bit 0, then bit 9, 8, .., 2; the chunk partials (at most 128 here) are folded by
+ *   the same rule as one more such array.
+ *   Valid: outer >= 0 (0: nothing happens), n >= 1, inner >= 1, both axis strides >= inner and, for outer > 1, both outer
+ *   strides >= (n - 1) * axis_stride + inner; dst == src with equal strides allowed (any other overlap is not); any base
+ *   alignment.  inner == 1 with both axis strides 1 forwards to the row kernels (n <= 2^26); otherwise
+ *   n <= LASER_HIP_SOFTMAX_AXIS_MAX_N (one workgroup walks a whole column; past that: LASER_HIP_E_INVALID, and the text says
+ *   so).  Asynchronous on `stream`.  A workgroup owns a strip of CW consecutive inner positions of one outer index over all
+ *   n, every access a run of CW * 4 contiguous bytes per row.
+ *   get_option "last_softmax_kernel" after it: 8 = column strip, column resident (n <= 2048: one read, one write),
+ *   9 = column strip, streaming (three reads, one write); + 4 for the single-element instance (a base or a stride off its
+ *   16-byte alignment); 0 - 2 (+ 4) when it forwarded to the row kernels.
+ * laser_hip_softmax_axis_plan: what the call above would launch for a shape, without a device: out4 = {kernel code, strip
+ *   width CW (0 for the row kernels), workgroups, LDS bytes}.  vec: 1 when bases and strides allow 16-byte vectors; cus: the
+ *   device's compute units, taken for symmetry with laser_hip_plan_f32: the grid is min(2048, strips) on every device and
+ *   does not depend on it.  inner == 1 is planned with unit axis strides.  The logic is laser_amd/csrc/softmax_axis_plan.h, which has no HIP dependency.
+ * Not built: float64, splitting one long column over several workgroups (few strips x long n keeps few compute units
+ *   busy), backward.
  * No gfx950 device: LASER_HIP_E_NODEVICE. */
 #define LASER_HIP_SOFTMAX_MAX_N (1ll << 26)
+#define LASER_HIP_SOFTMAX_AXIS_MAX_N (1ll << 20)   /* for inner > 1 */
 int laser_hip_exp_f32_dev(float *d_dst, const int64_t *dst_strides, const float *d_src, const int64_t *src_strides,
                           const int64_t *shape, int rank, void *stream);
 int laser_hip_exp_f32(float *dst, const float *src, int64_t len);
 int laser_hip_softmax_rows_f32_dev(float *d_dst, int64_t dst_row_stride, const float *d_src, int64_t src_row_stride,
                                    int64_t rows, int64_t n, void *stream);
+int laser_hip_softmax_axis_f32_dev(float *d_dst, int64_t dst_outer_stride, int64_t dst_axis_stride,
+                                   const float *d_src, int64_t src_outer_stride, int64_t src_axis_stride,
+                                   int64_t outer, int64_t n, int64_t inner, void *stream);
+int laser_hip_softmax_axis_plan(int64_t outer, int64_t n, int64_t inner, int vec, int cus, int64_t *out4);
 
 /* ---- forEachReduce: forEach with a private accumulator per lane, merged at the end ---------------------------------
  * The device form of forEachStaged (laser/strided_iteration/foreach_staged.nim:318), e.g. a dot product:

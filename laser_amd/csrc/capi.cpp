@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "softmax_axis_plan.h"
 
 using namespace laser_hip;
 
@@ -1382,6 +1383,51 @@ int laser_hip_softmax_rows_f32_dev(float *dst, int64_t dst_row_stride, const flo
   if (rows == 0) return LASER_HIP_OK;
   if (!dst || !src) return fail(LASER_HIP_E_INVALID, "softmax: null buffer");
   HIP_TRY(launch_softmax_rows_f32(dst, dst_row_stride, src, src_row_stride, rows, n, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+
+int laser_hip_softmax_axis_f32_dev(float *dst, int64_t dst_outer_stride, int64_t dst_axis_stride, const float *src,
+                                   int64_t src_outer_stride, int64_t src_axis_stride, int64_t outer, int64_t n, int64_t inner,
+                                   void *stream) {
+  if (n < 1 || inner < 1 || outer < 0)
+    return fail(LASER_HIP_E_INVALID, "softmax_axis: outer %lld, n %lld, inner %lld (outer >= 0, n >= 1, inner >= 1)", (long long)outer,
+                (long long)n, (long long)inner);
+  if (dst_axis_stride < inner || src_axis_stride < inner)
+    return fail(LASER_HIP_E_INVALID, "softmax_axis: axis strides %lld / %lld below inner %lld", (long long)dst_axis_stride,
+                (long long)src_axis_stride, (long long)inner);
+  const bool rows = inner == 1 && dst_axis_stride == 1 && src_axis_stride == 1;
+  if (n > (rows ? LASER_HIP_SOFTMAX_MAX_N : LASER_HIP_SOFTMAX_AXIS_MAX_N))
+    return fail(LASER_HIP_E_INVALID,
+                rows ? "softmax_axis: axis length %lld outside 1..2^26"
+                     : "softmax_axis: axis length %lld past 2^20 on a strided axis (one workgroup walks a whole column; splitting a "
+                       "column over workgroups is not built)",
+                (long long)n);
+  if (outer > 1) {
+    const __int128 ext_d = (__int128)(n - 1) * dst_axis_stride + inner, ext_s = (__int128)(n - 1) * src_axis_stride + inner;
+    if (dst_outer_stride < ext_d || src_outer_stride < ext_s)
+      return fail(LASER_HIP_E_INVALID, "softmax_axis: outer strides %lld / %lld below (n - 1) * axis stride + inner",
+                  (long long)dst_outer_stride, (long long)src_outer_stride);
+  }
+  if (dst == src && (dst_axis_stride != src_axis_stride || (outer > 1 && dst_outer_stride != src_outer_stride)))
+    return fail(LASER_HIP_E_INVALID, "softmax_axis: in place needs equal strides");
+  if (int rc = ensure_init()) return rc;
+  if (outer == 0) return LASER_HIP_OK;
+  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "softmax_axis: null buffer");
+  if (rows)  // a single row has no row stride to speak of
+    HIP_TRY(launch_softmax_rows_f32(dst, outer > 1 ? dst_outer_stride : n, src, outer > 1 ? src_outer_stride : n, outer, n,
+                                    (hipStream_t)stream));
+  else
+    HIP_TRY(launch_softmax_axis_f32(dst, dst_outer_stride, dst_axis_stride, src, src_outer_stride, src_axis_stride, outer, n, inner,
+                                    (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_softmax_axis_plan(int64_t outer, int64_t n, int64_t inner, int vec, int cus, int64_t *out4) {
+  if (!out4) return fail(LASER_HIP_E_INVALID, "softmax_axis_plan: null out4");
+  long long p[4];
+  if (lh_softmax_axis_plan(outer, n, inner, vec, cus, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "softmax_axis_plan: outer %lld, n %lld, inner %lld outside what softmax_axis takes", (long long)outer,
+                (long long)n, (long long)inner);
+  for (int i = 0; i < 4; i++) out4[i] = p[i];
   return LASER_HIP_OK;
 }
 

@@ -280,6 +280,10 @@ hipError_t launch_exp_f32(float *dst, const int64_t *dstrides, const float *src,
                           int rank, hipStream_t s);
 hipError_t launch_softmax_rows_f32(float *dst, int64_t dstride, const float *src, int64_t sstride, int64_t rows, int64_t n,
                                    hipStream_t s);
+// the softmax along a strided axis of (outer, n, inner), inner unit-stride (softmax_axis.hip; softmax_axis_plan.h picks the kernel)
+hipError_t launch_softmax_axis_f32(float *dst, int64_t dst_outer_stride, int64_t dst_axis_stride, const float *src,
+                                   int64_t src_outer_stride, int64_t src_axis_stride, int64_t outer, int64_t n, int64_t inner,
+                                   hipStream_t s);
 extern std::atomic<int> g_last_softmax_kernel;
 template <typename T>
 hipError_t launch_pack_pad(T *dst, int64_t Rpad, int64_t Cpad, const T *src, int64_t R,

@@ -3,6 +3,8 @@
 
     laser_amd.exp(t)        lexp of every element: the exported SIMD `exp*` of the reference, bit for bit
     laser_amd.softmax(t)    softmax over the rows of a 2-D tensor, summed in the fixed order of the reductions
+    laser_amd.softmax(t, axis=k)   the same along any axis of a tensor of rank 1 .. 6: bit for bit what the row form gives the
+                            same values as rows (not built: float64, backward)
 
 An operand is a laser_amd.Tensor or a torch CUDA tensor (anything with __cuda_array_interface__); `exp` also takes a host
 float32 numpy array, like the reference's benchmark loop.  With out=None a device call returns a fresh row-major Tensor;
@@ -47,9 +49,46 @@ def exp(t, out=None):
     return out
 
 
-def softmax(t, out=None):
+def _collapse(dims):
+    """(count, stride) of the (extent, stride) pairs `dims` as one dimension, None when they do not collapse into one;
+    extent-1 dimensions do not count, and nothing left is (1, None)"""
+    dims = [(e, s) for e, s in dims if e != 1]
+    count = 1
+    for (e, s), (e1, s1) in zip(dims, dims[1:]):
+        if s != s1 * e1:
+            return None
+    for e, _ in dims:
+        count *= e
+    return count, (dims[-1][1] if dims else None)
+
+
+def _axis_view(v, axis):
+    """(outer, outer_stride, axis_stride, inner) of `v` with the softmax along `axis`, as the strip kernels see it (the dims
+    after the axis one unit-stride run) and as the row kernels see it (the axis unit-stride, every other dim one stride);
+    None where the view does not fit"""
+    dims = list(zip(v.shape, v.strides))
+    n, sa = dims[axis]
+    pre, post = _collapse(dims[:axis]), _collapse(dims[axis + 1:])
+    strip = rows = None
+    if pre is not None and post is not None and post[1] in (None, 1):
+        inner = post[0]
+        strip = (pre[0], pre[1] if pre[1] is not None else 0, sa if n > 1 else inner, inner)      # n == 1: no axis stride to speak of
+    others = _collapse(dims[:axis] + dims[axis + 1:])
+    if others is not None and (n == 1 or sa == 1):
+        rows = (others[0], others[1] if others[1] is not None else 0, 1, 1)
+    return strip, rows
+
+
+def softmax(t, out=None, axis=None):
     """Softmax over the rows of the 2-D `t` (last stride 1): y = lexp(x - max) / sum, the sum in the order of reduce_sum, so
-    a row's result depends on its values and length alone.  A NaN in a row, or a row of all -Inf, gives a NaN row."""
+    a row's result depends on its values and length alone.  A NaN in a row, or a row of all -Inf, gives a NaN row.
+    With `axis` (negative counts from the end) `t` has rank 1 .. 6 and the softmax runs along that axis, every 1-D slice along
+    it exactly as a row above.  The dims before the axis must collapse into one stride and the dims after it into one
+    unit-stride run (any C-contiguous tensor, and slices of one that keep that); or the axis itself has stride 1 and all
+    other dims collapse into one stride (the rows of a transposed view; `out` must then be such a view too).  Anything else:
+    ValueError -- make it contiguous."""
+    if axis is not None:
+        return _softmax_axis(t, out, axis)
     src = _f32("t", t)
     if out is None:
         out = newTensor(np.float32, *src.shape)
@@ -68,3 +107,30 @@ def softmax(t, out=None):
     ds, ss = (dst.strides[0], src.strides[0]) if rows > 1 else (n, n)
     _lib.check(_lib.lib().laser_hip_softmax_rows_f32_dev(C.c_void_p(dst.ptr), ds, C.c_void_p(src.ptr), ss, rows, n, _stream()))
     return out
+
+
+def _softmax_axis(t, out, axis):
+    src = _f32("t", t)
+    if not 1 <= src.rank <= 6:
+        raise ValueError(f"softmax: t has rank {src.rank} (1 .. 6 with axis=)")
+    if not isinstance(axis, (int, np.integer)) or not -src.rank <= axis < src.rank:
+        raise ValueError(f"softmax: axis {axis!r} outside a tensor of rank {src.rank}")
+    axis = int(axis) % src.rank
+    if out is None:
+        out = newTensor(np.float32, *src.shape)
+    dst = _f32("out", out)
+    if dst.shape != src.shape:
+        raise ValueError(f"softmax: out has shape {dst.shape}, t has {src.shape}")
+    n = src.shape[axis]
+    if n < 1:
+        raise ValueError("softmax: empty axis")
+    if 0 in src.shape:
+        return out
+    for s, d in zip(_axis_view(src, axis), _axis_view(dst, axis)):
+        if s is not None and d is not None:
+            _lib.check(_lib.lib().laser_hip_softmax_axis_f32_dev(C.c_void_p(dst.ptr), d[1], d[2], C.c_void_p(src.ptr), s[1], s[2],
+                                                                 s[0], n, s[3], _stream()))
+            return out
+    raise ValueError(f"softmax: axis {axis} of shapes {src.shape} with strides {src.strides} (t) and {dst.strides} (out): the dims "
+                     "before the axis must collapse into one stride and the dims after it into one unit-stride run, in both "
+                     "(make the tensor contiguous)")

@@ -641,6 +641,8 @@ proc laser_hip_exp_f32(dst: ptr float32, src: ptr float32, len: int64): cint {.l
 # device views (asynchronous on `stream`): element strides, rank <= 6; dst may be src
 proc laser_hip_exp_f32_dev*(dst: ptr float32, dstStrides: ptr int64, src: ptr float32, srcStrides: ptr int64, shape: ptr int64, rank: cint, stream: pointer): cint {.lh, importc: "laser_hip_exp_f32_dev".}
 proc laser_hip_softmax_rows_f32_dev*(dst: ptr float32, dstRowStride: int64, src: ptr float32, srcRowStride: int64, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_softmax_rows_f32_dev".}
+proc laser_hip_softmax_axis_f32_dev*(dst: ptr float32, dstOuterStride: int64, dstAxisStride: int64, src: ptr float32, srcOuterStride: int64, srcAxisStride: int64, outer: int64, n: int64, inner: int64, stream: pointer): cint {.lh, importc: "laser_hip_softmax_axis_f32_dev".}
+proc laser_hip_softmax_axis_plan*(outer: int64, n: int64, inner: int64, vec: cint, cus: cint, out4: ptr int64): cint {.lh, importc: "laser_hip_softmax_axis_plan".}
 
 proc exp*(dst, src: ptr (float32 or UncheckedArray[float32]), len: Natural) =
   ## exp_log_avx2.nim:49-65 over a contiguous range of float32 (host memory; the GPU computes it): dst[i] = exp(src[i])
@@ -649,6 +651,11 @@ proc exp*(dst, src: ptr (float32 or UncheckedArray[float32]), len: Natural) =
 proc softmax*(dst: DevicePtr[float32], dstRowStride: int, src: DevicePtr[float32], srcRowStride: int, rows, n: Natural, stream: pointer = nil) =
   ## softmax over the rows of a device matrix (row elements contiguous, row strides in elements); dst may be src
   check laser_hip_softmax_rows_f32_dev(cast[ptr float32](dst), int64(dstRowStride), cast[ptr float32](src), int64(srcRowStride), int64(rows), int64(n), stream)
+
+proc softmaxAxis*(dst: DevicePtr[float32], dstOuterStride, dstAxisStride: int, src: DevicePtr[float32], srcOuterStride, srcAxisStride: int, outer, n, inner: Natural, stream: pointer = nil) =
+  ## softmax along the middle axis of a device operand viewed as (outer, n, inner): element (o, k, i) at
+  ## o * outerStride + k * axisStride + i (element strides); every column bit for bit what `softmax` gives it as a row
+  check laser_hip_softmax_axis_f32_dev(cast[ptr float32](dst), int64(dstOuterStride), int64(dstAxisStride), cast[ptr float32](src), int64(srcOuterStride), int64(srcAxisStride), int64(outer), int64(n), int64(inner), stream)
 
 # ---- forEachReduce (include/laser_hip.h "forEachReduce"): foreach_staged.nim:318 on device buffers ------------------------
 proc laser_hip_foreach_reduce_source(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, accName: cstring, accDtype: cint, merge: cstring, buf: pointer, cap: int64, len: ptr int64): cint {.lh, importc: "laser_hip_foreach_reduce_source".}
