@@ -585,6 +585,56 @@ inline Tensor<float> softmax_axis(const Tensor<float> &src, int axis, void *stre
   return dst;
 }
 
+// ---- F+tree weighted sampler (include/laser_hip.h "F+tree weighted sampler"): fenwicktree.nim's Sampler, one per row --------
+//   laser::Sampler s(weights);                  weights: a 2-D Tensor<float> whose rows are contiguous (1-D: one row)
+//   s.sample(u);  s.sampleAndRemove(u);         u: a row-major (rows, num) Tensor<float> of numbers in [0, 1) -- the caller's:
+//                                               the library holds no random number generator -> Tensor<int32_t> (rows, num)
+//   s.update(elem, weight);                     one (elem, weight) per row, Tensor<int32_t> / Tensor<float> of `rows` elements
+// Asynchronous on `stream`.  sampleAndRemove and update mutate `tree`.
+struct Sampler {
+  Tensor<float> tree;  // (rows, 2 P): the images
+  int64_t rows = 0, n = 0;
+
+  explicit Sampler(const Tensor<float> &weights, void *stream = nullptr) {
+    const int r = weights.rank();
+    if (r != 1 && r != 2) throw Error(LASER_HIP_E_INVALID, "Sampler: a matrix of weights (or a vector for one row) is needed");
+    rows = r == 2 ? weights.shape[0] : 1;
+    n = weights.shape[r - 1];
+    if (n != 1 && weights.strides[r - 1] != 1) throw Error(LASER_HIP_E_INVALID, "Sampler: the elements of a row must be contiguous");
+    int64_t elems = 0;
+    check(laser_hip_sampler_tree_elems(n, &elems));
+    tree = newTensor<float>({rows, elems});
+    check(laser_hip_sampler_build_f32_dev(tree.unsafe_raw_data(), elems, weights.unsafe_raw_data(), rows > 1 ? weights.strides[0] : n,
+                                          rows, n, stream));
+  }
+  Tensor<int32_t> sample(const Tensor<float> &u, void *stream = nullptr) const {
+    Tensor<int32_t> idx = result_for(u);
+    check(laser_hip_sampler_sample_f32_dev(idx.unsafe_raw_data(), tree.unsafe_raw_data(), tree.shape[1], u.unsafe_raw_data(), rows, n,
+                                           u.shape[1], stream));
+    return idx;
+  }
+  Tensor<int32_t> sampleAndRemove(const Tensor<float> &u, void *stream = nullptr) {
+    Tensor<int32_t> idx = result_for(u);
+    check(laser_hip_sampler_sample_remove_f32_dev(idx.unsafe_raw_data(), tree.unsafe_raw_data(), tree.shape[1], u.unsafe_raw_data(),
+                                                  rows, n, u.shape[1], stream));
+    return idx;
+  }
+  void update(const Tensor<int32_t> &elem, const Tensor<float> &weight, void *stream = nullptr) {
+    if (elem.rank() != 1 || weight.rank() != 1 || elem.shape[0] != rows || weight.shape[0] != rows || !elem.is_C_contiguous() ||
+        !weight.is_C_contiguous())
+      throw Error(LASER_HIP_E_INVALID, "Sampler::update: one contiguous (elem, weight) per row");
+    check(laser_hip_sampler_update_f32_dev(tree.unsafe_raw_data(), tree.shape[1], elem.unsafe_raw_data(), weight.unsafe_raw_data(), rows,
+                                           n, stream));
+  }
+
+ private:
+  Tensor<int32_t> result_for(const Tensor<float> &u) const {
+    if (u.rank() != 2 || u.shape[0] != rows || !u.is_C_contiguous())
+      throw Error(LASER_HIP_E_INVALID, "Sampler: a row-major (rows, num) tensor of uniform numbers is needed");
+    return newTensor<int32_t>({rows, u.shape[1]});
+  }
+};
+
 #undef LASER_DISPATCH
 #undef LASER_GEMM_DISPATCH
 }  // namespace laser

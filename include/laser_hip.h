@@ -660,6 +660,71 @@ int laser_hip_softmax_axis_f32_dev(float *d_dst, int64_t dst_outer_stride, int64
                                    int64_t outer, int64_t n, int64_t inner, void *stream);
 int laser_hip_softmax_axis_plan(int64_t outer, int64_t n, int64_t inner, int vec, int cus, int64_t *out4);
 
+/* ---- F+tree weighted sampler (f32): benchmarks/random_sampling/fenwicktree.nim, bench_multinomial_samplers.nim --------
+ * The reference's `Sampler` over device rows: from a row of weights (the softmax above, or anything non-negative) to drawn
+ * indices without leaving the device.  All float32, every operation rounded to float32 on its own, no denormal flushed.
+ * The library holds no random number generator: the caller supplies the uniform numbers, so every call is a pure function
+ * of its operands.
+ * Tree image of one row of n weights w, 1 <= n <= LASER_HIP_SAMPLER_MAX_N = 2^24.  P = the next power of two >= n; a row is
+ *   2 P elements:
+ *     slot 0      +0
+ *     slot P + i  w[i] for i < n, +0 for n <= i < P
+ *     slot j      slot[2 j] + slot[2 j + 1]  for j = P - 1 .. 1   (one addition of exactly these two; slot 1 is the root)
+ *   The order of summation is this balanced pairwise tree and nothing else, so an image is a function of the row's values and
+ *   n alone, never of rows, the strides, the base alignment, the grid or the stream.  It is the reference's array
+ *   (newSampler, fenwicktree.nim:67-118) shifted up by one slot, image[i + 1] == ref[i] -- the ONE layout deviation: with
+ *   the shift every level and every (left, right) pair starts on an aligned boundary (children 2 j, 2 j + 1, parent j / 2).
+ *   Rows are tree_row_stride elements apart, tree_row_stride >= 2 P; nothing is written past a row's 2 P elements.
+ *   laser_hip_sampler_tree_elems(n, &elems): elems = 2 P.  Needs no device.
+ * Draw for one row and one u01 in [0, 1):
+ *     root = slot[1]; not finite or not > 0 (an all-zero row, a NaN, an Inf): the result is -1.
+ *     u = u01 * root (one multiply); j = 1
+ *     while j < P:  l = slot[2 j], r = slot[2 j + 1];  if u >= l && r > 0: u = u - l, j = 2 j + 1;  else j = 2 j
+ *     the result is j - P.
+ *   Without the `r > 0` test this is sampleImpl (fenwicktree.nim:126-145).  The test is needed: rounding can leave u >= l
+ *   (u01 * root rounds up to the root; a parent rounded below the sum of its children's exact values) under a right subtree
+ *   that sums to 0, and the reference then ends on a zero-weight or padding leaf.  With the test, non-negative finite weights
+ *   and a root > 0: a node > 0 has a child > 0 (x + y > 0 needs x > 0 or y > 0), the descent enters the right child only when
+ *   it is > 0, and the left child only when u < l (so l > 0) or r is not > 0 (so l = node > 0): every node on the path is > 0,
+ *   the leaf too, so 0 <= index < n and w[index] > 0.  The two rules differ only where the reference returns such an
+ *   impossible element (on the host, 460 800 draws over sparse rows scaled by 10^+-30, n in {1, 2, 3, 5, 63, 64, 65, 1000,
+ *   1025, 4097}, u01 random, 0 and 1 - 2^-24: 0 bad results with the test, 128 without).  Negative weights with a finite positive root: whatever the rule reaches (it stays inside
+ *   [0, P)); nothing is promised about it.
+ * Update(row, idx, w): slot[P + idx] = w, then slot[j] = slot[2 j] + slot[2 j + 1] for j = (P + idx) / 2 .. 1 (halving):
+ *   the bits a rebuild would give.  idx = -1 does nothing; any other idx outside [0, n) is skipped (the indices live on the
+ *   device, the host cannot check them).
+ * Draw and remove, k times: for s = 0 .. k - 1: idx = draw(u01[row, s]); store it; update(row, idx, +0) unless it is -1.  Once
+ *   the root is 0 the remaining draws are -1 (sampleAndRemove, fenwicktree.nim:186-199).
+ * laser_hip_sampler_build_f32_dev      d_w: `rows` rows of n weights, w_row_stride >= n elements apart, elements of a row
+ *                                      contiguous, any base alignment; writes rows images.
+ * laser_hip_sampler_sample_f32_dev     m independent draws per row with replacement; d_u01 and d_idx are (rows, m) row-major;
+ *                                      the tree is only read.
+ * laser_hip_sampler_sample_remove_f32_dev   k draws per row without replacement; d_u01 and d_idx are (rows, k) row-major;
+ *                                      MUTATES the tree.  One lane owns a row for the whole launch (k * log2 P dependent
+ *                                      accesses); a concurrent sample on the same tree from another stream is the caller's race.
+ * laser_hip_sampler_update_f32_dev     one (d_elem[row], d_weight[row]) per row; mutates the tree; the same race rule.
+ * All asynchronous on `stream`; pointers are device pointers; indices are int32.  LASER_HIP_E_INVALID, in this order: n
+ *   outside 1 .. 2^24, a negative rows / m / k, tree_row_stride < 2 P, w_row_stride < n; then the device is looked for
+ *   (LASER_HIP_E_NODEVICE without a gfx950); then rows = 0 (or m = 0, k = 0) does nothing; then a null pointer is
+ *   LASER_HIP_E_INVALID.
+ * laser_hip_sampler_plan(rows, n, out4): what the build would launch, without a device: out4 = {kernel: 0 = whole rows in LDS
+ *   (P <= 512), 1 = segments of 1024 leaves plus a second launch for the levels above them; leaves a workgroup owns in one
+ *   step; workgroups of the first launch; workgroups of the second launch (0: none)}.  The logic is
+ *   laser_amd/csrc/sampler_plan.h, which has no HIP dependency.
+ * Not built: float64, weights along an axis other than the last, the benchmark's other sampler (cumsum + searchsorted: a
+ *   parallel float prefix sum is not monotone, so a zero-probability element could be drawn), an on-device RNG, alias tables. */
+#define LASER_HIP_SAMPLER_MAX_N (1ll << 24)
+int laser_hip_sampler_tree_elems(int64_t n, int64_t *elems);
+int laser_hip_sampler_plan(int64_t rows, int64_t n, int64_t *out4);
+int laser_hip_sampler_build_f32_dev(float *d_tree, int64_t tree_row_stride, const float *d_w, int64_t w_row_stride,
+                                    int64_t rows, int64_t n, void *stream);
+int laser_hip_sampler_sample_f32_dev(int32_t *d_idx, const float *d_tree, int64_t tree_row_stride, const float *d_u01,
+                                     int64_t rows, int64_t n, int64_t m, void *stream);
+int laser_hip_sampler_sample_remove_f32_dev(int32_t *d_idx, float *d_tree, int64_t tree_row_stride, const float *d_u01,
+                                            int64_t rows, int64_t n, int64_t k, void *stream);
+int laser_hip_sampler_update_f32_dev(float *d_tree, int64_t tree_row_stride, const int32_t *d_elem, const float *d_weight,
+                                     int64_t rows, int64_t n, void *stream);
+
 /* ---- forEachReduce: forEach with a private accumulator per lane, merged at the end ---------------------------------
  * The device form of forEachStaged (laser/strided_iteration/foreach_staged.nim:318), e.g. a dot product:
  *   forEachReduce acc (f64) in x, y:  body "acc += x * y",  merge "acc += other",  init 0

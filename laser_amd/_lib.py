@@ -134,6 +134,12 @@ def lib():
     L.laser_hip_softmax_rows_f32_dev.argtypes = [vp, i64, vp, i64, i64, i64, vp]
     L.laser_hip_softmax_axis_f32_dev.argtypes = [vp, i64, i64, vp, i64, i64, i64, i64, i64, vp]
     L.laser_hip_softmax_axis_plan.argtypes = [i64, i64, i64, ci, ci, pi]
+    L.laser_hip_sampler_tree_elems.argtypes = [i64, pi]
+    L.laser_hip_sampler_plan.argtypes = [i64, i64, pi]
+    L.laser_hip_sampler_build_f32_dev.argtypes = [vp, i64, vp, i64, i64, i64, vp]
+    L.laser_hip_sampler_sample_f32_dev.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp]
+    L.laser_hip_sampler_sample_remove_f32_dev.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp]
+    L.laser_hip_sampler_update_f32_dev.argtypes = [vp, i64, vp, vp, i64, i64, vp]
     L.laser_hip_cblas_sgemm.argtypes = [ci, ci, ci, i64, i64, i64, C.c_float, vp, i64, vp, i64, C.c_float, vp, i64]
     L.laser_hip_cblas_dgemm.argtypes = [ci, ci, ci, i64, i64, i64, C.c_double, vp, i64, vp, i64, C.c_double, vp, i64]
     _lib = L
@@ -171,7 +177,9 @@ def declared_symbols():
              "laser_hip_foreach_reduce_source", "laser_hip_foreach_reduce_code", "laser_hip_foreach_reduce_kernel",
              "laser_hip_foreach_reduce_dev", "laser_hip_reduce_sum_f32", "laser_hip_reduce_min_f32", "laser_hip_reduce_max_f32",
              "laser_hip_exp_f32_dev", "laser_hip_exp_f32", "laser_hip_softmax_rows_f32_dev",
-             "laser_hip_softmax_axis_f32_dev", "laser_hip_softmax_axis_plan"]
+             "laser_hip_softmax_axis_f32_dev", "laser_hip_softmax_axis_plan",
+             "laser_hip_sampler_tree_elems", "laser_hip_sampler_plan", "laser_hip_sampler_build_f32_dev",
+             "laser_hip_sampler_sample_f32_dev", "laser_hip_sampler_sample_remove_f32_dev", "laser_hip_sampler_update_f32_dev"]
     for s in _CT:
         names += [f"laser_hip_gemm_strided_{s}", f"laser_hip_gemm_strided_{s}_dev",
                   f"laser_hip_gemm_strided_batched_{s}_dev", f"laser_hip_gemm_packed_{s}",

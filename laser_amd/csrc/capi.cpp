@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "sampler_plan.h"
 #include "softmax_axis_plan.h"
 
 using namespace laser_hip;
@@ -1428,6 +1429,71 @@ int laser_hip_softmax_axis_plan(int64_t outer, int64_t n, int64_t inner, int vec
     return fail(LASER_HIP_E_INVALID, "softmax_axis_plan: outer %lld, n %lld, inner %lld outside what softmax_axis takes", (long long)outer,
                 (long long)n, (long long)inner);
   for (int i = 0; i < 4; i++) out4[i] = p[i];
+  return LASER_HIP_OK;
+}
+
+// ---- the F+tree weighted sampler: benchmarks/random_sampling/fenwicktree.nim (sampler.hip, sampler_plan.h) ---------------
+int laser_hip_sampler_tree_elems(int64_t n, int64_t *elems) {
+  if (!elems) return fail(LASER_HIP_E_INVALID, "sampler_tree_elems: null elems");
+  long long e;
+  if (lh_sampler_tree_elems(n, &e) != 0) return fail(LASER_HIP_E_INVALID, "sampler: row length %lld outside 1..2^24", (long long)n);
+  *elems = e;
+  return LASER_HIP_OK;
+}
+int laser_hip_sampler_plan(int64_t rows, int64_t n, int64_t *out4) {
+  if (!out4) return fail(LASER_HIP_E_INVALID, "sampler_plan: null out4");
+  long long p[4];
+  if (lh_sampler_plan(rows, n, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "sampler_plan: rows %lld, n %lld outside what sampler_build takes", (long long)rows, (long long)n);
+  for (int i = 0; i < 4; i++) out4[i] = p[i];
+  return LASER_HIP_OK;
+}
+// the checks every sampler call shares, in the order of the softmax entry points; `count` is m or k (1 where there is none)
+static int sampler_args(const char *what, int64_t tree_row_stride, int64_t rows, int64_t n, int64_t count) {
+  long long elems;
+  if (lh_sampler_tree_elems(n, &elems) != 0) return fail(LASER_HIP_E_INVALID, "%s: row length %lld outside 1..2^24", what, (long long)n);
+  if (rows < 0 || count < 0) return fail(LASER_HIP_E_INVALID, "%s: negative count", what);
+  if (tree_row_stride < elems)
+    return fail(LASER_HIP_E_INVALID, "%s: tree row stride %lld below the %lld elements of a tree of %lld leaves", what,
+                (long long)tree_row_stride, elems, (long long)n);
+  return LASER_HIP_OK;
+}
+int laser_hip_sampler_build_f32_dev(float *tree, int64_t tree_row_stride, const float *w, int64_t w_row_stride, int64_t rows, int64_t n,
+                                    void *stream) {
+  if (int rc = sampler_args("sampler_build", tree_row_stride, rows, n, 1)) return rc;
+  if (w_row_stride < n)
+    return fail(LASER_HIP_E_INVALID, "sampler_build: weight row stride %lld below the row length %lld", (long long)w_row_stride, (long long)n);
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0) return LASER_HIP_OK;
+  if (!tree || !w) return fail(LASER_HIP_E_INVALID, "sampler_build: null buffer");
+  HIP_TRY(launch_sampler_build_f32(tree, tree_row_stride, w, w_row_stride, rows, n, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_sampler_sample_f32_dev(int32_t *idx, const float *tree, int64_t tree_row_stride, const float *u01, int64_t rows, int64_t n,
+                                     int64_t m, void *stream) {
+  if (int rc = sampler_args("sampler_sample", tree_row_stride, rows, n, m)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0 || m == 0) return LASER_HIP_OK;
+  if (!idx || !tree || !u01) return fail(LASER_HIP_E_INVALID, "sampler_sample: null buffer");
+  HIP_TRY(launch_sampler_sample_f32(idx, tree, tree_row_stride, u01, rows, n, m, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_sampler_sample_remove_f32_dev(int32_t *idx, float *tree, int64_t tree_row_stride, const float *u01, int64_t rows, int64_t n,
+                                            int64_t k, void *stream) {
+  if (int rc = sampler_args("sampler_sample_remove", tree_row_stride, rows, n, k)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0 || k == 0) return LASER_HIP_OK;
+  if (!idx || !tree || !u01) return fail(LASER_HIP_E_INVALID, "sampler_sample_remove: null buffer");
+  HIP_TRY(launch_sampler_sample_remove_f32(idx, tree, tree_row_stride, u01, rows, n, k, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_sampler_update_f32_dev(float *tree, int64_t tree_row_stride, const int32_t *elem, const float *weight, int64_t rows,
+                                     int64_t n, void *stream) {
+  if (int rc = sampler_args("sampler_update", tree_row_stride, rows, n, 1)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0) return LASER_HIP_OK;
+  if (!tree || !elem || !weight) return fail(LASER_HIP_E_INVALID, "sampler_update: null buffer");
+  HIP_TRY(launch_sampler_update_f32(tree, tree_row_stride, elem, weight, rows, n, (hipStream_t)stream));
   return LASER_HIP_OK;
 }
 

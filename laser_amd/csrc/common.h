@@ -285,6 +285,15 @@ hipError_t launch_softmax_axis_f32(float *dst, int64_t dst_outer_stride, int64_t
                                    int64_t src_outer_stride, int64_t src_axis_stride, int64_t outer, int64_t n, int64_t inner,
                                    hipStream_t s);
 extern std::atomic<int> g_last_softmax_kernel;
+// the F+tree weighted sampler (sampler.hip; sampler_plan.h picks the build kernel): tree images of 2 P elements per row
+hipError_t launch_sampler_build_f32(float *tree, int64_t tree_row_stride, const float *w, int64_t w_row_stride, int64_t rows, int64_t n,
+                                    hipStream_t s);
+hipError_t launch_sampler_sample_f32(int32_t *idx, const float *tree, int64_t tree_row_stride, const float *u01, int64_t rows, int64_t n,
+                                     int64_t m, hipStream_t s);
+hipError_t launch_sampler_sample_remove_f32(int32_t *idx, float *tree, int64_t tree_row_stride, const float *u01, int64_t rows, int64_t n,
+                                            int64_t k, hipStream_t s);
+hipError_t launch_sampler_update_f32(float *tree, int64_t tree_row_stride, const int32_t *elem, const float *weight, int64_t rows,
+                                     int64_t n, hipStream_t s);
 template <typename T>
 hipError_t launch_pack_pad(T *dst, int64_t Rpad, int64_t Cpad, const T *src, int64_t R,
                            int64_t Ccols, int64_t rs, int64_t cs, hipStream_t s, int relu = 0);

@@ -657,6 +657,44 @@ proc softmaxAxis*(dst: DevicePtr[float32], dstOuterStride, dstAxisStride: int, s
   ## o * outerStride + k * axisStride + i (element strides); every column bit for bit what `softmax` gives it as a row
   check laser_hip_softmax_axis_f32_dev(cast[ptr float32](dst), int64(dstOuterStride), int64(dstAxisStride), cast[ptr float32](src), int64(srcOuterStride), int64(srcAxisStride), int64(outer), int64(n), int64(inner), stream)
 
+# ---- F+tree weighted sampler (include/laser_hip.h "F+tree weighted sampler"): fenwicktree.nim over HipStorage -----------
+# One tree image of 2 P float32 per row (P = the next power of two >= n; the reference's array shifted up by one slot).  The
+# uniform numbers are the caller's: no random number generator lives in the library.
+proc laser_hip_sampler_tree_elems*(n: int64, elems: ptr int64): cint {.lh, importc: "laser_hip_sampler_tree_elems".}
+proc laser_hip_sampler_plan*(rows: int64, n: int64, out4: ptr int64): cint {.lh, importc: "laser_hip_sampler_plan".}
+proc laser_hip_sampler_build_f32_dev*(tree: ptr float32, treeRowStride: int64, w: ptr float32, wRowStride: int64, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_sampler_build_f32_dev".}
+proc laser_hip_sampler_sample_f32_dev*(idx: ptr int32, tree: ptr float32, treeRowStride: int64, u01: ptr float32, rows: int64, n: int64, m: int64, stream: pointer): cint {.lh, importc: "laser_hip_sampler_sample_f32_dev".}
+proc laser_hip_sampler_sample_remove_f32_dev*(idx: ptr int32, tree: ptr float32, treeRowStride: int64, u01: ptr float32, rows: int64, n: int64, k: int64, stream: pointer): cint {.lh, importc: "laser_hip_sampler_sample_remove_f32_dev".}
+proc laser_hip_sampler_update_f32_dev*(tree: ptr float32, treeRowStride: int64, elem: ptr int32, weight: ptr float32, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_sampler_update_f32_dev".}
+
+type
+  Sampler* = object
+    ## fenwicktree.nim:38 for `rows` rows of `n` weights on the device: `tree` holds rows images of `treeElems` float32
+    tree*: HipStorage[float32]
+    rows*, n*, treeElems*: int
+
+proc newSampler*(weights: DevicePtr[float32], wRowStride: int, rows, n: Natural, stream: pointer = nil): Sampler =
+  ## fenwicktree.nim:67-118 for every row of a device matrix (row elements contiguous, wRowStride >= n elements)
+  var elems: int64
+  check laser_hip_sampler_tree_elems(int64(n), elems.addr)
+  result.rows = rows
+  result.n = n
+  result.treeElems = int(elems)
+  allocHipStorage(result.tree, rows * int(elems))
+  check laser_hip_sampler_build_f32_dev(cast[ptr float32](result.tree.raw_buffer), elems, cast[ptr float32](weights), int64(wRowStride), int64(rows), int64(n), stream)
+
+proc sample*(s: Sampler, idx: DevicePtr[int32], u01: DevicePtr[float32], m: Natural = 1, stream: pointer = nil) =
+  ## fenwicktree.nim:147-165: m independent draws per row; idx and u01 are (rows, m) row-major on the device, u01 in [0, 1)
+  check laser_hip_sampler_sample_f32_dev(cast[ptr int32](idx), cast[ptr float32](s.tree.raw_buffer), int64(s.treeElems), cast[ptr float32](u01), int64(s.rows), int64(s.n), int64(m), stream)
+
+proc sampleAndRemove*(s: var Sampler, idx: DevicePtr[int32], u01: DevicePtr[float32], k: Natural = 1, stream: pointer = nil) =
+  ## fenwicktree.nim:186-199, k times per row: a drawn element's weight becomes 0 before the next draw; -1 once a row is empty
+  check laser_hip_sampler_sample_remove_f32_dev(cast[ptr int32](idx), cast[ptr float32](s.tree.raw_buffer), int64(s.treeElems), cast[ptr float32](u01), int64(s.rows), int64(s.n), int64(k), stream)
+
+proc update*(s: var Sampler, elem: DevicePtr[int32], weight: DevicePtr[float32], stream: pointer = nil) =
+  ## fenwicktree.nim:175-184 with one (elem, weight) per row on the device; elem -1 leaves that row alone
+  check laser_hip_sampler_update_f32_dev(cast[ptr float32](s.tree.raw_buffer), int64(s.treeElems), cast[ptr int32](elem), cast[ptr float32](weight), int64(s.rows), int64(s.n), stream)
+
 # ---- forEachReduce (include/laser_hip.h "forEachReduce"): foreach_staged.nim:318 on device buffers ------------------------
 proc laser_hip_foreach_reduce_source(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, accName: cstring, accDtype: cint, merge: cstring, buf: pointer, cap: int64, len: ptr int64): cint {.lh, importc: "laser_hip_foreach_reduce_source".}
 proc laser_hip_foreach_reduce_code(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, accName: cstring, accDtype: cint, merge: cstring, arch: cstring, buf: pointer, cap: int64, len: ptr int64): cint {.lh, importc: "laser_hip_foreach_reduce_code".}
