@@ -185,7 +185,11 @@ const char *laser_hip_f32_config_name(int cfg);
                                          int64_t rowStrideB, int64_t colStrideB, T beta, T *dC,   \
                                          int64_t rowStrideC, int64_t colStrideC, void *stream);   \
   /* `batch` independent problems; operand b starts at ptr + b*batchStrideX (elements; 0 shares). \
-   * Used by the convolution (one GEMM per image, conv2d_im2col.nim:126-166). */                  \
+   * Used by the convolution (one GEMM per image, conv2d_im2col.nim:126-166).                     \
+   * The entries of A and of B may overlap or be shared, and any batch stride may be zero or      \
+   * negative (entry 0 then lies at the far end); the elements of C the call addresses must be    \
+   * pairwise distinct over the whole batch.  batch <= 65535 (more is LASER_HIP_E_INVALID, C      \
+   * untouched); batch == 0 and K == 0 leave C untouched. */                                      \
   int laser_hip_gemm_strided_batched_##SFX##_dev(                                                 \
       int64_t batch, int64_t M, int64_t N, int64_t K, T alpha, const T *dA, int64_t rowStrideA,   \
       int64_t colStrideA, int64_t batchStrideA, const T *dB, int64_t rowStrideB,                  \

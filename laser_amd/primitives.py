@@ -279,6 +279,8 @@ def gemm_strided_batched(batch, M, N, K, alpha, A, rsA, csA, bsA, B, rsB, csB, b
     """Device-only: `batch` independent problems, operand b at ptr + b*batchStride (0 = shared)."""
     L = _lib.lib()
     s = _sfx(C_)
+    if _sfx(A) != s or _sfx(B) != s:
+        raise TypeError("A, B, C must share one element type")
     if not _same_side(A, B, C_):
         raise TypeError("batched GEMM is a device-resident entry point")
     _lib.check(getattr(L, f"laser_hip_gemm_strided_batched_{s}_dev")(

@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Randomised parity stress (GPU box): random shapes / layouts / element offsets / leading-dimension padding /
 alpha, beta / tile configuration, device path.  float32 + float64 in laser-order mode must equal the oracle bit for
-bit; FAST mode must stay within 1e-5 mean relative error.  usage: fuzz_gemm.py [cases] [seed]"""
+bit; FAST mode must stay within 1e-5 mean relative error.  usage: fuzz_gemm.py [cases] [seed] [batched]
+
+`batched` runs laser_hip_gemm_strided_batched_*_dev instead: 2..6 problems per call, each operand independently dense / padded with
+an odd batch stride and base / transposed / shared by the batch (A, B) / in reversed batch order / interleaved (batch stride 1),
+inside a buffer with a whole batch span of guard elements on both sides; the same bars, per entry, and C's guard elements must keep
+their bytes.  Without it the single-problem stream and output are what they always were."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -12,6 +17,96 @@ cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 ncfg = len(laser_amd.f32_configs())
 fails = 0
+
+
+def within_fast_bound(got, want, A, B, C0, alpha, beta, dtype):
+    """the norm-wise bound of the single-problem loop below (see there)"""
+    eps = np.finfo(dtype).eps
+    Aa, Ba = np.abs(np.ascontiguousarray(A)).astype(np.float64), np.abs(np.ascontiguousarray(B)).astype(np.float64)
+    bound = 8 * eps * (abs(float(alpha)) * (Aa @ Ba) + abs(float(beta)) * np.abs(np.ascontiguousarray(C0)).astype(np.float64)) + np.finfo(dtype).tiny
+    return bool(np.all(np.abs(got.astype(np.float64) - want.astype(np.float64)) <= bound))
+
+
+def fuzz_batched():
+    fails = 0
+    kinds = ["dense", "padded", "transposed", "shared", "reversed", "interleaved"]
+    for it in range(cases):
+        dtype = [np.float32, np.float64, np.int32, np.int64][int(rng.choice(4, p=[0.55, 0.15, 0.2, 0.1]))]
+        is_int = np.dtype(dtype).kind == "i"
+        batch = int(rng.integers(2, 7))
+        M, N = int(rng.integers(1, 301)), int(rng.integers(1, 301))
+        K = int(rng.integers(1, 1101))
+        alpha, beta = (dtype(rng.choice([1, 1, 0, -3, 2] if is_int else [1.0, 1.0, 0.0, -0.5, 2.0])) for _ in range(2))
+
+        def draw(n):
+            if is_int:
+                info = np.iinfo(dtype)
+                return rng.integers(info.min, info.max, n, dtype=dtype)
+            return rng.uniform(-0.5, 0.5, n).astype(dtype)
+
+        def make(rows, cols, kind):
+            """(numpy view [batch][rows][cols], host buffer, device buffer, element offset, (bs, rs, cs))"""
+            off = 0
+            if kind == "dense":
+                st = (rows * cols, cols, 1)
+            elif kind == "padded":
+                ld = cols + int(rng.integers(1, 6))
+                st = ((rows * ld + int(rng.integers(0, 8))) | 1, ld, 1)
+                off = int(rng.integers(1, 4))
+            elif kind == "transposed":
+                ld = rows + int(rng.integers(0, 6))
+                st = (cols * ld, 1, ld)
+            elif kind == "shared":
+                st = (0, cols, 1)
+            elif kind == "reversed":
+                st = (-rows * cols, cols, 1)
+            else:
+                st = (1, cols * batch, batch)
+            ext = [(n - 1) * s_ for n, s_ in zip((batch, rows, cols), st)]
+            lo, hi = sum(min(0, e) for e in ext), sum(max(0, e) for e in ext)
+            guard = batch * abs(st[0]) + (rows - 1) * abs(st[1]) + (cols - 1) * abs(st[2]) + 1
+            base = guard - lo + off
+            buf = draw(base + hi + 1 + guard)
+            size = buf.itemsize
+            view = np.lib.stride_tricks.as_strided(buf[base:], (batch, rows, cols), tuple(s_ * size for s_ in st))
+            return view, buf, torch.from_numpy(buf).cuda(), base, st
+
+        kA, kB = kinds[int(rng.integers(0, 6))], kinds[int(rng.integers(0, 6))]
+        kC = [k for k in kinds if k != "shared"][int(rng.integers(0, 5))]
+        A, _, dA, oA, sA = make(M, K, kA)
+        B, _, dB, oB, sB = make(K, N, kB)
+        C0, bufC, dC, oC, sC = make(M, N, kC)
+        cfg = int(rng.integers(0, ncfg)) if (dtype == np.float32 and rng.random() < 0.5) else -1
+        mode = int(rng.random() < 0.3)
+        laser_amd.set_f32_config(cfg); laser_amd.set_float_mode(mode)
+        want = np.stack([oracle.matmul(np.ascontiguousarray(A[p]), np.ascontiguousarray(B[p]), alpha=alpha, beta=beta,
+                                       C_=np.ascontiguousarray(C0[p]).copy(), isa=oracle.fused_isa(dtype)) for p in range(batch)])
+        laser_amd.gemm_strided_batched(batch, M, N, K, alpha, dA[oA:], sA[1], sA[2], sA[0], dB[oB:], sB[1], sB[2], sB[0], beta,
+                                       dC[oC:], sC[1], sC[2], sC[0])
+        after = dC.cpu().numpy()
+        got = np.lib.stride_tricks.as_strided(after[oC:], C0.shape, C0.strides).copy()
+        mask = np.ones(after.size, dtype=bool)
+        idx = oC + sum(np.arange(n).reshape([-1 if ax == i else 1 for i in range(3)]) * s_ for ax, (n, s_) in enumerate(zip(C0.shape, sC)))
+        mask[idx.ravel()] = False
+        untouched = np.array_equal(after[mask].view(np.uint8), bufC[mask].view(np.uint8))
+        if mode == 0 or is_int:
+            ok = np.array_equal(got, want)
+        else:
+            ok = all(within_fast_bound(got[p], want[p], A[p], B[p], C0[p], alpha, beta, dtype) for p in range(batch))
+        if not (ok and untouched):
+            fails += 1
+            print("FAIL", dict(it=it, dtype=dtype.__name__, batch=batch, M=M, N=N, K=K, layouts=(kA, kB, kC), strides=(sA, sB, sC),
+                               offs=(oA, oB, oC), alpha=float(alpha), beta=float(beta), cfg=cfg, mode=mode, untouched=untouched,
+                               nbad=int(np.sum(got != want))), flush=True)
+    laser_amd.set_f32_config(-1); laser_amd.set_float_mode(0)
+    print(f"fuzz batched: {cases} cases, {fails} failures")
+    sys.exit(1 if fails else 0)
+
+
+if len(sys.argv) > 3:
+    if sys.argv[3] != "batched":
+        sys.exit("usage: fuzz_gemm.py [cases] [seed] [batched]")
+    fuzz_batched()
 for it in range(cases):
     dtype = [np.float32, np.float64, np.int32, np.int64][int(rng.choice(4, p=[0.55, 0.15, 0.2, 0.1]))]
     is_int = np.dtype(dtype).kind == "i"
