@@ -585,10 +585,56 @@ inline Tensor<float> softmax_axis(const Tensor<float> &src, int axis, void *stre
   return dst;
 }
 
+// ---- Random numbers (include/laser_hip.h "Random numbers"): Philox4x32-10 streams and the reference's randomTensor ----------
+//   laser::Rng rng(seed, subseq);               names a stream; (seed, subseq, offset) live on the host, nothing on the device
+//   laser::randomTensor<T>({2, 3}, lo, hi, rng) uniform on the closed interval [lo, hi], T = float, double, int32_t, int64_t:
+//                                               element k of the row-major order from word rng.offset + k (pair 2 k, 2 k + 1 for
+//                                               the 64-bit types); the rng advances by the words used
+//   laser::randomTensor<T>({2, 3}, max, rng)    [0, max], the reference's second form
+//   laser::randomBits(n, rng)                   n raw words as a Tensor<int32_t> holding the bits
+// A result is a function of (seed, subseq, offset) and the arguments alone.  Asynchronous on `stream`.
+struct Rng {
+  uint64_t seed = 0, subseq = 0, offset = 0;
+  explicit Rng(uint64_t seed_, uint64_t subseq_ = 0, uint64_t offset_ = 0) : seed(seed_), subseq(subseq_), offset(offset_) {}
+  uint64_t advance(uint64_t words) {  // the offset before; wraps mod 2^64
+    const uint64_t before = offset;
+    offset += words;
+    return before;
+  }
+};
+template <typename T>
+Tensor<T> randomTensor(std::initializer_list<int64_t> shape, T lo, T hi, Rng &rng, void *stream = nullptr) {
+  static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value || std::is_same<T, int32_t>::value ||
+                    std::is_same<T, int64_t>::value,
+                "randomTensor: float, double, int32_t or int64_t");
+  Tensor<T> t = newTensor<T>(shape);
+  const int64_t n = t.size(), sd = (int64_t)rng.seed, sq = (int64_t)rng.subseq, off = (int64_t)rng.offset;
+  if constexpr (std::is_same<T, float>::value) check(laser_hip_random_uniform_f32_dev(t.unsafe_raw_data(), n, lo, hi, sd, sq, off, stream));
+  else if constexpr (std::is_same<T, double>::value) check(laser_hip_random_uniform_f64_dev(t.unsafe_raw_data(), n, lo, hi, sd, sq, off, stream));
+  else if constexpr (std::is_same<T, int32_t>::value) check(laser_hip_random_uniform_i32_dev(t.unsafe_raw_data(), n, lo, hi, sd, sq, off, stream));
+  else check(laser_hip_random_uniform_i64_dev(t.unsafe_raw_data(), n, lo, hi, sd, sq, off, stream));
+  rng.advance((uint64_t)n * (sizeof(T) / 4));
+  return t;
+}
+template <typename T>
+Tensor<T> randomTensor(std::initializer_list<int64_t> shape, T max, Rng &rng, void *stream = nullptr) {
+  return randomTensor<T>(shape, T(0), max, rng, stream);
+}
+inline Tensor<int32_t> randomBits(int64_t n, Rng &rng, void *stream = nullptr) {
+  Tensor<int32_t> t = newTensor<int32_t>({n});
+  check(laser_hip_random_bits_u32_dev(reinterpret_cast<uint32_t *>(t.unsafe_raw_data()), n, (int64_t)rng.seed, (int64_t)rng.subseq,
+                                      (int64_t)rng.offset, stream));
+  rng.advance((uint64_t)n);
+  return t;
+}
+
 // ---- F+tree weighted sampler (include/laser_hip.h "F+tree weighted sampler"): fenwicktree.nim's Sampler, one per row --------
 //   laser::Sampler s(weights);                  weights: a 2-D Tensor<float> whose rows are contiguous (1-D: one row)
-//   s.sample(u);  s.sampleAndRemove(u);         u: a row-major (rows, num) Tensor<float> of numbers in [0, 1) -- the caller's:
-//                                               the library holds no random number generator -> Tensor<int32_t> (rows, num)
+//   s.sample(u);  s.sampleAndRemove(u);         u: a row-major (rows, num) Tensor<float> of numbers in [0, 1), the caller's
+//                                               -> Tensor<int32_t> (rows, num)
+//   s.sample(rng, num);  s.sampleAndRemove(rng, num);   the uniform numbers made in the kernel from the stream of a laser::Rng
+//                                               (below "Random numbers"): u[row, j] from word rng.offset + row * num + j; the
+//                                               rng advances by rows * num
 //   s.update(elem, weight);                     one (elem, weight) per row, Tensor<int32_t> / Tensor<float> of `rows` elements
 // Asynchronous on `stream`.  sampleAndRemove and update mutate `tree`.
 struct Sampler {
@@ -617,6 +663,22 @@ struct Sampler {
     Tensor<int32_t> idx = result_for(u);
     check(laser_hip_sampler_sample_remove_f32_dev(idx.unsafe_raw_data(), tree.unsafe_raw_data(), tree.shape[1], u.unsafe_raw_data(),
                                                   rows, n, u.shape[1], stream));
+    return idx;
+  }
+  Tensor<int32_t> sample(Rng &rng, int64_t num = 1, void *stream = nullptr) const {
+    if (num < 0) throw Error(LASER_HIP_E_INVALID, "Sampler: a count >= 0 is needed");
+    Tensor<int32_t> idx = newTensor<int32_t>({rows, num});
+    check(laser_hip_sampler_sample_rng_f32_dev(idx.unsafe_raw_data(), tree.unsafe_raw_data(), tree.shape[1], (int64_t)rng.seed,
+                                               (int64_t)rng.subseq, (int64_t)rng.offset, rows, n, num, stream));
+    rng.advance((uint64_t)(rows * num));
+    return idx;
+  }
+  Tensor<int32_t> sampleAndRemove(Rng &rng, int64_t num = 1, void *stream = nullptr) {
+    if (num < 0) throw Error(LASER_HIP_E_INVALID, "Sampler: a count >= 0 is needed");
+    Tensor<int32_t> idx = newTensor<int32_t>({rows, num});
+    check(laser_hip_sampler_sample_remove_rng_f32_dev(idx.unsafe_raw_data(), tree.unsafe_raw_data(), tree.shape[1], (int64_t)rng.seed,
+                                                      (int64_t)rng.subseq, (int64_t)rng.offset, rows, n, num, stream));
+    rng.advance((uint64_t)(rows * num));
     return idx;
   }
   void update(const Tensor<int32_t> &elem, const Tensor<float> &weight, void *stream = nullptr) {

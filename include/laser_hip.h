@@ -667,8 +667,8 @@ int laser_hip_softmax_axis_plan(int64_t outer, int64_t n, int64_t inner, int vec
 /* ---- F+tree weighted sampler (f32): benchmarks/random_sampling/fenwicktree.nim, bench_multinomial_samplers.nim --------
  * The reference's `Sampler` over device rows: from a row of weights (the softmax above, or anything non-negative) to drawn
  * indices without leaving the device.  All float32, every operation rounded to float32 on its own, no denormal flushed.
- * The library holds no random number generator: the caller supplies the uniform numbers, so every call is a pure function
- * of its operands.
+ * The caller supplies the uniform numbers, or names a stream of the library's counter-based generator ("Random numbers"
+ * below; the _rng forms): either way every call is a pure function of its operands.
  * Tree image of one row of n weights w, 1 <= n <= LASER_HIP_SAMPLER_MAX_N = 2^24.  P = the next power of two >= n; a row is
  *   2 P elements:
  *     slot 0      +0
@@ -707,6 +707,12 @@ int laser_hip_softmax_axis_plan(int64_t outer, int64_t n, int64_t inner, int vec
  *                                      MUTATES the tree.  One lane owns a row for the whole launch (k * log2 P dependent
  *                                      accesses); a concurrent sample on the same tree from another stream is the caller's race.
  * laser_hip_sampler_update_f32_dev     one (d_elem[row], d_weight[row]) per row; mutates the tree; the same race rule.
+ * laser_hip_sampler_sample_rng_f32_dev, laser_hip_sampler_sample_remove_rng_f32_dev   the two draws with u01[row, j] = the f32
+ *                                      u01 of word offset + row * m + j (k for m) of the stream (seed, subseq) of "Random numbers",
+ *                                      made in the kernel: no buffer of uniform numbers is written or read.  The indices (and,
+ *                                      for remove, the trees afterwards) are exactly those of laser_hip_random_uniform_f32_dev
+ *                                      (lo = 0, hi = 1) into a (rows, m) buffer followed by the call above.  The draws use
+ *                                      rows * m words.
  * All asynchronous on `stream`; pointers are device pointers; indices are int32.  LASER_HIP_E_INVALID, in this order: n
  *   outside 1 .. 2^24, a negative rows / m / k, tree_row_stride < 2 P, w_row_stride < n; then the device is looked for
  *   (LASER_HIP_E_NODEVICE without a gfx950); then rows = 0 (or m = 0, k = 0) does nothing; then a null pointer is
@@ -716,7 +722,7 @@ int laser_hip_softmax_axis_plan(int64_t outer, int64_t n, int64_t inner, int vec
  *   step; workgroups of the first launch; workgroups of the second launch (0: none)}.  The logic is
  *   laser_amd/csrc/sampler_plan.h, which has no HIP dependency.
  * Not built: float64, weights along an axis other than the last, the benchmark's other sampler (cumsum + searchsorted: a
- *   parallel float prefix sum is not monotone, so a zero-probability element could be drawn), an on-device RNG, alias tables. */
+ *   parallel float prefix sum is not monotone, so a zero-probability element could be drawn), alias tables. */
 #define LASER_HIP_SAMPLER_MAX_N (1ll << 24)
 int laser_hip_sampler_tree_elems(int64_t n, int64_t *elems);
 int laser_hip_sampler_plan(int64_t rows, int64_t n, int64_t *out4);
@@ -728,6 +734,62 @@ int laser_hip_sampler_sample_remove_f32_dev(int32_t *d_idx, float *d_tree, int64
                                             int64_t rows, int64_t n, int64_t k, void *stream);
 int laser_hip_sampler_update_f32_dev(float *d_tree, int64_t tree_row_stride, const int32_t *d_elem, const float *d_weight,
                                      int64_t rows, int64_t n, void *stream);
+int laser_hip_sampler_sample_rng_f32_dev(int32_t *d_idx, const float *d_tree, int64_t tree_row_stride, int64_t seed,
+                                         int64_t subseq, int64_t offset, int64_t rows, int64_t n, int64_t m, void *stream);
+int laser_hip_sampler_sample_remove_rng_f32_dev(int32_t *d_idx, float *d_tree, int64_t tree_row_stride, int64_t seed,
+                                                int64_t subseq, int64_t offset, int64_t rows, int64_t n, int64_t k,
+                                                void *stream);
+
+/* ---- Random numbers: Philox4x32-10 and randomTensor's uniform fills -- the `randomTensor(shape, valrange)` and
+ * `randomTensor(shape, max)` that open the reference's benchmarks (bench_exp.nim:17, reduction_bench.nim:40, ...) ----------
+ * A counter-based generator (Salmon, Moraes, Dror, Shaw, SC'11): word w of a stream is a function of (seed, subseq, w) and of
+ * nothing else.  No state lives on the device; a call captured in a graph replays the same numbers; a result never depends on
+ * the grid, the stream, the base alignment or on how a fill was cut into calls.  One definition, laser_amd/csrc/philox_core.h
+ * (no HIP dependency: a host program can include it); tests/philox_model.py is the numpy model.
+ * seed, subseq and offset are 64-bit patterns read as UNSIGNED (mod 2^64).  They travel as int64_t like every other 64-bit
+ *   integer of this ABI: pass the same bits (a uint64_t converts implicitly).
+ * Philox4x32-10: multipliers 0xD2511F53 and 0xCD9E8D57, Weyl key increments 0x9E3779B9 and 0xBB67AE85, ten rounds.  Word w of
+ *   the stream (seed, subseq) is word w & 3 of the block with counter {lo32(b), hi32(b), lo32(subseq), hi32(subseq)}, b = w >> 2,
+ *   and key {lo32(seed), hi32(seed)}.  Counter and key all 0 give 6627e8d5 e169c58d bc57ac4c 9b00dbd8.
+ * Element i of a call uses word (offset + i) mod 2^64; a 64-bit element type uses the pair (offset + 2 i, offset + 2 i + 1),
+ *   low word first: x = w0 | w1 << 32.  A fill of n elements uses n (2 n) words: the next call continues at offset + n (2 n).
+ * Distributions; every float operation rounded on its own in the element type, no fused multiply-add:
+ *   bits_u32         the word itself
+ *   u01 f32          float(x >> 8) * 2^-24, in [0, 1), at most 1 - 2^-24;   u01 f64: double(x >> 11) * 2^-53 of the 64-bit x
+ *   uniform_f32/f64  on the CLOSED interval [lo, hi] like Nim's rand(a..b): t = u01 * (hi - lo), v = lo + t, the result
+ *                    min(v, hi) -- the min is needed: float32 (1, 2) and (0.1, 0.3) reach hi at the largest u01.  lo = 0,
+ *                    hi = 1 returns u01's bits, so there is no separate u01 entry point.  Valid: lo, hi and hi - lo finite,
+ *                    lo <= hi.
+ *   uniform_i32      on [lo, hi]: span = hi - lo + 1 in 1 .. 2^32; lo + int32((uint64(x) * span) >> 32)
+ *   uniform_i64      span = hi - lo + 1 mod 2^64; 0 is the full range: x as a signed value; else lo + mulhi64(x, span), wrapping
+ *   The integer multiply-shift is biased: a value's probability is off by a factor of at most 1 +- span / 2^32 (i32) or
+ *   span / 2^64 (i64).  No rejection loop: an element costs a fixed number of words.  lo <= hi is required.
+ * The fills are asynchronous on `stream`; d_dst is a device pointer to n contiguous elements, any alignment of the element
+ *   type.  LASER_HIP_E_INVALID, in this order: n outside 0 .. LASER_HIP_RANDOM_MAX_N = 2^60, bounds that are not valid; then
+ *   the device is looked for (LASER_HIP_E_NODEVICE without a gfx950); then n = 0 does nothing; then a null pointer is
+ *   LASER_HIP_E_INVALID.
+ * Kernels: one lane computes one Philox block per step and stores the elements that start in it (four 32-bit, two 64-bit: 16
+ *   contiguous bytes) with one 16-byte store; blocks partly outside [0, n) (the head when offset & 3 != 0, the tail) and
+ *   destinations whose runs are off their 16-byte boundaries are stored element by element, same bits.  A 64-bit type at an odd
+ *   offset has elements that straddle two blocks; the lane computes both (twice the arithmetic).
+ * laser_hip_random_plan(n, words_per_elem, offset, dst_misaligned, cus, out4): what a fill would launch, without a device:
+ *   out4 = {variant: 0 = 16-byte stores, 1 = single-element; workgroups of 256 lanes (at most 8 per compute unit; cus <= 0: 256
+ *   compute units); the most blocks one lane walks; the index of the first block, offset >> 2}.  words_per_elem: 1 for the 32-bit
+ *   types, 2 for the 64-bit ones.  The fills plan for 256 compute units on every device.  The logic is
+ *   laser_amd/csrc/random_plan.h, which has no HIP dependency.
+ * Not built: normal and other non-uniform distributions (they need a bit-defined log and sincos first), the other six element
+ *   types, strided destinations, a laser_rand callable in forEach bodies. */
+#define LASER_HIP_RANDOM_MAX_N (1ll << 60)
+int laser_hip_random_plan(int64_t n, int words_per_elem, int64_t offset, int dst_misaligned, int cus, int64_t *out4);
+int laser_hip_random_bits_u32_dev(uint32_t *d_dst, int64_t n, int64_t seed, int64_t subseq, int64_t offset, void *stream);
+int laser_hip_random_uniform_f32_dev(float *d_dst, int64_t n, float lo, float hi, int64_t seed, int64_t subseq,
+                                     int64_t offset, void *stream);
+int laser_hip_random_uniform_f64_dev(double *d_dst, int64_t n, double lo, double hi, int64_t seed, int64_t subseq,
+                                     int64_t offset, void *stream);
+int laser_hip_random_uniform_i32_dev(int32_t *d_dst, int64_t n, int32_t lo, int32_t hi, int64_t seed, int64_t subseq,
+                                     int64_t offset, void *stream);
+int laser_hip_random_uniform_i64_dev(int64_t *d_dst, int64_t n, int64_t lo, int64_t hi, int64_t seed, int64_t subseq,
+                                     int64_t offset, void *stream);
 
 /* ---- forEachReduce: forEach with a private accumulator per lane, merged at the end ---------------------------------
  * The device form of forEachStaged (laser/strided_iteration/foreach_staged.nim:318), e.g. a dot product:

@@ -22,6 +22,8 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "philox_core.h"
+#include "random_plan.h"
 #include "sampler_plan.h"
 #include "softmax_axis_plan.h"
 
@@ -1494,6 +1496,72 @@ int laser_hip_sampler_update_f32_dev(float *tree, int64_t tree_row_stride, const
   if (rows == 0) return LASER_HIP_OK;
   if (!tree || !elem || !weight) return fail(LASER_HIP_E_INVALID, "sampler_update: null buffer");
   HIP_TRY(launch_sampler_update_f32(tree, tree_row_stride, elem, weight, rows, n, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+
+int laser_hip_sampler_sample_rng_f32_dev(int32_t *idx, const float *tree, int64_t tree_row_stride, int64_t seed, int64_t subseq,
+                                         int64_t offset, int64_t rows, int64_t n, int64_t m, void *stream) {
+  if (int rc = sampler_args("sampler_sample_rng", tree_row_stride, rows, n, m)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0 || m == 0) return LASER_HIP_OK;
+  if (!idx || !tree) return fail(LASER_HIP_E_INVALID, "sampler_sample_rng: null buffer");
+  HIP_TRY(launch_sampler_sample_rng_f32(idx, tree, tree_row_stride, (uint64_t)seed, (uint64_t)subseq, (uint64_t)offset, rows, n, m,
+                                        (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_sampler_sample_remove_rng_f32_dev(int32_t *idx, float *tree, int64_t tree_row_stride, int64_t seed, int64_t subseq,
+                                                int64_t offset, int64_t rows, int64_t n, int64_t k, void *stream) {
+  if (int rc = sampler_args("sampler_sample_remove_rng", tree_row_stride, rows, n, k)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0 || k == 0) return LASER_HIP_OK;
+  if (!idx || !tree) return fail(LASER_HIP_E_INVALID, "sampler_sample_remove_rng: null buffer");
+  HIP_TRY(launch_sampler_sample_remove_rng_f32(idx, tree, tree_row_stride, (uint64_t)seed, (uint64_t)subseq, (uint64_t)offset, rows, n, k,
+                                               (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+
+// ---- random numbers: Philox4x32-10 and the uniform fills (random.hip, philox_core.h, random_plan.h) -------------------------
+int laser_hip_random_plan(int64_t n, int words_per_elem, int64_t offset, int dst_misaligned, int cus, int64_t *out4) {
+  if (!out4) return fail(LASER_HIP_E_INVALID, "random_plan: null out4");
+  long long p[4];
+  if (lh_random_plan(n, words_per_elem, (uint64_t)offset, dst_misaligned, cus, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "random_plan: n %lld outside 0..2^60 or %d words per element (1 or 2)", (long long)n, words_per_elem);
+  for (int i = 0; i < 4; i++) out4[i] = p[i];
+  return LASER_HIP_OK;
+}
+// the checks every fill shares, in the order of the sampler entry points: arguments (`range_ok`: the bounds), the device,
+// n = 0, a null pointer; 0 = launch, -1 = done with nothing to do, else the error
+static int random_args(const char *what, const void *dst, int64_t n, bool range_ok) {
+  if (n < 0 || n > LH_RANDOM_MAX_N) return fail(LASER_HIP_E_INVALID, "%s: n %lld outside 0..2^60", what, (long long)n);
+  if (!range_ok) return fail(LASER_HIP_E_INVALID, "%s: lo, hi and hi - lo must be finite and lo <= hi", what);
+  if (int rc = ensure_init()) return rc;
+  if (n == 0) return -1;
+  if (!dst) return fail(LASER_HIP_E_INVALID, "%s: null buffer", what);
+  return LASER_HIP_OK;
+}
+int laser_hip_random_bits_u32_dev(uint32_t *dst, int64_t n, int64_t seed, int64_t subseq, int64_t offset, void *stream) {
+  if (int rc = random_args("random_bits_u32", dst, n, true)) return rc < 0 ? LASER_HIP_OK : rc;
+  HIP_TRY(launch_random_bits_u32(dst, n, (uint64_t)seed, (uint64_t)subseq, (uint64_t)offset, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_random_uniform_f32_dev(float *dst, int64_t n, float lo, float hi, int64_t seed, int64_t subseq, int64_t offset, void *stream) {
+  if (int rc = random_args("random_uniform_f32", dst, n, lh_uniform_range_ok_f32(lo, hi))) return rc < 0 ? LASER_HIP_OK : rc;
+  HIP_TRY(launch_random_uniform_f32(dst, n, lo, hi, (uint64_t)seed, (uint64_t)subseq, (uint64_t)offset, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_random_uniform_f64_dev(double *dst, int64_t n, double lo, double hi, int64_t seed, int64_t subseq, int64_t offset, void *stream) {
+  if (int rc = random_args("random_uniform_f64", dst, n, lh_uniform_range_ok_f64(lo, hi))) return rc < 0 ? LASER_HIP_OK : rc;
+  HIP_TRY(launch_random_uniform_f64(dst, n, lo, hi, (uint64_t)seed, (uint64_t)subseq, (uint64_t)offset, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_random_uniform_i32_dev(int32_t *dst, int64_t n, int32_t lo, int32_t hi, int64_t seed, int64_t subseq, int64_t offset, void *stream) {
+  if (int rc = random_args("random_uniform_i32", dst, n, lo <= hi)) return rc < 0 ? LASER_HIP_OK : rc;
+  HIP_TRY(launch_random_uniform_i32(dst, n, lo, hi, (uint64_t)seed, (uint64_t)subseq, (uint64_t)offset, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_random_uniform_i64_dev(int64_t *dst, int64_t n, int64_t lo, int64_t hi, int64_t seed, int64_t subseq, int64_t offset, void *stream) {
+  if (int rc = random_args("random_uniform_i64", dst, n, lo <= hi)) return rc < 0 ? LASER_HIP_OK : rc;
+  HIP_TRY(launch_random_uniform_i64(dst, n, lo, hi, (uint64_t)seed, (uint64_t)subseq, (uint64_t)offset, (hipStream_t)stream));
   return LASER_HIP_OK;
 }
 

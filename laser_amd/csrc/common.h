@@ -294,6 +294,21 @@ hipError_t launch_sampler_sample_remove_f32(int32_t *idx, float *tree, int64_t t
                                             int64_t k, hipStream_t s);
 hipError_t launch_sampler_update_f32(float *tree, int64_t tree_row_stride, const int32_t *elem, const float *weight, int64_t rows,
                                      int64_t n, hipStream_t s);
+// the same draws with u01[row, j] made in the kernel from word offset + row * m + j of the Philox stream (philox_core.h)
+hipError_t launch_sampler_sample_rng_f32(int32_t *idx, const float *tree, int64_t tree_row_stride, uint64_t seed, uint64_t subseq,
+                                         uint64_t offset, int64_t rows, int64_t n, int64_t m, hipStream_t s);
+hipError_t launch_sampler_sample_remove_rng_f32(int32_t *idx, float *tree, int64_t tree_row_stride, uint64_t seed, uint64_t subseq,
+                                                uint64_t offset, int64_t rows, int64_t n, int64_t k, hipStream_t s);
+// fills with uniform random numbers (random.hip; philox_core.h is the generator, random_plan.h the launch plan)
+hipError_t launch_random_bits_u32(uint32_t *dst, int64_t n, uint64_t seed, uint64_t subseq, uint64_t offset, hipStream_t s);
+hipError_t launch_random_uniform_f32(float *dst, int64_t n, float lo, float hi, uint64_t seed, uint64_t subseq, uint64_t offset,
+                                     hipStream_t s);
+hipError_t launch_random_uniform_f64(double *dst, int64_t n, double lo, double hi, uint64_t seed, uint64_t subseq, uint64_t offset,
+                                     hipStream_t s);
+hipError_t launch_random_uniform_i32(int32_t *dst, int64_t n, int32_t lo, int32_t hi, uint64_t seed, uint64_t subseq, uint64_t offset,
+                                     hipStream_t s);
+hipError_t launch_random_uniform_i64(int64_t *dst, int64_t n, int64_t lo, int64_t hi, uint64_t seed, uint64_t subseq, uint64_t offset,
+                                     hipStream_t s);
 template <typename T>
 hipError_t launch_pack_pad(T *dst, int64_t Rpad, int64_t Cpad, const T *src, int64_t R,
                            int64_t Ccols, int64_t rs, int64_t cs, hipStream_t s, int relu = 0);

@@ -18,12 +18,16 @@
 //                                segment nodes (at most 2^14 - 1 nodes) and writes slot 0.  No workgroup waits on another.
 // Draw: one lane per (row, draw), one 8-byte load of the (left, right) pair per level.  Draw-and-remove and update: one lane
 // per row does the draws and the walks back up; no other lane touches that row's tree inside the launch.
+// The draw kernels take the source of their uniform numbers as a parameter: the caller's buffer, or (the _rng forms) a Philox
+// stream, u01[row, j] being the float32 u01 (philox_core.h) of word offset + row * m + j, one Philox block per draw, no buffer
+// of uniform numbers written or read.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "../../include/laser_hip.h"
 #include "common.h"
+#include "philox_core.h"
 #include "sampler_plan.h"
 
 static_assert(LH_SAMPLER_MAX_N == LASER_HIP_SAMPLER_MAX_N, "plan and header agree");
@@ -203,21 +207,33 @@ __device__ __forceinline__ void update(float *tr, const int P, const int idx, co
   }
 }
 
-template <bool A8>
-__global__ void __launch_bounds__(256) sampler_sample_kernel(int *idx, const float *tree, const long long ts, const float *u01,
+// where the uniform number of draw e = row * m + j comes from: the caller's buffer, or word offset + e of a Philox stream
+struct U01Buffer {
+  const float *u01;
+  __device__ __forceinline__ float operator()(const long long e) const { return u01[e]; }
+};
+struct U01Philox {
+  unsigned long long seed, subseq, offset;
+  __device__ __forceinline__ float operator()(const long long e) const {
+    return lh_u01_f32(lh_philox_word(seed, subseq, offset + (unsigned long long)e));
+  }
+};
+
+template <bool A8, class U01>
+__global__ void __launch_bounds__(256) sampler_sample_kernel(int *idx, const float *tree, const long long ts, const U01 u01,
                                                              const long long rows, const long long m, const int P) {
   const long long total = rows * m;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256)
-    idx[e] = draw<A8>(tree + (e / m) * ts, P, u01[e]);
+    idx[e] = draw<A8>(tree + (e / m) * ts, P, u01(e));
 }
 
-template <bool A8>
-__global__ void __launch_bounds__(256) sampler_sample_remove_kernel(int *idx, float *tree, const long long ts, const float *u01,
+template <bool A8, class U01>
+__global__ void __launch_bounds__(256) sampler_sample_remove_kernel(int *idx, float *tree, const long long ts, const U01 u01,
                                                                     const long long rows, const long long k, const int P) {
   for (long long row = (long long)blockIdx.x * 256 + threadIdx.x; row < rows; row += (long long)gridDim.x * 256) {
     float *tr = tree + row * ts;
     for (long long s = 0; s < k; s++) {
-      const int i = draw<A8>(tr, P, u01[row * k + s]);
+      const int i = draw<A8>(tr, P, u01(row * k + s));
       idx[row * k + s] = i;
       if (i >= 0) update<A8>(tr, P, i, 0.0f);
     }
@@ -272,28 +288,48 @@ hipError_t launch_sampler_build_f32(float *tree, int64_t ts, const float *w, int
   return hipGetLastError();
 }
 
-hipError_t launch_sampler_sample_f32(int32_t *idx, const float *tree, int64_t ts, const float *u01, int64_t rows, int64_t n, int64_t m,
-                                     hipStream_t s) {
+template <class U01>
+static hipError_t sample_from(int32_t *idx, const float *tree, int64_t ts, const U01 &u01, int64_t rows, int64_t n, int64_t m, hipStream_t s) {
   if (rows == 0 || m == 0) return hipSuccess;
   const int P = (int)lh_sampler_leaves(n, 0);
   const dim3 grid(lane_grid((long long)rows * m));
   if (pair_aligned(tree, ts, rows))
-    hipLaunchKernelGGL(sampler_sample_kernel<true>, grid, dim3(256), 0, s, idx, tree, (long long)ts, u01, (long long)rows, (long long)m, P);
+    hipLaunchKernelGGL((sampler_sample_kernel<true, U01>), grid, dim3(256), 0, s, idx, tree, (long long)ts, u01, (long long)rows, (long long)m, P);
   else
-    hipLaunchKernelGGL(sampler_sample_kernel<false>, grid, dim3(256), 0, s, idx, tree, (long long)ts, u01, (long long)rows, (long long)m, P);
+    hipLaunchKernelGGL((sampler_sample_kernel<false, U01>), grid, dim3(256), 0, s, idx, tree, (long long)ts, u01, (long long)rows, (long long)m, P);
   return hipGetLastError();
 }
 
-hipError_t launch_sampler_sample_remove_f32(int32_t *idx, float *tree, int64_t ts, const float *u01, int64_t rows, int64_t n, int64_t k,
-                                            hipStream_t s) {
+template <class U01>
+static hipError_t sample_remove_from(int32_t *idx, float *tree, int64_t ts, const U01 &u01, int64_t rows, int64_t n, int64_t k, hipStream_t s) {
   if (rows == 0 || k == 0) return hipSuccess;
   const int P = (int)lh_sampler_leaves(n, 0);
   const dim3 grid(lane_grid(rows));
   if (pair_aligned(tree, ts, rows))
-    hipLaunchKernelGGL(sampler_sample_remove_kernel<true>, grid, dim3(256), 0, s, idx, tree, (long long)ts, u01, (long long)rows, (long long)k, P);
+    hipLaunchKernelGGL((sampler_sample_remove_kernel<true, U01>), grid, dim3(256), 0, s, idx, tree, (long long)ts, u01, (long long)rows, (long long)k, P);
   else
-    hipLaunchKernelGGL(sampler_sample_remove_kernel<false>, grid, dim3(256), 0, s, idx, tree, (long long)ts, u01, (long long)rows, (long long)k, P);
+    hipLaunchKernelGGL((sampler_sample_remove_kernel<false, U01>), grid, dim3(256), 0, s, idx, tree, (long long)ts, u01, (long long)rows, (long long)k, P);
   return hipGetLastError();
+}
+
+hipError_t launch_sampler_sample_f32(int32_t *idx, const float *tree, int64_t ts, const float *u01, int64_t rows, int64_t n, int64_t m,
+                                     hipStream_t s) {
+  return sample_from(idx, tree, ts, U01Buffer{u01}, rows, n, m, s);
+}
+
+hipError_t launch_sampler_sample_remove_f32(int32_t *idx, float *tree, int64_t ts, const float *u01, int64_t rows, int64_t n, int64_t k,
+                                            hipStream_t s) {
+  return sample_remove_from(idx, tree, ts, U01Buffer{u01}, rows, n, k, s);
+}
+
+hipError_t launch_sampler_sample_rng_f32(int32_t *idx, const float *tree, int64_t ts, uint64_t seed, uint64_t subseq, uint64_t offset,
+                                         int64_t rows, int64_t n, int64_t m, hipStream_t s) {
+  return sample_from(idx, tree, ts, U01Philox{seed, subseq, offset}, rows, n, m, s);
+}
+
+hipError_t launch_sampler_sample_remove_rng_f32(int32_t *idx, float *tree, int64_t ts, uint64_t seed, uint64_t subseq, uint64_t offset,
+                                                int64_t rows, int64_t n, int64_t k, hipStream_t s) {
+  return sample_remove_from(idx, tree, ts, U01Philox{seed, subseq, offset}, rows, n, k, s);
 }
 
 hipError_t launch_sampler_update_f32(float *tree, int64_t ts, const int32_t *elem, const float *weight, int64_t rows, int64_t n,

@@ -2,16 +2,19 @@
 include/laser_hip.h "F+tree weighted sampler") over the rows of a float32 matrix.
 
     s = laser_amd.newSampler(weights)          one tree per row of the 2-D `weights` (1-D: one row)
-    s.sample(u=None, num=1)                    num independent draws per row, with replacement  -> int32 Tensor (rows, num)
-    s.sampleAndRemove(u=None, num=1)           num draws per row without replacement (mutates the trees; -1 once a row is empty)
+    s.sample(u=None, num=1, rng=None)          num independent draws per row, with replacement  -> int32 Tensor (rows, num)
+    s.sampleAndRemove(u=None, num=1, rng=None) num draws per row without replacement (mutates the trees; -1 once a row is empty)
     s.update(elem, weight)                     one (elem, weight) per row; elem = -1 leaves that row alone
-    laser_amd.multinomial(probs, num_samples=1, replacement=False, u=None)     build and draw in one call
+    laser_amd.multinomial(probs, num_samples=1, replacement=False, u=None, rng=None)     build and draw in one call
 
-`weights` is a laser_amd.Tensor or a torch CUDA tensor whose rows are contiguous; the weights need not sum to 1.  The library
-holds no random number generator: `u` is a float32 array of shape (rows, num) with values in [0, 1) -- a device tensor, or a
-host numpy array, which is checked and uploaded -- and every result is a function of the weights and `u` alone, bit for bit.
-u=None draws the numbers with torch.rand on the device: this module is the one place randomness enters.  Calls are
-asynchronous on the current torch stream.  Not built: float64, weights along another axis, alias tables.
+`weights` is a laser_amd.Tensor or a torch CUDA tensor whose rows are contiguous; the weights need not sum to 1.  The uniform
+numbers come from one of three places.  `u` is a float32 array of shape (rows, num) with values in [0, 1) -- a device tensor,
+or a host numpy array, which is checked and uploaded -- and every result is a function of the weights and `u` alone, bit for
+bit.  `rng` is a laser_amd.Rng (laser_amd/random.py), the library's counter-based generator: the kernel makes
+u[row, j] = the float32 u01 of word rng.offset + row * num + j itself, the result is a function of the weights and
+(seed, subseq, offset), and the rng advances by rows * num.  Giving both raises ValueError.  With neither, the numbers are
+drawn with torch.rand on the device: the one place where a result depends on state outside the call.  Calls are asynchronous
+on the current torch stream.  Not built: float64, weights along another axis, alias tables.
 """
 import ctypes as C
 
@@ -44,10 +47,15 @@ def tree_elems(n):
     return out.value
 
 
-def _uniforms(u, rows, num):
-    """the (rows, num) float32 uniform numbers as a device operand; None: torch.rand on the device"""
+def _count(num):
     if isinstance(num, bool) or not isinstance(num, (int, np.integer)) or num < 0:
         raise ValueError(f"num = {num!r} (a count >= 0 is needed)")
+    return int(num)
+
+
+def _uniforms(u, rows, num):
+    """the (rows, num) float32 uniform numbers as a device operand; None: torch.rand on the device"""
+    _count(num)
     if u is None:
         import torch
         return torch.rand((rows, int(num)), dtype=torch.float32, device="cuda")
@@ -80,20 +88,33 @@ class Sampler:
     def __init__(self, tree, rows, n):
         self.tree, self.rows, self.n = tree, int(rows), int(n)
 
-    def _draw(self, entry, u, num):
-        u = _uniforms(u, self.rows, num)
-        out = newTensor(np.int32, self.rows, int(num))
-        _lib.check(entry(C.c_void_p(out.unsafe_raw_data()), C.c_void_p(self.tree.unsafe_raw_data()), self.tree.shape[1],
-                         C.c_void_p(_View("u", u).ptr), self.rows, self.n, int(num), _stream()))
+    def _draw(self, which, u, num, rng):
+        """laser_hip_sampler_<which>_f32_dev on `u`, or its _rng form on the stream of `rng`, which then advances"""
+        num = _count(num)
+        if rng is None:
+            u = _uniforms(u, self.rows, num)
+            entry, source = getattr(_lib.lib(), f"laser_hip_sampler_{which}_f32_dev"), (C.c_void_p(_View("u", u).ptr),)
+        else:
+            from .random import Rng
+            if u is not None:
+                raise ValueError("give the uniform numbers `u` or the generator `rng`, not both")
+            if not isinstance(rng, Rng):
+                raise TypeError(f"rng: {type(rng).__name__} (a laser_amd.Rng is needed)")
+            entry, source = getattr(_lib.lib(), f"laser_hip_sampler_{which}_rng_f32_dev"), (rng.seed, rng.subseq, rng.offset)
+        out = newTensor(np.int32, self.rows, num)
+        _lib.check(entry(C.c_void_p(out.unsafe_raw_data()), C.c_void_p(self.tree.unsafe_raw_data()), self.tree.shape[1], *source,
+                         self.rows, self.n, num, _stream()))
+        if rng is not None:
+            rng.advance(self.rows * num)
         return out
 
-    def sample(self, u=None, num=1):
+    def sample(self, u=None, num=1, rng=None):
         """num independent draws per row with replacement; the trees are only read"""
-        return self._draw(_lib.lib().laser_hip_sampler_sample_f32_dev, u, num)
+        return self._draw("sample", u, num, rng)
 
-    def sampleAndRemove(self, u=None, num=1):
+    def sampleAndRemove(self, u=None, num=1, rng=None):
         """num draws per row, each drawn element's weight set to 0 before the next draw; -1 once nothing is left"""
-        return self._draw(_lib.lib().laser_hip_sampler_sample_remove_f32_dev, u, num)
+        return self._draw("sample_remove", u, num, rng)
 
     def update(self, elem, weight):
         """per row: the weight of element elem[row] becomes weight[row] (elem -1: nothing).  Host sequences are checked
@@ -133,8 +154,10 @@ def newSampler(weights):
     return Sampler(tree, rows, n)
 
 
-def multinomial(probs, num_samples=1, replacement=False, u=None):
+def multinomial(probs, num_samples=1, replacement=False, u=None, rng=None):
     """num_samples indices per row of `probs`, drawn in proportion to the weights: int32 Tensor (rows, num_samples).  Without
     replacement an element is drawn at most once, and a row with fewer positive weights than num_samples ends in -1."""
+    if u is not None and rng is not None:
+        raise ValueError("give the uniform numbers `u` or the generator `rng`, not both")
     s = newSampler(probs)
-    return s.sample(u, num_samples) if replacement else s.sampleAndRemove(u, num_samples)
+    return s.sample(u, num_samples, rng) if replacement else s.sampleAndRemove(u, num_samples, rng)

@@ -659,7 +659,7 @@ proc softmaxAxis*(dst: DevicePtr[float32], dstOuterStride, dstAxisStride: int, s
 
 # ---- F+tree weighted sampler (include/laser_hip.h "F+tree weighted sampler"): fenwicktree.nim over HipStorage -----------
 # One tree image of 2 P float32 per row (P = the next power of two >= n; the reference's array shifted up by one slot).  The
-# uniform numbers are the caller's: no random number generator lives in the library.
+# uniform numbers are the caller's, or come from a HipRng stream ("Random numbers" below): the overloads taking `rng`.
 proc laser_hip_sampler_tree_elems*(n: int64, elems: ptr int64): cint {.lh, importc: "laser_hip_sampler_tree_elems".}
 proc laser_hip_sampler_plan*(rows: int64, n: int64, out4: ptr int64): cint {.lh, importc: "laser_hip_sampler_plan".}
 proc laser_hip_sampler_build_f32_dev*(tree: ptr float32, treeRowStride: int64, w: ptr float32, wRowStride: int64, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_sampler_build_f32_dev".}
@@ -694,6 +694,65 @@ proc sampleAndRemove*(s: var Sampler, idx: DevicePtr[int32], u01: DevicePtr[floa
 proc update*(s: var Sampler, elem: DevicePtr[int32], weight: DevicePtr[float32], stream: pointer = nil) =
   ## fenwicktree.nim:175-184 with one (elem, weight) per row on the device; elem -1 leaves that row alone
   check laser_hip_sampler_update_f32_dev(cast[ptr float32](s.tree.raw_buffer), int64(s.treeElems), cast[ptr int32](elem), cast[ptr float32](weight), int64(s.rows), int64(s.n), stream)
+
+# ---- Random numbers (include/laser_hip.h "Random numbers"): Philox4x32-10 streams, randomTensor over HipStorage -----------
+# Word w of a stream is a function of (seed, subseq, w) alone; a HipRng holds (seed, subseq, offset) on the host and nothing
+# lives on the device.  The three travel as int64 (the C-ABI has no unsigned parameters): the same 64 bits, read as unsigned.
+proc laser_hip_random_plan*(n: int64, wordsPerElem: cint, offset: int64, dstMisaligned: cint, cus: cint, out4: ptr int64): cint {.lh, importc: "laser_hip_random_plan".}
+proc laser_hip_random_bits_u32_dev*(dst: ptr uint32, n: int64, seed: int64, subseq: int64, offset: int64, stream: pointer): cint {.lh, importc: "laser_hip_random_bits_u32_dev".}
+proc laser_hip_random_uniform_f32_dev*(dst: ptr float32, n: int64, lo: float32, hi: float32, seed: int64, subseq: int64, offset: int64, stream: pointer): cint {.lh, importc: "laser_hip_random_uniform_f32_dev".}
+proc laser_hip_random_uniform_f64_dev*(dst: ptr float64, n: int64, lo: float64, hi: float64, seed: int64, subseq: int64, offset: int64, stream: pointer): cint {.lh, importc: "laser_hip_random_uniform_f64_dev".}
+proc laser_hip_random_uniform_i32_dev*(dst: ptr int32, n: int64, lo: int32, hi: int32, seed: int64, subseq: int64, offset: int64, stream: pointer): cint {.lh, importc: "laser_hip_random_uniform_i32_dev".}
+proc laser_hip_random_uniform_i64_dev*(dst: ptr int64, n: int64, lo: int64, hi: int64, seed: int64, subseq: int64, offset: int64, stream: pointer): cint {.lh, importc: "laser_hip_random_uniform_i64_dev".}
+proc laser_hip_sampler_sample_rng_f32_dev*(idx: ptr int32, tree: ptr float32, treeRowStride: int64, seed: int64, subseq: int64, offset: int64, rows: int64, n: int64, m: int64, stream: pointer): cint {.lh, importc: "laser_hip_sampler_sample_rng_f32_dev".}
+proc laser_hip_sampler_sample_remove_rng_f32_dev*(idx: ptr int32, tree: ptr float32, treeRowStride: int64, seed: int64, subseq: int64, offset: int64, rows: int64, n: int64, k: int64, stream: pointer): cint {.lh, importc: "laser_hip_sampler_sample_remove_rng_f32_dev".}
+
+type
+  HipRng* = object
+    ## the stream (seed, subseq) and the next unused word; every draw advances `offset` by the words it used (mod 2^64)
+    seed*, subseq*, offset*: uint64
+
+func initHipRng*(seed: uint64, subseq: uint64 = 0, offset: uint64 = 0): HipRng {.inline.} =
+  HipRng(seed: seed, subseq: subseq, offset: offset)
+
+proc randomTensor*[T](shape: openarray[int], valrange: Slice[T], rng: var HipRng): HipStorage[T] =
+  ## randomTensor(shape, valrange) of the reference's benchmarks (bench_exp.nim:17) on the device: prod(shape) elements in
+  ## row-major order, uniform on the closed interval valrange.a .. valrange.b; T is float32, float64, int32 or int64 (int)
+  var size = 1
+  for s in shape: size *= s
+  allocHipStorage(result, size)
+  let (sd, sq, off) = (cast[int64](rng.seed), cast[int64](rng.subseq), cast[int64](rng.offset))
+  when T is float32:
+    check laser_hip_random_uniform_f32_dev(cast[ptr float32](result.raw_buffer), int64(size), valrange.a, valrange.b, sd, sq, off, nil)
+  elif T is float64:
+    check laser_hip_random_uniform_f64_dev(cast[ptr float64](result.raw_buffer), int64(size), valrange.a, valrange.b, sd, sq, off, nil)
+  elif T is int32:
+    check laser_hip_random_uniform_i32_dev(cast[ptr int32](result.raw_buffer), int64(size), valrange.a, valrange.b, sd, sq, off, nil)
+  elif T is int64 or T is int:
+    check laser_hip_random_uniform_i64_dev(cast[ptr int64](result.raw_buffer), int64(size), int64(valrange.a), int64(valrange.b), sd, sq, off, nil)
+  else:
+    {.error: "randomTensor: float32, float64, int32 or int64".}
+  rng.offset += uint64(size) * uint64(sizeof(T) div 4)
+
+proc randomTensor*[T](shape: openarray[int], max: T, rng: var HipRng): HipStorage[T] =
+  ## randomTensor(shape, max) (reduction_bench.nim:40): uniform on 0 .. max
+  randomTensor(shape, T(0)..max, rng)
+
+proc randomBits*(n: Natural, rng: var HipRng): HipStorage[uint32] =
+  ## the next n words of the stream
+  allocHipStorage(result, n)
+  check laser_hip_random_bits_u32_dev(cast[ptr uint32](result.raw_buffer), int64(n), cast[int64](rng.seed), cast[int64](rng.subseq), cast[int64](rng.offset), nil)
+  rng.offset += uint64(n)
+
+proc sample*(s: Sampler, idx: DevicePtr[int32], rng: var HipRng, m: Natural = 1, stream: pointer = nil) =
+  ## `sample` with u01[row, j] made in the kernel from word rng.offset + row * m + j; the rng advances by rows * m
+  check laser_hip_sampler_sample_rng_f32_dev(cast[ptr int32](idx), cast[ptr float32](s.tree.raw_buffer), int64(s.treeElems), cast[int64](rng.seed), cast[int64](rng.subseq), cast[int64](rng.offset), int64(s.rows), int64(s.n), int64(m), stream)
+  rng.offset += uint64(s.rows * m)
+
+proc sampleAndRemove*(s: var Sampler, idx: DevicePtr[int32], rng: var HipRng, k: Natural = 1, stream: pointer = nil) =
+  ## `sampleAndRemove` with the uniform numbers of the stream; the rng advances by rows * k
+  check laser_hip_sampler_sample_remove_rng_f32_dev(cast[ptr int32](idx), cast[ptr float32](s.tree.raw_buffer), int64(s.treeElems), cast[int64](rng.seed), cast[int64](rng.subseq), cast[int64](rng.offset), int64(s.rows), int64(s.n), int64(k), stream)
+  rng.offset += uint64(s.rows * k)
 
 # ---- forEachReduce (include/laser_hip.h "forEachReduce"): foreach_staged.nim:318 on device buffers ------------------------
 proc laser_hip_foreach_reduce_source(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, accName: cstring, accDtype: cint, merge: cstring, buf: pointer, cap: int64, len: ptr int64): cint {.lh, importc: "laser_hip_foreach_reduce_source".}
