@@ -697,6 +697,107 @@ struct Sampler {
   }
 };
 
+// ---- Row cumsum, searchsorted and the inverse-CDF sampler (include/laser_hip.h, the section of that name):
+// cumsum, searchsorted and sample of bench_multinomial_samplers.nim over device Tensors -------------------------------------
+//   laser::cumsum(t)                            inclusive prefix sum along the last axis of a 1-D or 2-D Tensor<T> whose rows
+//                                               are contiguous, T = float, double, int32_t, int64_t -> Tensor<T> of t's shape
+//   laser::searchsorted(a, v, leftSide)         v: (rows) or a row-major (rows, m) Tensor<T> -> Tensor<int32_t> of v's shape
+//   laser::cdfSample(cdf, u)                    u: a row-major (rows, num) Tensor<float> in [0, 1) -> Tensor<int32_t> (rows, num)
+//   laser::cdfSampleAndRemove(weights, u)       without replacement, on a private copy of the weights
+//   laser::cdfSample(cdf, rng, num);  laser::cdfSampleAndRemove(weights, rng, num)   the uniform numbers from a laser::Rng
+// Asynchronous on `stream`.
+namespace detail {
+template <typename T>
+void scan_rows(const Tensor<T> &t, const char *what, int64_t &rows, int64_t &n, int64_t &rs) {
+  const int r = t.rank();
+  if (r != 1 && r != 2) throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": a matrix (or a vector for one row) is needed").c_str());
+  rows = r == 2 ? t.shape[0] : 1;
+  n = t.shape[r - 1];
+  if (n < 1) throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": empty rows").c_str());
+  if (n != 1 && t.strides[r - 1] != 1) throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": the elements of a row must be contiguous").c_str());
+  rs = rows > 1 ? t.strides[0] : n;
+}
+inline Tensor<int32_t> scan_result_for(const Tensor<float> &u, int64_t rows) {
+  if (u.rank() != 2 || u.shape[0] != rows || !u.is_C_contiguous())
+    throw Error(LASER_HIP_E_INVALID, "cdfSample: a row-major (rows, num) tensor of uniform numbers is needed");
+  return newTensor<int32_t>({rows, u.shape[1]});
+}
+}  // namespace detail
+template <typename T>
+Tensor<T> cumsum(const Tensor<T> &t, void *stream = nullptr) {
+  int64_t rows, n, rs;
+  detail::scan_rows(t, "cumsum", rows, n, rs);
+  Tensor<T> out = t.rank() == 1 ? newTensor<T>({n}) : newTensor<T>({rows, n});
+  LASER_DISPATCH(T, check(laser_hip_cumsum_f32_dev(out.unsafe_raw_data(), n, t.unsafe_raw_data(), rs, rows, n, stream)),
+                 check(laser_hip_cumsum_f64_dev(out.unsafe_raw_data(), n, t.unsafe_raw_data(), rs, rows, n, stream)),
+                 check(laser_hip_cumsum_i32_dev(out.unsafe_raw_data(), n, t.unsafe_raw_data(), rs, rows, n, stream)),
+                 check(laser_hip_cumsum_i64_dev(out.unsafe_raw_data(), n, t.unsafe_raw_data(), rs, rows, n, stream)))
+  return out;
+}
+template <typename T>
+Tensor<int32_t> searchsorted(const Tensor<T> &a, const Tensor<T> &v, bool leftSide = true, void *stream = nullptr) {
+  int64_t rows, n, rs;
+  detail::scan_rows(a, "searchsorted", rows, n, rs);
+  if ((v.rank() != 1 && v.rank() != 2) || v.shape[0] != rows || !v.is_C_contiguous())
+    throw Error(LASER_HIP_E_INVALID, "searchsorted: values of shape (rows) or a row-major (rows, m) are needed");
+  const int64_t m = v.rank() == 1 ? 1 : v.shape[1];
+  const int right = leftSide ? 0 : 1;
+  Tensor<int32_t> idx = v.rank() == 1 ? newTensor<int32_t>({rows}) : newTensor<int32_t>({rows, m});
+  LASER_DISPATCH(T, check(laser_hip_searchsorted_f32_dev(idx.unsafe_raw_data(), a.unsafe_raw_data(), rs, v.unsafe_raw_data(), rows, n, m, right, stream)),
+                 check(laser_hip_searchsorted_f64_dev(idx.unsafe_raw_data(), a.unsafe_raw_data(), rs, v.unsafe_raw_data(), rows, n, m, right, stream)),
+                 check(laser_hip_searchsorted_i32_dev(idx.unsafe_raw_data(), a.unsafe_raw_data(), rs, v.unsafe_raw_data(), rows, n, m, right, stream)),
+                 check(laser_hip_searchsorted_i64_dev(idx.unsafe_raw_data(), a.unsafe_raw_data(), rs, v.unsafe_raw_data(), rows, n, m, right, stream)))
+  return idx;
+}
+inline Tensor<int32_t> cdfSample(const Tensor<float> &cdf, const Tensor<float> &u, void *stream = nullptr) {
+  int64_t rows, n, rs;
+  detail::scan_rows(cdf, "cdfSample", rows, n, rs);
+  Tensor<int32_t> idx = detail::scan_result_for(u, rows);
+  check(laser_hip_cdf_sample_f32_dev(idx.unsafe_raw_data(), cdf.unsafe_raw_data(), rs, u.unsafe_raw_data(), rows, n, u.shape[1], stream));
+  return idx;
+}
+inline Tensor<int32_t> cdfSample(const Tensor<float> &cdf, Rng &rng, int64_t num = 1, void *stream = nullptr) {
+  int64_t rows, n, rs;
+  detail::scan_rows(cdf, "cdfSample", rows, n, rs);
+  if (num < 0) throw Error(LASER_HIP_E_INVALID, "cdfSample: a count >= 0 is needed");
+  Tensor<int32_t> idx = newTensor<int32_t>({rows, num});
+  check(laser_hip_cdf_sample_rng_f32_dev(idx.unsafe_raw_data(), cdf.unsafe_raw_data(), rs, (int64_t)rng.seed, (int64_t)rng.subseq,
+                                         (int64_t)rng.offset, rows, n, num, stream));
+  rng.advance((uint64_t)(rows * num));
+  return idx;
+}
+namespace detail {
+// a row-major private copy of the weights and a CDF workspace of the same shape
+inline void scan_private(const Tensor<float> &weights, int64_t rows, int64_t n, int64_t rs, Tensor<float> &w, Tensor<float> &cdf, void *stream) {
+  w = newTensor<float>({rows, n});
+  cdf = newTensor<float>({rows, n});
+  const int64_t shape[2] = {rows, n}, dstr[2] = {n, 1}, sstr[2] = {rs, 1};
+  check(laser_hip_copy_strided_b32_dev(w.unsafe_raw_data(), dstr, weights.unsafe_raw_data(), sstr, shape, 2, stream));
+}
+}  // namespace detail
+inline Tensor<int32_t> cdfSampleAndRemove(const Tensor<float> &weights, const Tensor<float> &u, void *stream = nullptr) {
+  int64_t rows, n, rs;
+  detail::scan_rows(weights, "cdfSampleAndRemove", rows, n, rs);
+  Tensor<int32_t> idx = detail::scan_result_for(u, rows);
+  Tensor<float> w, cdf;
+  detail::scan_private(weights, rows, n, rs, w, cdf, stream);
+  check(laser_hip_cdf_sample_remove_f32_dev(idx.unsafe_raw_data(), w.unsafe_raw_data(), n, cdf.unsafe_raw_data(), n, u.unsafe_raw_data(),
+                                            rows, n, u.shape[1], stream));
+  return idx;
+}
+inline Tensor<int32_t> cdfSampleAndRemove(const Tensor<float> &weights, Rng &rng, int64_t num = 1, void *stream = nullptr) {
+  int64_t rows, n, rs;
+  detail::scan_rows(weights, "cdfSampleAndRemove", rows, n, rs);
+  if (num < 0) throw Error(LASER_HIP_E_INVALID, "cdfSampleAndRemove: a count >= 0 is needed");
+  Tensor<int32_t> idx = newTensor<int32_t>({rows, num});
+  Tensor<float> w, cdf;
+  detail::scan_private(weights, rows, n, rs, w, cdf, stream);
+  check(laser_hip_cdf_sample_remove_rng_f32_dev(idx.unsafe_raw_data(), w.unsafe_raw_data(), n, cdf.unsafe_raw_data(), n, (int64_t)rng.seed,
+                                                (int64_t)rng.subseq, (int64_t)rng.offset, rows, n, num, stream));
+  rng.advance((uint64_t)(rows * num));
+  return idx;
+}
+
 #undef LASER_DISPATCH
 #undef LASER_GEMM_DISPATCH
 }  // namespace laser

@@ -721,8 +721,8 @@ int laser_hip_softmax_axis_plan(int64_t outer, int64_t n, int64_t inner, int vec
  *   (P <= 512), 1 = segments of 1024 leaves plus a second launch for the levels above them; leaves a workgroup owns in one
  *   step; workgroups of the first launch; workgroups of the second launch (0: none)}.  The logic is
  *   laser_amd/csrc/sampler_plan.h, which has no HIP dependency.
- * Not built: float64, weights along an axis other than the last, the benchmark's other sampler (cumsum + searchsorted: a
- *   parallel float prefix sum is not monotone, so a zero-probability element could be drawn), alias tables. */
+ * Not built: float64, weights along an axis other than the last, alias tables.  The benchmark's other sampler (cumsum +
+ *   searchsorted) is the next section, "Row cumsum, searchsorted and the inverse-CDF sampler". */
 #define LASER_HIP_SAMPLER_MAX_N (1ll << 24)
 int laser_hip_sampler_tree_elems(int64_t n, int64_t *elems);
 int laser_hip_sampler_plan(int64_t rows, int64_t n, int64_t *out4);
@@ -739,6 +739,99 @@ int laser_hip_sampler_sample_rng_f32_dev(int32_t *d_idx, const float *d_tree, in
 int laser_hip_sampler_sample_remove_rng_f32_dev(int32_t *d_idx, float *d_tree, int64_t tree_row_stride, int64_t seed,
                                                 int64_t subseq, int64_t offset, int64_t rows, int64_t n, int64_t k,
                                                 void *stream);
+
+/* ---- Row cumsum, searchsorted and the inverse-CDF sampler: bench_multinomial_samplers.nim:49-61, 143-214 ----------------
+ * The other half of the reference's sampling benchmark: `cumsum` over the rows of a matrix, `searchsorted` (lowerBound /
+ * upperBound) and `sample`, the classic inverse-CDF multinomial draw -- the baseline the F+tree above is measured against.
+ * One definition, laser_amd/csrc/scan_core.h (no HIP dependency: a host program can include it); tests/scan_model.py is the
+ * numpy model.
+ * Scan order.  An inclusive prefix sum along the contiguous last axis, one row at a time.  R = LH_SCAN_RUN (scan_core.h; 32,
+ *   the fastest of 8, 16 and 32 at 128 rows of 50 000: profiles/scan).
+ *   Row x[0..n) is cut into runs, run r = [r R, min(n, (r + 1) R)).
+ *     loc(i) = x[i] at the first element of a run, else fl(loc(i - 1) + x[i])       (a serial sum inside the run)
+ *     run 0:       out[i] = loc(i)
+ *     run r >= 1:  out[i] = fl(carry_r + loc(i)), one addition, carry_r = out[r R - 1]   (the value stored for the last
+ *                  element of the previous run)
+ *   Every addition is rounded on its own in the element type; no denormal is flushed, nothing is reassociated.  The result is
+ *   a function of the row's values, n and R alone, never of rows, the strides, the base alignment, the grid or the stream.
+ *   The integer types wrap mod 2^32 / 2^64, where any order gives the serial result.  A usual work-efficient parallel float
+ *   scan is NOT monotone (a later prefix can round below an earlier one); this order is, by construction.  For non-negative
+ *   finite input without overflow:
+ *   (a) Monotone: out is non-decreasing.  Inside a run loc is a serial sum of non-negatives, so loc is non-decreasing, and
+ *       c -> fl(c + .) is monotone; across a boundary out[r R] = fl(out[r R - 1] + x[r R]) >= out[r R - 1].
+ *   (b) Zero steps: x[i] == 0 (either sign) gives out[i] == out[i - 1].  Inside a run loc(i) = fl(loc(i - 1) + 0) = loc(i - 1),
+ *       so out does not move; at a run's first element out[i] = fl(carry + 0) = carry = out[i - 1].
+ *   The price is a chain of ceil(n / R) - 1 dependent additions per row, carry_{r+1} = fl(carry_r + total_r); the R-element
+ *   local sums and the final carry + loc are parallel across lanes, rows across workgroups.
+ * Search.  The result of this exact descent on any input, sorted or not, NaN included: lo = 0, count = n; while count > 0:
+ *   step = count / 2, pos = lo + step; go right (lo = pos + 1, count -= step + 1) iff a[pos] < v (left side, right = 0) or
+ *   a[pos] <= v (right side, right != 0); otherwise count = step.  The result is lo, in [0, n].  A comparison with NaN is
+ *   false, so NaN goes left: what the reference's lowerBound / upperBound do.  At most 25 steps for n <= 2^24.
+ * CDF draw (f32) for one row and one u01 in [0, 1):
+ *     total = cdf[n - 1]; not finite or not > 0: the result is -1 (the rule of the F+tree root).
+ *     u = u01 * total, one multiply -- the documented deviation from the reference, which divides the whole CDF by its last
+ *       element instead; it is the F+tree draw's.
+ *     idx = the right-side search of u;  idx == n: idx = the left-side search of total.
+ *   The last rule is needed when u01 * total rounds up to total; in float32 that happens only for denormal totals (the smallest
+ *   denormal times 1 - 2^-24 rounds to itself).  With a CDF made by the scan above from non-negative finite weights w, every
+ *   result has 0 <= idx < n and w[idx] > 0: by (a) the searches are those of a sorted row.  The right-side search gives the
+ *   first idx with cdf[idx] > u >= 0 and, for idx > 0, cdf[idx - 1] <= u < cdf[idx]: the CDF moves at idx, so by (b) w[idx] is
+ *   not 0 (idx = 0: w[0] = cdf[0] > 0).  idx == n means u >= total, so u == total, and the left-side search gives the first
+ *   idx with cdf[idx] >= total, which exists (n - 1 qualifies) and again has cdf[idx - 1] < cdf[idx] or idx = 0.
+ * Draw and remove, min(k, n) rounds: round s scans the weights into the CDF workspace, draws with u01[row, s], stores the index
+ *   and sets w[row, idx] = +0 unless the index is -1 (the reference zeroes, recomputes the CDF and rescales it; here the
+ *   multiply by the fresh total stands for the rescaling).  Columns s >= n are -1.  Two launches per round.  OVERWRITES the
+ *   caller's weights; d_cdf is workspace of rows rows, cdf_row_stride >= n apart.
+ * laser_hip_cumsum_{f32,f64,i32,i64}_dev   rows rows of n elements, row strides >= n elements, the elements of a row contiguous,
+ *                                      any base alignment of the element type.  d_dst == d_src with equal strides (in place)
+ *                                      works; any other overlap is the caller's error.  Nothing outside a row's n elements is
+ *                                      written.
+ * laser_hip_searchsorted_{f32,f64,i32,i64}_dev   d_v and d_idx are (rows, m) row-major; row i of d_v is searched in row i of d_a.
+ * laser_hip_cdf_sample_f32_dev         m draws per row with replacement; d_u01 and d_idx are (rows, m) row-major.
+ * laser_hip_cdf_sample_remove_f32_dev  k draws per row without replacement; d_u01 and d_idx are (rows, k) row-major.
+ * laser_hip_cdf_sample_rng_f32_dev, laser_hip_cdf_sample_remove_rng_f32_dev   the two draws with u01[row, j] = the f32 u01 of
+ *                                      word offset + row * m + j (k for m) of the stream (seed, subseq) of "Random numbers", made
+ *                                      in the kernel: exactly the results of laser_hip_random_uniform_f32_dev (lo = 0, hi = 1)
+ *                                      into a (rows, m) buffer followed by the buffer form.
+ * All asynchronous on `stream`; pointers are device pointers; indices are int32.  LASER_HIP_E_INVALID, in this order: n
+ *   outside 1 .. LASER_HIP_SCAN_MAX_N = 2^24, a negative rows / m / k, a row stride < n; then the device is looked for
+ *   (LASER_HIP_E_NODEVICE without a gfx950); then rows = 0 (or m = 0, k = 0) does nothing; then a null pointer is
+ *   LASER_HIP_E_INVALID.
+ * Kernels (laser_amd/csrc/scan.hip).  cumsum: a workgroup of 256 lanes owns a row (n > 64 R) or four rows of a wave each, and
+ *   walks the row in tiles of 256 R (64 R) elements.  A lane owns one run of the tile: R elements in registers (16-byte loads
+ *   and stores where both bases and both row strides allow, element by element otherwise and for the row's last, partial
+ *   run: same bits), the run's total into LDS.  ONE lane per row walks the tile's chain, the fewest that keep the order;
+ *   meanwhile the other waves form the local sums of the next tile, whose loads were issued before the chain.  Then every
+ *   lane adds its run's carry and stores.  No workgroup waits on another and nothing spins.  searchsorted and the draws: one
+ *   lane per (row, value); a round of draw-and-remove: one lane per row.
+ * laser_hip_cumsum_plan(rows, n, elem_size, cus, out4): what a cumsum would launch, without a device: out4 = {variant: 0 = a
+ *   wave per row, 1 = a workgroup per row; rows a workgroup owns at a time (4 or 1: a tile is 256 / that * R elements);
+ *   workgroups (at most 8 per compute unit; cus <= 0: 256 compute units, which is what the entry points plan for); tiles per
+ *   row}.  elem_size 4 or 8.  The logic is laser_amd/csrc/scan_plan.h, which has no HIP dependency.
+ * Not built: exclusive scans, scans along another axis, the other six element types, float64 draws, a scan across workgroups
+ *   for one very long row (one workgroup walks it: the chain of n / R additions bounds it). */
+#define LASER_HIP_SCAN_MAX_N (1ll << 24)
+#define LASER_HIP_DECL_SCAN(SFX, T)                                                                                     \
+  int laser_hip_cumsum_##SFX##_dev(T *d_dst, int64_t dst_row_stride, const T *d_src, int64_t src_row_stride,           \
+                                   int64_t rows, int64_t n, void *stream);                                              \
+  int laser_hip_searchsorted_##SFX##_dev(int32_t *d_idx, const T *d_a, int64_t a_row_stride, const T *d_v,             \
+                                         int64_t rows, int64_t n, int64_t m, int right, void *stream);
+LASER_HIP_DECL_SCAN(f32, float)
+LASER_HIP_DECL_SCAN(f64, double)
+LASER_HIP_DECL_SCAN(i32, int32_t)
+LASER_HIP_DECL_SCAN(i64, int64_t)
+#undef LASER_HIP_DECL_SCAN
+int laser_hip_cumsum_plan(int64_t rows, int64_t n, int elem_size, int cus, int64_t *out4);
+int laser_hip_cdf_sample_f32_dev(int32_t *d_idx, const float *d_cdf, int64_t cdf_row_stride, const float *d_u01,
+                                 int64_t rows, int64_t n, int64_t m, void *stream);
+int laser_hip_cdf_sample_remove_f32_dev(int32_t *d_idx, float *d_w, int64_t w_row_stride, float *d_cdf,
+                                        int64_t cdf_row_stride, const float *d_u01, int64_t rows, int64_t n, int64_t k,
+                                        void *stream);
+int laser_hip_cdf_sample_rng_f32_dev(int32_t *d_idx, const float *d_cdf, int64_t cdf_row_stride, int64_t seed,
+                                     int64_t subseq, int64_t offset, int64_t rows, int64_t n, int64_t m, void *stream);
+int laser_hip_cdf_sample_remove_rng_f32_dev(int32_t *d_idx, float *d_w, int64_t w_row_stride, float *d_cdf,
+                                            int64_t cdf_row_stride, int64_t seed, int64_t subseq, int64_t offset,
+                                            int64_t rows, int64_t n, int64_t k, void *stream);
 
 /* ---- Random numbers: Philox4x32-10 and randomTensor's uniform fills -- the `randomTensor(shape, valrange)` and
  * `randomTensor(shape, max)` that open the reference's benchmarks (bench_exp.nim:17, reduction_bench.nim:40, ...) ----------

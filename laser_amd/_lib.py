@@ -143,6 +143,14 @@ def lib():
     u64 = C.c_uint64   # seed, subseq, offset: 64-bit patterns read as unsigned (int64_t in the header, the same register)
     L.laser_hip_sampler_sample_rng_f32_dev.argtypes = [vp, vp, i64, u64, u64, u64, i64, i64, i64, vp]
     L.laser_hip_sampler_sample_remove_rng_f32_dev.argtypes = [vp, vp, i64, u64, u64, u64, i64, i64, i64, vp]
+    L.laser_hip_cumsum_plan.argtypes = [i64, i64, ci, ci, pi]
+    for sfx in _CT:
+        getattr(L, f"laser_hip_cumsum_{sfx}_dev").argtypes = [vp, i64, vp, i64, i64, i64, vp]
+        getattr(L, f"laser_hip_searchsorted_{sfx}_dev").argtypes = [vp, vp, i64, vp, i64, i64, i64, ci, vp]
+    L.laser_hip_cdf_sample_f32_dev.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp]
+    L.laser_hip_cdf_sample_remove_f32_dev.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, i64, vp]
+    L.laser_hip_cdf_sample_rng_f32_dev.argtypes = [vp, vp, i64, u64, u64, u64, i64, i64, i64, vp]
+    L.laser_hip_cdf_sample_remove_rng_f32_dev.argtypes = [vp, vp, i64, vp, i64, u64, u64, u64, i64, i64, i64, vp]
     L.laser_hip_random_plan.argtypes = [i64, ci, u64, ci, ci, pi]
     L.laser_hip_random_bits_u32_dev.argtypes = [vp, i64, u64, u64, u64, vp]
     for sfx, ct in _CT.items():
@@ -188,14 +196,17 @@ def declared_symbols():
              "laser_hip_sampler_tree_elems", "laser_hip_sampler_plan", "laser_hip_sampler_build_f32_dev",
              "laser_hip_sampler_sample_f32_dev", "laser_hip_sampler_sample_remove_f32_dev", "laser_hip_sampler_update_f32_dev",
              "laser_hip_sampler_sample_rng_f32_dev", "laser_hip_sampler_sample_remove_rng_f32_dev",
-             "laser_hip_random_plan", "laser_hip_random_bits_u32_dev"]
+             "laser_hip_random_plan", "laser_hip_random_bits_u32_dev",
+             "laser_hip_cumsum_plan", "laser_hip_cdf_sample_f32_dev", "laser_hip_cdf_sample_remove_f32_dev",
+             "laser_hip_cdf_sample_rng_f32_dev", "laser_hip_cdf_sample_remove_rng_f32_dev"]
     for s in _CT:
         names += [f"laser_hip_gemm_strided_{s}", f"laser_hip_gemm_strided_{s}_dev",
                   f"laser_hip_gemm_strided_batched_{s}_dev", f"laser_hip_gemm_packed_{s}",
                   f"laser_hip_gemm_strided_{s}_sharded", f"laser_hip_gemm_strided_{s}_sharded_dev",
                   f"laser_hip_map_strided_unary_{s}_dev", f"laser_hip_map_strided_binary_{s}_dev",
                   f"laser_hip_gemm_packed_{s}_dev", f"laser_hip_reduce_sum_{s}_dev", f"laser_hip_reduce_min_{s}_dev",
-                  f"laser_hip_reduce_max_{s}_dev", f"laser_hip_random_uniform_{s}_dev"]
+                  f"laser_hip_reduce_max_{s}_dev", f"laser_hip_random_uniform_{s}_dev",
+                  f"laser_hip_cumsum_{s}_dev", f"laser_hip_searchsorted_{s}_dev"]
         for ab in "AB":
             names += [f"laser_hip_gemm_prepack{ab}_mem_required_{s}", f"laser_hip_gemm_prepack{ab}_{s}",
                       f"laser_hip_gemm_prepack{ab}_{s}_dev"]

@@ -25,6 +25,7 @@
 #include "philox_core.h"
 #include "random_plan.h"
 #include "sampler_plan.h"
+#include "scan_plan.h"
 #include "softmax_axis_plan.h"
 
 using namespace laser_hip;
@@ -1517,6 +1518,89 @@ int laser_hip_sampler_sample_remove_rng_f32_dev(int32_t *idx, float *tree, int64
   if (!idx || !tree) return fail(LASER_HIP_E_INVALID, "sampler_sample_remove_rng: null buffer");
   HIP_TRY(launch_sampler_sample_remove_rng_f32(idx, tree, tree_row_stride, (uint64_t)seed, (uint64_t)subseq, (uint64_t)offset, rows, n, k,
                                                (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+
+// ---- row cumsum, searchsorted and the inverse-CDF sampler: bench_multinomial_samplers.nim (scan.hip, scan_core.h, scan_plan.h)
+int laser_hip_cumsum_plan(int64_t rows, int64_t n, int elem_size, int cus, int64_t *out4) {
+  if (!out4) return fail(LASER_HIP_E_INVALID, "cumsum_plan: null out4");
+  long long p[4];
+  if (lh_scan_plan(rows, n, elem_size, cus, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "cumsum_plan: rows %lld, n %lld, element size %d outside what cumsum takes", (long long)rows,
+                (long long)n, elem_size);
+  for (int i = 0; i < 4; i++) out4[i] = p[i];
+  return LASER_HIP_OK;
+}
+// the checks every call of this section shares, in the order of the sampler entry points; `count` is m or k (1 where there is
+// none), s0 / s1 the row strides of the call (n where it has fewer than two)
+static int scan_args(const char *what, int64_t rows, int64_t n, int64_t count, int64_t s0, int64_t s1) {
+  if (n < 1 || n > LH_SCAN_MAX_N) return fail(LASER_HIP_E_INVALID, "%s: row length %lld outside 1..2^24", what, (long long)n);
+  if (rows < 0 || count < 0) return fail(LASER_HIP_E_INVALID, "%s: negative count", what);
+  if (s0 < n || s1 < n)
+    return fail(LASER_HIP_E_INVALID, "%s: row stride %lld below the row length %lld", what, (long long)(s0 < n ? s0 : s1), (long long)n);
+  return LASER_HIP_OK;
+}
+#define LASER_HIP_DEF_SCAN(SFX, T)                                                                                                  \
+  int laser_hip_cumsum_##SFX##_dev(T *dst, int64_t dst_row_stride, const T *src, int64_t src_row_stride, int64_t rows, int64_t n,   \
+                                   void *stream) {                                                                                  \
+    if (int rc = scan_args("cumsum_" #SFX, rows, n, 1, dst_row_stride, src_row_stride)) return rc;                                  \
+    if (int rc = ensure_init()) return rc;                                                                                          \
+    if (rows == 0) return LASER_HIP_OK;                                                                                             \
+    if (!dst || !src) return fail(LASER_HIP_E_INVALID, "cumsum_" #SFX ": null buffer");                                             \
+    HIP_TRY(launch_cumsum_##SFX(dst, dst_row_stride, src, src_row_stride, rows, n, (hipStream_t)stream));                           \
+    return LASER_HIP_OK;                                                                                                            \
+  }                                                                                                                                 \
+  int laser_hip_searchsorted_##SFX##_dev(int32_t *idx, const T *a, int64_t a_row_stride, const T *v, int64_t rows, int64_t n,       \
+                                         int64_t m, int right, void *stream) {                                                      \
+    if (int rc = scan_args("searchsorted_" #SFX, rows, n, m, a_row_stride, n)) return rc;                                           \
+    if (int rc = ensure_init()) return rc;                                                                                          \
+    if (rows == 0 || m == 0) return LASER_HIP_OK;                                                                                   \
+    if (!idx || !a || !v) return fail(LASER_HIP_E_INVALID, "searchsorted_" #SFX ": null buffer");                                   \
+    HIP_TRY(launch_searchsorted_##SFX(idx, a, a_row_stride, v, rows, n, m, right, (hipStream_t)stream));                            \
+    return LASER_HIP_OK;                                                                                                            \
+  }
+LASER_HIP_DEF_SCAN(f32, float)
+LASER_HIP_DEF_SCAN(f64, double)
+LASER_HIP_DEF_SCAN(i32, int32_t)
+LASER_HIP_DEF_SCAN(i64, int64_t)
+#undef LASER_HIP_DEF_SCAN
+int laser_hip_cdf_sample_f32_dev(int32_t *idx, const float *cdf, int64_t cdf_row_stride, const float *u01, int64_t rows, int64_t n,
+                                 int64_t m, void *stream) {
+  if (int rc = scan_args("cdf_sample", rows, n, m, cdf_row_stride, n)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0 || m == 0) return LASER_HIP_OK;
+  if (!idx || !cdf || !u01) return fail(LASER_HIP_E_INVALID, "cdf_sample: null buffer");
+  HIP_TRY(launch_cdf_sample_f32(idx, cdf, cdf_row_stride, u01, rows, n, m, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_cdf_sample_remove_f32_dev(int32_t *idx, float *w, int64_t w_row_stride, float *cdf, int64_t cdf_row_stride,
+                                        const float *u01, int64_t rows, int64_t n, int64_t k, void *stream) {
+  if (int rc = scan_args("cdf_sample_remove", rows, n, k, w_row_stride, cdf_row_stride)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0 || k == 0) return LASER_HIP_OK;
+  if (!idx || !w || !cdf || !u01) return fail(LASER_HIP_E_INVALID, "cdf_sample_remove: null buffer");
+  HIP_TRY(launch_cdf_sample_remove_f32(idx, w, w_row_stride, cdf, cdf_row_stride, u01, rows, n, k, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_cdf_sample_rng_f32_dev(int32_t *idx, const float *cdf, int64_t cdf_row_stride, int64_t seed, int64_t subseq,
+                                     int64_t offset, int64_t rows, int64_t n, int64_t m, void *stream) {
+  if (int rc = scan_args("cdf_sample_rng", rows, n, m, cdf_row_stride, n)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0 || m == 0) return LASER_HIP_OK;
+  if (!idx || !cdf) return fail(LASER_HIP_E_INVALID, "cdf_sample_rng: null buffer");
+  HIP_TRY(launch_cdf_sample_rng_f32(idx, cdf, cdf_row_stride, (uint64_t)seed, (uint64_t)subseq, (uint64_t)offset, rows, n, m,
+                                    (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_cdf_sample_remove_rng_f32_dev(int32_t *idx, float *w, int64_t w_row_stride, float *cdf, int64_t cdf_row_stride,
+                                            int64_t seed, int64_t subseq, int64_t offset, int64_t rows, int64_t n, int64_t k,
+                                            void *stream) {
+  if (int rc = scan_args("cdf_sample_remove_rng", rows, n, k, w_row_stride, cdf_row_stride)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0 || k == 0) return LASER_HIP_OK;
+  if (!idx || !w || !cdf) return fail(LASER_HIP_E_INVALID, "cdf_sample_remove_rng: null buffer");
+  HIP_TRY(launch_cdf_sample_remove_rng_f32(idx, w, w_row_stride, cdf, cdf_row_stride, (uint64_t)seed, (uint64_t)subseq,
+                                           (uint64_t)offset, rows, n, k, (hipStream_t)stream));
   return LASER_HIP_OK;
 }
 

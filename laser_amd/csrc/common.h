@@ -299,6 +299,27 @@ hipError_t launch_sampler_sample_rng_f32(int32_t *idx, const float *tree, int64_
                                          uint64_t offset, int64_t rows, int64_t n, int64_t m, hipStream_t s);
 hipError_t launch_sampler_sample_remove_rng_f32(int32_t *idx, float *tree, int64_t tree_row_stride, uint64_t seed, uint64_t subseq,
                                                 uint64_t offset, int64_t rows, int64_t n, int64_t k, hipStream_t s);
+// the row prefix sum, the sorted search and the inverse-CDF sampler (scan.hip; scan_core.h is the order, scan_plan.h the launch plan)
+hipError_t launch_cumsum_f32(float *dst, int64_t ds, const float *src, int64_t ss, int64_t rows, int64_t n, hipStream_t s);
+hipError_t launch_cumsum_f64(double *dst, int64_t ds, const double *src, int64_t ss, int64_t rows, int64_t n, hipStream_t s);
+hipError_t launch_cumsum_i32(int32_t *dst, int64_t ds, const int32_t *src, int64_t ss, int64_t rows, int64_t n, hipStream_t s);
+hipError_t launch_cumsum_i64(int64_t *dst, int64_t ds, const int64_t *src, int64_t ss, int64_t rows, int64_t n, hipStream_t s);
+hipError_t launch_searchsorted_f32(int32_t *idx, const float *a, int64_t as, const float *v, int64_t rows, int64_t n, int64_t m, int right,
+                                   hipStream_t s);
+hipError_t launch_searchsorted_f64(int32_t *idx, const double *a, int64_t as, const double *v, int64_t rows, int64_t n, int64_t m, int right,
+                                   hipStream_t s);
+hipError_t launch_searchsorted_i32(int32_t *idx, const int32_t *a, int64_t as, const int32_t *v, int64_t rows, int64_t n, int64_t m,
+                                   int right, hipStream_t s);
+hipError_t launch_searchsorted_i64(int32_t *idx, const int64_t *a, int64_t as, const int64_t *v, int64_t rows, int64_t n, int64_t m,
+                                   int right, hipStream_t s);
+hipError_t launch_cdf_sample_f32(int32_t *idx, const float *cdf, int64_t cs, const float *u01, int64_t rows, int64_t n, int64_t m,
+                                 hipStream_t s);
+hipError_t launch_cdf_sample_rng_f32(int32_t *idx, const float *cdf, int64_t cs, uint64_t seed, uint64_t subseq, uint64_t offset,
+                                     int64_t rows, int64_t n, int64_t m, hipStream_t s);
+hipError_t launch_cdf_sample_remove_f32(int32_t *idx, float *w, int64_t ws, float *cdf, int64_t cs, const float *u01, int64_t rows,
+                                        int64_t n, int64_t k, hipStream_t s);
+hipError_t launch_cdf_sample_remove_rng_f32(int32_t *idx, float *w, int64_t ws, float *cdf, int64_t cs, uint64_t seed, uint64_t subseq,
+                                            uint64_t offset, int64_t rows, int64_t n, int64_t k, hipStream_t s);
 // fills with uniform random numbers (random.hip; philox_core.h is the generator, random_plan.h the launch plan)
 hipError_t launch_random_bits_u32(uint32_t *dst, int64_t n, uint64_t seed, uint64_t subseq, uint64_t offset, hipStream_t s);
 hipError_t launch_random_uniform_f32(float *dst, int64_t n, float lo, float hi, uint64_t seed, uint64_t subseq, uint64_t offset,

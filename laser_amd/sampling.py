@@ -5,7 +5,7 @@ include/laser_hip.h "F+tree weighted sampler") over the rows of a float32 matrix
     s.sample(u=None, num=1, rng=None)          num independent draws per row, with replacement  -> int32 Tensor (rows, num)
     s.sampleAndRemove(u=None, num=1, rng=None) num draws per row without replacement (mutates the trees; -1 once a row is empty)
     s.update(elem, weight)                     one (elem, weight) per row; elem = -1 leaves that row alone
-    laser_amd.multinomial(probs, num_samples=1, replacement=False, u=None, rng=None)     build and draw in one call
+    laser_amd.multinomial(probs, num_samples=1, replacement=False, u=None, rng=None, method="ftree")   build and draw in one call
 
 `weights` is a laser_amd.Tensor or a torch CUDA tensor whose rows are contiguous; the weights need not sum to 1.  The uniform
 numbers come from one of three places.  `u` is a float32 array of shape (rows, num) with values in [0, 1) -- a device tensor,
@@ -154,10 +154,20 @@ def newSampler(weights):
     return Sampler(tree, rows, n)
 
 
-def multinomial(probs, num_samples=1, replacement=False, u=None, rng=None):
+def multinomial(probs, num_samples=1, replacement=False, u=None, rng=None, method="ftree"):
     """num_samples indices per row of `probs`, drawn in proportion to the weights: int32 Tensor (rows, num_samples).  Without
-    replacement an element is drawn at most once, and a row with fewer positive weights than num_samples ends in -1."""
+    replacement an element is drawn at most once, and a row with fewer positive weights than num_samples ends in -1.
+    method: "ftree" builds the F+tree and draws from it; "cdf" is the reference's other sampler (laser_amd/scan.py): one
+    cumsum and one search per draw with replacement, a fresh cumsum per draw without."""
     if u is not None and rng is not None:
         raise ValueError("give the uniform numbers `u` or the generator `rng`, not both")
+    if method == "cdf":
+        from . import scan
+        if replacement:
+            _f32_rows("probs", probs)
+            return scan.cdfSample(scan.cumsum(probs), u, num_samples, rng)
+        return scan.cdfSampleAndRemove(probs, u, num_samples, rng)
+    if method != "ftree":
+        raise ValueError(f"method = {method!r} (\"ftree\" or \"cdf\")")
     s = newSampler(probs)
     return s.sample(u, num_samples, rng) if replacement else s.sampleAndRemove(u, num_samples, rng)

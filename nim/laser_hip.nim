@@ -754,6 +754,73 @@ proc sampleAndRemove*(s: var Sampler, idx: DevicePtr[int32], rng: var HipRng, k:
   check laser_hip_sampler_sample_remove_rng_f32_dev(cast[ptr int32](idx), cast[ptr float32](s.tree.raw_buffer), int64(s.treeElems), cast[int64](rng.seed), cast[int64](rng.subseq), cast[int64](rng.offset), int64(s.rows), int64(s.n), int64(k), stream)
   rng.offset += uint64(s.rows * k)
 
+# ---- Row cumsum, searchsorted and the inverse-CDF sampler (include/laser_hip.h, the section of that name):
+# cumsum, searchsorted and sample of bench_multinomial_samplers.nim:49-61, 143-214 over HipStorage --------------------------
+proc laser_hip_cumsum_f32_dev*(dst: ptr float32, dstRowStride: int64, src: ptr float32, srcRowStride: int64, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_cumsum_f32_dev".}
+proc laser_hip_cumsum_f64_dev*(dst: ptr float64, dstRowStride: int64, src: ptr float64, srcRowStride: int64, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_cumsum_f64_dev".}
+proc laser_hip_cumsum_i32_dev*(dst: ptr int32, dstRowStride: int64, src: ptr int32, srcRowStride: int64, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_cumsum_i32_dev".}
+proc laser_hip_cumsum_i64_dev*(dst: ptr int64, dstRowStride: int64, src: ptr int64, srcRowStride: int64, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_cumsum_i64_dev".}
+proc laser_hip_searchsorted_f32_dev*(idx: ptr int32, a: ptr float32, aRowStride: int64, v: ptr float32, rows: int64, n: int64, m: int64, right: cint, stream: pointer): cint {.lh, importc: "laser_hip_searchsorted_f32_dev".}
+proc laser_hip_searchsorted_f64_dev*(idx: ptr int32, a: ptr float64, aRowStride: int64, v: ptr float64, rows: int64, n: int64, m: int64, right: cint, stream: pointer): cint {.lh, importc: "laser_hip_searchsorted_f64_dev".}
+proc laser_hip_searchsorted_i32_dev*(idx: ptr int32, a: ptr int32, aRowStride: int64, v: ptr int32, rows: int64, n: int64, m: int64, right: cint, stream: pointer): cint {.lh, importc: "laser_hip_searchsorted_i32_dev".}
+proc laser_hip_searchsorted_i64_dev*(idx: ptr int32, a: ptr int64, aRowStride: int64, v: ptr int64, rows: int64, n: int64, m: int64, right: cint, stream: pointer): cint {.lh, importc: "laser_hip_searchsorted_i64_dev".}
+proc laser_hip_cumsum_plan*(rows: int64, n: int64, elemSize: cint, cus: cint, out4: ptr int64): cint {.lh, importc: "laser_hip_cumsum_plan".}
+proc laser_hip_cdf_sample_f32_dev*(idx: ptr int32, cdf: ptr float32, cdfRowStride: int64, u01: ptr float32, rows: int64, n: int64, m: int64, stream: pointer): cint {.lh, importc: "laser_hip_cdf_sample_f32_dev".}
+proc laser_hip_cdf_sample_remove_f32_dev*(idx: ptr int32, w: ptr float32, wRowStride: int64, cdf: ptr float32, cdfRowStride: int64, u01: ptr float32, rows: int64, n: int64, k: int64, stream: pointer): cint {.lh, importc: "laser_hip_cdf_sample_remove_f32_dev".}
+proc laser_hip_cdf_sample_rng_f32_dev*(idx: ptr int32, cdf: ptr float32, cdfRowStride: int64, seed: int64, subseq: int64, offset: int64, rows: int64, n: int64, m: int64, stream: pointer): cint {.lh, importc: "laser_hip_cdf_sample_rng_f32_dev".}
+proc laser_hip_cdf_sample_remove_rng_f32_dev*(idx: ptr int32, w: ptr float32, wRowStride: int64, cdf: ptr float32, cdfRowStride: int64, seed: int64, subseq: int64, offset: int64, rows: int64, n: int64, k: int64, stream: pointer): cint {.lh, importc: "laser_hip_cdf_sample_remove_rng_f32_dev".}
+
+proc cumsum*[T](t: HipStorage[T], rows, n: Natural, stream: pointer = nil): HipStorage[T] =
+  ## cumsum(t) of bench_multinomial_samplers.nim:143-148 on the device: `rows` contiguous rows of n elements, the inclusive
+  ## prefix sum of every row in the order of scan_core.h; T is float32, float64, int32 or int64 (int)
+  allocHipStorage(result, rows * n)
+  when T is float32:
+    check laser_hip_cumsum_f32_dev(cast[ptr float32](result.raw_buffer), int64(n), cast[ptr float32](t.raw_buffer), int64(n), int64(rows), int64(n), stream)
+  elif T is float64:
+    check laser_hip_cumsum_f64_dev(cast[ptr float64](result.raw_buffer), int64(n), cast[ptr float64](t.raw_buffer), int64(n), int64(rows), int64(n), stream)
+  elif T is int32:
+    check laser_hip_cumsum_i32_dev(cast[ptr int32](result.raw_buffer), int64(n), cast[ptr int32](t.raw_buffer), int64(n), int64(rows), int64(n), stream)
+  elif T is int64 or T is int:
+    check laser_hip_cumsum_i64_dev(cast[ptr int64](result.raw_buffer), int64(n), cast[ptr int64](t.raw_buffer), int64(n), int64(rows), int64(n), stream)
+  else:
+    {.error: "cumsum: float32, float64, int32 or int64".}
+
+proc searchsorted*[T](input: HipStorage[T], values: HipStorage[T], leftSide: bool, rows, n: Natural, m: Natural = 1, stream: pointer = nil): HipStorage[int32] =
+  ## searchsorted(input, values, leftSide) of bench_multinomial_samplers.nim:162-170: `input` holds `rows` sorted rows of n
+  ## elements, `values` m values per row; lowerBound (leftSide) or upperBound of every value in its row
+  allocHipStorage(result, rows * m)
+  let right = cint(if leftSide: 0 else: 1)
+  when T is float32:
+    check laser_hip_searchsorted_f32_dev(cast[ptr int32](result.raw_buffer), cast[ptr float32](input.raw_buffer), int64(n), cast[ptr float32](values.raw_buffer), int64(rows), int64(n), int64(m), right, stream)
+  elif T is float64:
+    check laser_hip_searchsorted_f64_dev(cast[ptr int32](result.raw_buffer), cast[ptr float64](input.raw_buffer), int64(n), cast[ptr float64](values.raw_buffer), int64(rows), int64(n), int64(m), right, stream)
+  elif T is int32:
+    check laser_hip_searchsorted_i32_dev(cast[ptr int32](result.raw_buffer), cast[ptr int32](input.raw_buffer), int64(n), cast[ptr int32](values.raw_buffer), int64(rows), int64(n), int64(m), right, stream)
+  elif T is int64 or T is int:
+    check laser_hip_searchsorted_i64_dev(cast[ptr int32](result.raw_buffer), cast[ptr int64](input.raw_buffer), int64(n), cast[ptr int64](values.raw_buffer), int64(rows), int64(n), int64(m), right, stream)
+  else:
+    {.error: "searchsorted: float32, float64, int32 or int64".}
+
+proc sample*(probs: HipStorage[float32], rows, n: Natural, nbSamples: Natural, rng: var HipRng, stream: pointer = nil): HipStorage[int32] =
+  ## sample(probs, nb_samples) of bench_multinomial_samplers.nim:172-214: nbSamples == 1 is one cumsum and one right-side search
+  ## per row; more draws are made WITHOUT replacement on a private copy of the weights.  The uniform numbers are those of `rng`,
+  ## which advances by rows * nbSamples.
+  allocHipStorage(result, rows * nbSamples)
+  var cdf: HipStorage[float32]
+  allocHipStorage(cdf, rows * n)
+  let (sd, sq, off) = (cast[int64](rng.seed), cast[int64](rng.subseq), cast[int64](rng.offset))
+  if nbSamples == 1:
+    check laser_hip_cumsum_f32_dev(cast[ptr float32](cdf.raw_buffer), int64(n), cast[ptr float32](probs.raw_buffer), int64(n), int64(rows), int64(n), stream)
+    check laser_hip_cdf_sample_rng_f32_dev(cast[ptr int32](result.raw_buffer), cast[ptr float32](cdf.raw_buffer), int64(n), sd, sq, off, int64(rows), int64(n), 1, stream)
+  else:
+    var w: HipStorage[float32]
+    allocHipStorage(w, rows * n)
+    var shape = [int(rows), int(n)]
+    var strides = [int(n), 1]
+    check laser_hip_copy_strided_b32_dev(pointer(w.raw_buffer), strides[0].addr, pointer(probs.raw_buffer), strides[0].addr, shape[0].addr, 2, stream)
+    check laser_hip_cdf_sample_remove_rng_f32_dev(cast[ptr int32](result.raw_buffer), cast[ptr float32](w.raw_buffer), int64(n), cast[ptr float32](cdf.raw_buffer), int64(n), sd, sq, off, int64(rows), int64(n), int64(nbSamples), stream)
+  rng.offset += uint64(rows * nbSamples)
+
 # ---- forEachReduce (include/laser_hip.h "forEachReduce"): foreach_staged.nim:318 on device buffers ------------------------
 proc laser_hip_foreach_reduce_source(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, accName: cstring, accDtype: cint, merge: cstring, buf: pointer, cap: int64, len: ptr int64): cint {.lh, importc: "laser_hip_foreach_reduce_source".}
 proc laser_hip_foreach_reduce_code(body: cstring, nops: cint, names: ptr cstring, dtypes: ptr cint, writable: ptr cint, nparams: cint, paramNames: ptr cstring, paramDtypes: ptr cint, accName: cstring, accDtype: cint, merge: cstring, arch: cstring, buf: pointer, cap: int64, len: ptr int64): cint {.lh, importc: "laser_hip_foreach_reduce_code".}
