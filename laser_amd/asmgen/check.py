@@ -27,7 +27,7 @@ def reference(A, B, kc, alpha=1.0, beta=0.0, C0=None):
 
 
 def plan_units(tiles, Kd, G, exact, kc, BK, split=True):
-    """host model of the launcher's unit arithmetic (gemm_f32_asm.cpp: plan_launch): P slices per tile, slice length, units per
+    """host model of the launcher's unit arithmetic (asm_plan.h: plan_launch): P slices per tile, slice length, units per
     workgroup"""
     if not split:
         P, slen = 1, (Kd + BK - 1) // BK * BK

@@ -153,7 +153,7 @@ hipError_t run_gemm_core(const GemmArgs<float> &a, hipStream_t s) {
   g_last_f32_asm = 0;
   if (any && few_tiles) LH_RUNG(gemm_slice_parallel<float>(a, 512, s));
   // (a badly filled last round of tiles is the assembly launcher's business: its persistent plan hands the chip's workgroup slots
-  // equal numbers of kc slices and finishes a cut tile with an in-kernel ordered fix-up -- gemm_f32_asm.cpp plan_launch)
+  // equal numbers of kc slices and finishes a cut tile with an in-kernel ordered fix-up -- asm_plan.h plan_launch)
   if (any) LH_RUNG(launch_gemm_f32_asm(a, laser, s));
   if (any && !few_tiles) LH_RUNG(gemm_slice_parallel<float>(a, 512, s));
   return launch_gemm_f32(a, f32_cfg_now(), laser, s);

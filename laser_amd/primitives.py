@@ -137,7 +137,7 @@ def set_f32_asm(mode):
 
 def last_f32_asm():
     """0: the last float32 GEMM launch was a compiler-scheduled kernel; else 1 + the index of the assembly kernel
-    (gemm_f32_asm.cpp: 1 / 2 laser-order / one-chain large tile, 3 / 4 the 128x128 tile, 5..8 the same with B transposed,
+    (asm_kernels.h kKernels: 1 / 2 laser-order / one-chain large tile, 3 / 4 the 128x128 tile, 5..8 the same with B transposed,
     9 / 10 one chain on the 256x128 tile)."""
     return get_option("last_f32_asm")
 

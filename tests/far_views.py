@@ -20,13 +20,13 @@ a 32-bit slip gives a wrong number, which the comparison and the arena checksum 
 Rows of the far operands interleave inside one row pitch -- a pitch is megabytes, a row a few hundred elements -- and the
 dense operands of a pair sit in the gap of the first pitch, so a 4-8 GB span for all three costs one buffer.
 
-Each guard is written as the expression the launcher uses, with the source line next to it.
+Each guard is written as the expression the launcher uses, with the function that holds it next to it.
 
 Guards that cannot be straddled under the 12 GiB cap:
-  * bias strides above 0x3fffffff elements (gemm_f32_asm.cpp:741): a 2-row bias at that stride is 4 GiB and fits, but the span
+  * bias strides above 0x3fffffff elements (asm_plan.h choose_gemm_f32_asm): a 2-row bias at that stride is 4 GiB and fits, but the span
     limit on the same line declines first for any M, N >= 2, so the stride limit alone is unreachable with a real view;
   * gemm_small's K >= 2^30 (gemm_small.hip:203): the kernel is only offered K <= 128 (gemm_small_takes);
-  * the tile-count limits `t * 8 * tn >= 4e9` (gemm_f32_asm.cpp:797, :964, :1024): they need ~10^4 x 10^4 tiles, a C of
+  * the tile-count limits `t * 8 * tn >= 4e9` (asm_plan.h consider_kernel, gemm_f32_asm.cpp launch_gemm_int_asm): they need ~10^4 x 10^4 tiles, a C of
     terabytes;
   * a batch stride past 2^31 ELEMENTS on 8-byte types (16 GiB).  Batch strides of 2^29 elements (2 and 4 GiB) are covered.
 """
@@ -51,44 +51,44 @@ def _f(x):
 
 
 # ---- the guards, as the launchers write them: inside(...) is True where the guarded kernel still takes the view ----------
-def f32_asm_A(rsA):          # gemm_f32_asm.cpp:762  if ((double)a.rsA * 4.0 * 256 >= 4.0e9) return hipErrorNotSupported;
+def f32_asm_A(rsA):          # asm_plan.h gemm_operands_fit<float>  (double)a.rsA * el * rows >= 4.0e9, el = 4, rows = 256
     return not (_f(rsA) * 4.0 * 256 >= 4.0e9)
 
 
-def f32_asm_B(ldb, K=K):     # gemm_f32_asm.cpp:763  (double)a.K * (double)ldb * 4.0 >= 4.0e9   (B row-major)
+def f32_asm_B(ldb, K=K):     # gemm_operands_fit<float>  (double)a.K * (double)ldb * el >= 4.0e9   (B row-major)
     return not (_f(K) * _f(ldb) * 4.0 >= 4.0e9)         # == gemm_mfma.hip:50-51 small() on a row-major B: ld * K * 4 < 4.0e9
 
 
-def f32_asm_Bt(ldb):         # gemm_f32_asm.cpp:763  (double)ldb * 4.0 * 256 >= 4.0e9           (B passed transposed)
+def f32_asm_Bt(ldb):         # gemm_operands_fit<float>  (double)ldb * el * rows >= 4.0e9          (B passed transposed)
     return not (_f(ldb) * 4.0 * 256 >= 4.0e9)
 
 
-def f32_asm_C(rsC, csC=1, M=M, N=N):      # gemm_f32_asm.cpp:764  ((M-1) * rsC + (N-1) * csC + 1.0) * 4.0 > 2147483648.0
+def f32_asm_C(rsC, csC=1, M=M, N=N):      # gemm_operands_fit<float>  ((M-1) * rsC + (N-1) * csC + 1.0) * el > 2147483648.0
     return not ((_f(M - 1) * _f(rsC) + _f(N - 1) * _f(csC) + 1.0) * 4.0 > 2147483648.0)
 
 
-def f32_asm_bias(rs, cs=1, M=M, N=N):     # gemm_f32_asm.cpp:741-742
+def f32_asm_bias(rs, cs=1, M=M, N=N):     # asm_plan.h choose_gemm_f32_asm: the bias view
     return not (rs < 0 or cs < 0 or rs > 0x3fffffff or cs > 0x3fffffff or
                 (_f(M - 1) * rs + _f(N - 1) * cs + 1.0) * 4.0 >= 2147483648.0)
 
 
-def f64_asm_A(rsA):          # gemm_f32_asm.cpp:1012  (double)a.rsA * 8.0 * 128 >= 4.0e9
+def f64_asm_A(rsA):          # gemm_operands_fit<double>  (double)a.rsA * el * rows >= 4.0e9, el = 8, rows = 128
     return not (_f(rsA) * 8.0 * 128 >= 4.0e9)
 
 
-def f64_asm_B(ldb, K=K):     # gemm_f32_asm.cpp:1012  (double)a.K * (double)ldb * 8.0 >= 4.0e9
+def f64_asm_B(ldb, K=K):     # gemm_operands_fit<double>  (double)a.K * (double)ldb * el >= 4.0e9
     return not (_f(K) * _f(ldb) * 8.0 >= 4.0e9)
 
 
-def f64_asm_Bt(ldb):         # gemm_f32_asm.cpp:1012  (double)ldb * 8.0 * 128 >= 4.0e9
+def f64_asm_Bt(ldb):         # gemm_operands_fit<double>  (double)ldb * el * rows >= 4.0e9
     return not (_f(ldb) * 8.0 * 128 >= 4.0e9)
 
 
-def f64_asm_C(rsC, M=M, N=N):             # gemm_f32_asm.cpp:1013  ((M-1) * rsC + N) * 8.0 > 2147483648.0
+def f64_asm_C(rsC, M=M, N=N):             # gemm_operands_fit<double>  ((M-1) * rsC + (N-1) * csC + 1.0) * el > 2147483648.0 with csC = 1
     return not ((_f(M - 1) * _f(rsC) + _f(N)) * 8.0 > 2147483648.0)
 
 
-def int_asm_C(rsC, limbs, M=M, N=N):      # gemm_f32_asm.cpp:964  ((M-1) * rsC + N) * limbs > 2147483648.0
+def int_asm_C(rsC, limbs, M=M, N=N):      # gemm_f32_asm.cpp launch_gemm_int_asm  ((M-1) * rsC + N) * limbs > 2147483648.0
     return not ((_f(M - 1) * _f(rsC) + _f(N)) * _f(limbs) > 2147483648.0)
 
 

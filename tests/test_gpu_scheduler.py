@@ -1,4 +1,4 @@
-"""GPU tests of the assembly kernels' launch plans (laser_amd/csrc/gemm_f32_asm.cpp plan_launch, asmgen/f32_kernel.py sched_next):
+"""GPU tests of the assembly kernels' launch plans (laser_amd/csrc/asm_plan.h plan_launch, launched by gemm_f32_asm.cpp; asmgen/f32_kernel.py sched_next):
 the workgroup -> tile map is arithmetic in the kernel (no table, no lock, nothing to upload), launches may be persistent (fewer
 workgroups than tiles) and may cut tiles at K-slice boundaries, the owner of a tile's slice 0 handing its running sum on to the
 workgroup that owns the rest.  Laser-order results must be the SAME bits whatever the plan (gemm.nim:150-158: slices are independent chains,
@@ -37,7 +37,7 @@ def _mre(got, want):
     return float(np.mean(np.abs(got.astype(np.float64) - want) / np.maximum(np.abs(want), 1e-30)))
 
 
-# kernel index (gemm_f32_asm.cpp kKernels) -> tile; laser-order kernels only here
+# kernel index (asm_kernels.h kKernels) -> tile; laser-order kernels only here
 LASER_KERNELS = {0: (256, 128), 2: (128, 128), 12: (64, 64)}
 LASER_KERNELS_NT = {4: (256, 128), 6: (128, 128), 14: (64, 64)}
 
@@ -376,7 +376,7 @@ def test_no_fix_up_ever_gave_up_waiting(la):
 
 @pytest.mark.parametrize("mode", [0, 1])
 def test_strided_persistent_plan_with_pipelined_tile_transitions(la, oracle, mode):
-    """Round 6 (asmgen/f32_kernel.py Cfg.pipe, gemm_f32_asm.cpp plan_launch): with more tiles than workgroup slots the 256x128 kernels
+    """Round 6 (asmgen/f32_kernel.py Cfg.pipe, asm_plan.h plan_launch): with more tiles than workgroup slots the 256x128 kernels
     run as ONE workgroup per CU that walks tiles v, v + 256, ... without leaving its K loop -- the last bodies of a tile fetch the
     next tile's first K-tiles, the next tile's first body stores this tile's C.  Same bits as one workgroup per tile (also in
     one-chain mode: the chain order does not change), equal to the oracle in laser-order mode; ragged edges, a strided C view, every

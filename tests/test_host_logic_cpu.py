@@ -156,12 +156,12 @@ def test_dma_fed_lds_layouts_are_bank_conflict_free_in_the_model():
 
 def test_bench_kernel_names_match_the_kernel_table():
     """bench.py names the kernel of its `roofline` object from laser_hip_get_option("last_f32_asm") = 1 + index into kKernels
-    (gemm_f32_asm.cpp): the two tables must list the same symbols in the same order, and every symbol must be one the Makefile
+    (asm_kernels.h): the two tables must list the same symbols in the same order, and every symbol must be one the Makefile
     assembles into the embedded code object."""
     import re
     import importlib.util
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "laser_amd", "csrc", "gemm_f32_asm.cpp")).read()
+    src = open(os.path.join(root, "laser_amd", "csrc", "asm_kernels.h")).read()
     start = src.index("KernelInfo kKernels[kNumKernels] = {")
     table = src[start:src.index("\n};", start)]
     symbols = re.findall(r'\{"(lh_[a-z0-9_x]+)"', table)
