@@ -585,6 +585,69 @@ inline Tensor<float> softmax_axis(const Tensor<float> &src, int axis, void *stre
   return dst;
 }
 
+// ---- log, logsumexp, log-softmax and cross-entropy (include/laser_hip.h, the section of that name) over device Tensors ------
+//   laser::log(y, x);  laser::logsumexp(x);  laser::log_softmax(y, x);  laser::softmax_cross_entropy(logits, labels[, &grad, scale])
+// log: llog of log_core.h, faithful and monotone; x broadcasts against y.  The others run over the rows of a 2-D Tensor whose
+// last stride is 1, with exactly the maximum and the sum of laser::softmax.  (asynchronous on `stream`)
+inline void log(Tensor<float> &dst, const Tensor<float> &src, void *stream = nullptr) {
+  const int r = dst.rank(), pad = r - src.rank();
+  if (pad < 0) throw Error(LASER_HIP_E_INVALID, "log: the source has more dimensions than the destination");
+  std::vector<int64_t> ss((size_t)(r > 0 ? r : 1), 0);
+  for (int d = pad; d < r; d++) {  // numpy broadcasting: missing / extent-1 dimensions get stride 0
+    const int64_t e = src.shape[d - pad];
+    if (e != dst.shape[d] && e != 1) throw Error(LASER_HIP_E_INVALID, "log: the source does not broadcast to the destination");
+    ss[d] = e == 1 ? 0 : src.strides[d - pad];
+  }
+  check(laser_hip_log_f32_dev(dst.unsafe_raw_data(), dst.strides.data(), src.unsafe_raw_data(), ss.data(), dst.shape.data(), r, stream));
+}
+inline Tensor<float> log(const Tensor<float> &src, void *stream = nullptr) {
+  Tensor<float> dst = exp_result_like(src);
+  log(dst, src, stream);
+  return dst;
+}
+namespace detail {
+inline void rows_operand(const char *what, const Tensor<float> &t) {
+  if (t.rank() != 2 || t.shape[1] < 1 || (t.shape[1] != 1 && t.strides[1] != 1))
+    throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": a 2-D tensor with contiguous, non-empty rows is needed").c_str());
+}
+}  // namespace detail
+// one value per row: max + llog(sum); a fresh Tensor (rows)
+inline Tensor<float> logsumexp(const Tensor<float> &src, void *stream = nullptr) {
+  detail::rows_operand("logsumexp", src);
+  const int64_t rows = src.shape[0], n = src.shape[1];
+  Tensor<float> dst = newTensor<float>({rows});
+  check(laser_hip_logsumexp_rows_f32_dev(dst.unsafe_raw_data(), 1, src.unsafe_raw_data(), rows > 1 ? src.strides[0] : n, rows, n, stream));
+  return dst;
+}
+// y = (x - max) - llog(sum); dst may be src
+inline void log_softmax(Tensor<float> &dst, const Tensor<float> &src, void *stream = nullptr) {
+  detail::rows_operand("log_softmax", src);
+  detail::rows_operand("log_softmax", dst);
+  if (dst.shape != src.shape) throw Error(LASER_HIP_E_INVALID, "log_softmax: two 2-D tensors of one shape");
+  const int64_t rows = src.shape[0], n = src.shape[1];
+  check(laser_hip_log_softmax_rows_f32_dev(dst.unsafe_raw_data(), rows > 1 ? dst.strides[0] : n, src.unsafe_raw_data(),
+                                           rows > 1 ? src.strides[0] : n, rows, n, stream));
+}
+inline Tensor<float> log_softmax(const Tensor<float> &src, void *stream = nullptr) {
+  Tensor<float> dst = exp_result_like(src);
+  log_softmax(dst, src, stream);
+  return dst;
+}
+// the per-row loss for int32 labels (one per row, contiguous; -1: ignore, any other label outside [0, n): NaN); with `grad`
+// also *grad = (softmax - onehot) * scale, a fresh row-major Tensor like logits (scale 1: a sum, 1 / rows: a mean)
+inline Tensor<float> softmax_cross_entropy(const Tensor<float> &logits, const Tensor<int32_t> &labels, Tensor<float> *grad = nullptr,
+                                           float scale = 1.0f, void *stream = nullptr) {
+  detail::rows_operand("softmax_cross_entropy", logits);
+  const int64_t rows = logits.shape[0], n = logits.shape[1];
+  if (labels.rank() != 1 || labels.shape[0] != rows || (rows > 1 && labels.strides[0] != 1))
+    throw Error(LASER_HIP_E_INVALID, "softmax_cross_entropy: one contiguous int32 label per row is needed");
+  Tensor<float> loss = newTensor<float>({rows});
+  if (grad) *grad = exp_result_like(logits);
+  check(laser_hip_softmax_xent_rows_f32_dev(loss.unsafe_raw_data(), 1, grad ? grad->unsafe_raw_data() : nullptr, n, logits.unsafe_raw_data(),
+                                            rows > 1 ? logits.strides[0] : n, labels.unsafe_raw_data(), rows, n, scale, stream));
+  return loss;
+}
+
 // ---- Random numbers (include/laser_hip.h "Random numbers"): Philox4x32-10 streams and the reference's randomTensor ----------
 //   laser::Rng rng(seed, subseq);               names a stream; (seed, subseq, offset) live on the host, nothing on the device
 //   laser::randomTensor<T>({2, 3}, lo, hi, rng) uniform on the closed interval [lo, hi], T = float, double, int32_t, int64_t:

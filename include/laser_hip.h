@@ -664,6 +664,75 @@ int laser_hip_softmax_axis_f32_dev(float *d_dst, int64_t dst_outer_stride, int64
                                    int64_t outer, int64_t n, int64_t inner, void *stream);
 int laser_hip_softmax_axis_plan(int64_t outer, int64_t n, int64_t inner, int vec, int cus, int64_t *out4);
 
+/* ---- log, logsumexp, log-softmax and cross-entropy (f32): from logits to a loss without leaving the device ---------------
+ * The reference's simd_math files are named exp_log_* but hold no logarithm; llog is this library's own, defined the way
+ * lexp is: one definition, laser_amd/csrc/log_core.h, shared by every kernel below and by the forEach bodies, built from
+ * integer operations, bit casts, an exact float32 -> float64 conversion, float64 multiplies, adds and subtracts each rounded
+ * on its own (no fused multiply-add, no division, no libm) and one float64 -> float32 rounding to nearest even.  For a
+ * float32 x with bits b:
+ *   1. NaN gives NaN (payload unspecified).  +-0 gives -Inf.  Any other x with the sign bit set, -Inf included, gives NaN.
+ *      +Inf gives +Inf.
+ *   2. A subnormal x is normalised in integers (shift its bits left until the exponent field reads 1 and count the shifts
+ *      into the exponent), so no floating-point operation sees a subnormal and nothing depends on flushing.
+ *   3. x = 2^k z with z in [0.69921875, 1.3984375): t = b - 0x3f330000 mod 2^32, k = int32(t) >> 23 (plus the count of
+ *      step 2), i = (t >> 19) & 15, z = float64(bitcast<float>(b - (t & 0xff800000))).  The range is around 1, so next to 1
+ *      nothing cancels: k = 0 there.
+ *   4. r = z * INVC[i] - 1, INVC[i] = float64(1 / midpoint of the i-th sixteenth of the range); the sixteenth that holds 1
+ *      has INVC = 1 and LOGC = +0, so there r = z - 1 exactly.  |r| < 0.02963.
+ *   5. q = (((C6 r + C5) r + C4) r + C3) r + C2 with C_j = float64((-1)^(j+1) / j).
+ *   6. y = ((float64(k) * LN2 + LOGC[i]) + r) + (r * r) * q, LOGC[i] = float64(-ln INVC[i]), LN2 = float64(ln 2).
+ *   7. llog(x) = float32(y).   llog(1) = +0 exactly.
+ * Two properties, proved over all 2^31 - 2^23 positive finite float32 on the CPU (tests/cpp/log_core_host.cpp "sweep"):
+ *   faithful: llog(x) is one of the two float32 that bracket the true logarithm (error < 1 ulp; measured against
+ *     (float)log((double)x): maximum 0.501403 ulp at x = bits 0x3f8301a3, mean 0.250000 ulp);
+ *   monotone: non-decreasing over the positive float32 in increasing order.
+ * laser_hip_log_f32_dev: dst[idx] = llog(src[idx]) for every index of `shape`; the contract of laser_hip_exp_f32_dev (rank
+ *   <= 6, ELEMENT strides, negative strides allowed, stride 0 on src only, dst == src with equal strides allowed).
+ * laser_hip_log_f32: host pointers, `len` contiguous elements, synchronous.
+ * laser_log(x) is callable in forEach / forEachReduce bodies: the prelude embeds log_core.h after exp_core.h.  The name is
+ *   reserved like laser_exp.
+ * The three row entry points below see rows x[0..n) at d_src + row * src_row_stride, exactly as
+ * laser_hip_softmax_rows_f32_dev does, and m and s are exactly that softmax's: m = the maximum of the row under the rule of
+ * reduce_max, s = the sum of lexp(x[j] - m) in the order of "Reductions" applied to the row as a 1-D array of n float32.
+ * s >= 1 (the maximal element adds lexp(0) = 1), so llog(s) >= 0 and nothing cancels.  A row's result is a function of its
+ * values, n (and its label) alone.  1 <= n <= 2^26, rows >= 0 (0: nothing happens), row strides >= n, per-row strides >= 1,
+ * any base alignment; anything else LASER_HIP_E_INVALID.  Asynchronous on `stream`.
+ * laser_hip_logsumexp_rows_f32_dev: d_dst[row * dst_stride] = m + llog(s), one rounded add.  m = +Inf gives +Inf, m = -Inf
+ *   (a row of all -Inf) gives -Inf, a NaN in the row gives NaN.  Reads the row once (n <= 8192) or twice, writes 4 bytes.
+ * laser_hip_log_softmax_rows_f32_dev: y[j] = (x[j] - m) - llog(s): two separately rounded subtractions, never x[j] - lse
+ *   (which loses the low bits when |m| is large).  No special cases: a NaN in the row, a row of all -Inf or a +Inf maximum
+ *   give what IEEE gives (NaN where x[j] - m is NaN), as the softmax documents.  Every finite result is <= 0.  dst == src
+ *   with equal row strides allowed.
+ * laser_hip_softmax_xent_rows_f32_dev: the softmax cross-entropy with integer labels, d_labels[row] an int32 (the index type
+ *   the samplers return), in one launch; d_loss or d_grad may be NULL (not both), and the loss-only form reads the logits and
+ *   writes `rows` floats.
+ *     loss = llog(s) - (x[label] - m)                 at d_loss + row * loss_stride; the bits of 0 - log_softmax[label]
+ *     grad[j] = (lexp(x[j] - m) / s - [j == label]) * scale    at d_grad + row * grad_row_stride; the division is the
+ *       softmax's correctly rounded one (so the quotient has the softmax's bits), the subtraction and the multiply are rounded
+ *       separately.  scale: 1 for a sum over the batch, 1 / rows for a mean.
+ *   label == -1 (the samplers' "no draw") means ignore: the loss is +0 and the gradient row +0.  Any other label outside
+ *   [0, n) gives a NaN loss and a NaN gradient row: a wrong label never passes silently.  x[label] is one scalar load.
+ *   d_grad may not be d_src.
+ * laser_hip_softmax_rows_plan: what the three calls above launch for a shape, without a device: out3 = {kernel code,
+ *   workgroups, LDS bytes}.  Code 0 = one wave per row, four rows per workgroup (n <= 1024), 1 = one workgroup per row, the
+ *   row in registers (n <= 8192), 2 = long rows streamed, chunk partials in LDS; + 4 when vec == 0 (a base or a row stride off
+ *   its 16-byte alignment: single-element accesses) -- same bits all six.  At most 2048 workgroups, which stride over the
+ *   rows.  The logic is laser_amd/csrc/softmax_rows_plan.h, which has no HIP dependency.
+ * Not built: float64, these along a strided axis (the column-strip kernels), dense (probability-vector) targets, a fused
+ *   mean over the batch (reduce_sum over the loss vector does it).
+ * No gfx950 device: LASER_HIP_E_NODEVICE. */
+int laser_hip_log_f32_dev(float *d_dst, const int64_t *dst_strides, const float *d_src, const int64_t *src_strides,
+                          const int64_t *shape, int rank, void *stream);
+int laser_hip_log_f32(float *dst, const float *src, int64_t len);
+int laser_hip_logsumexp_rows_f32_dev(float *d_dst, int64_t dst_stride, const float *d_src, int64_t src_row_stride,
+                                     int64_t rows, int64_t n, void *stream);
+int laser_hip_log_softmax_rows_f32_dev(float *d_dst, int64_t dst_row_stride, const float *d_src, int64_t src_row_stride,
+                                       int64_t rows, int64_t n, void *stream);
+int laser_hip_softmax_xent_rows_f32_dev(float *d_loss, int64_t loss_stride, float *d_grad, int64_t grad_row_stride,
+                                        const float *d_src, int64_t src_row_stride, const int32_t *d_labels,
+                                        int64_t rows, int64_t n, float scale, void *stream);
+int laser_hip_softmax_rows_plan(int64_t rows, int64_t n, int vec, int64_t *out3);
+
 /* ---- F+tree weighted sampler (f32): benchmarks/random_sampling/fenwicktree.nim, bench_multinomial_samplers.nim --------
  * The reference's `Sampler` over device rows: from a row of weights (the softmax above, or anything non-negative) to drawn
  * indices without leaving the device.  All float32, every operation rounded to float32 on its own, no denormal flushed.
@@ -870,7 +939,7 @@ int laser_hip_cdf_sample_remove_rng_f32_dev(int32_t *d_idx, float *d_w, int64_t 
  *   compute units); the most blocks one lane walks; the index of the first block, offset >> 2}.  words_per_elem: 1 for the 32-bit
  *   types, 2 for the 64-bit ones.  The fills plan for 256 compute units on every device.  The logic is
  *   laser_amd/csrc/random_plan.h, which has no HIP dependency.
- * Not built: normal and other non-uniform distributions (they need a bit-defined log and sincos first), the other six element
+ * Not built: normal and other non-uniform distributions (they need a bit-defined sincos beside llog first), the other six element
  *   types, strided destinations, a laser_rand callable in forEach bodies. */
 #define LASER_HIP_RANDOM_MAX_N (1ll << 60)
 int laser_hip_random_plan(int64_t n, int words_per_elem, int64_t offset, int dst_misaligned, int cus, int64_t *out4);

@@ -27,6 +27,7 @@
 #include "sampler_plan.h"
 #include "scan_plan.h"
 #include "softmax_axis_plan.h"
+#include "softmax_rows_plan.h"
 
 using namespace laser_hip;
 
@@ -1432,6 +1433,96 @@ int laser_hip_softmax_axis_plan(int64_t outer, int64_t n, int64_t inner, int vec
     return fail(LASER_HIP_E_INVALID, "softmax_axis_plan: outer %lld, n %lld, inner %lld outside what softmax_axis takes", (long long)outer,
                 (long long)n, (long long)inner);
   for (int i = 0; i < 4; i++) out4[i] = p[i];
+  return LASER_HIP_OK;
+}
+
+// ---- llog, logsumexp, log-softmax and the softmax cross-entropy (log_core.h, log_softmax.hip, softmax_rows_plan.h) --------
+int laser_hip_log_f32_dev(float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
+                          void *stream) {
+  if (rank < 0 || rank > kMaxRank) return fail(LASER_HIP_E_INVALID, "log: rank %d outside 0..%d (LASER_MAXRANK)", rank, kMaxRank);
+  if (rank > 0 && (!ds || !ss || !shape)) return fail(LASER_HIP_E_INVALID, "log: null shape / strides");
+  int64_t total = 1;
+  for (int d = 0; d < rank; d++) {
+    if (shape[d] < 0) return fail(LASER_HIP_E_INVALID, "log: negative extent");
+    if (shape[d] > 1 && ds[d] == 0) return fail(LASER_HIP_E_INVALID, "log: stride 0 on the destination (dimension %d)", d);
+    total *= shape[d];
+  }
+  if (int rc = ensure_init()) return rc;
+  if (total == 0) return LASER_HIP_OK;
+  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "log: null buffer");
+  HIP_TRY(launch_log_f32(dst, ds, src, ss, shape, rank, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+// the host-pointer form: through device scratch, in place there, synchronous; the same kernel as the _dev form
+int laser_hip_log_f32(float *dst, const float *src, int64_t len) {
+  if (len < 0 || (len > 0 && (!dst || !src))) return fail(LASER_HIP_E_INVALID, "log: bad argument");
+  if (int rc = ensure_init()) return rc;
+  if (len == 0) return LASER_HIP_OK;
+  HostCall hc;
+  if (hc.rc) return hc.rc;
+  void *d_buf;
+  if (int rc = scratch_get(0, (size_t)len * sizeof(float), &d_buf)) return rc;
+  HIP_TRY(hipMemcpy(d_buf, src, (size_t)len * sizeof(float), hipMemcpyHostToDevice));
+  const int64_t stride = 1;
+  HIP_TRY(launch_log_f32((float *)d_buf, &stride, (const float *)d_buf, &stride, &len, 1, nullptr));
+  HIP_TRY(hipMemcpy(dst, d_buf, (size_t)len * sizeof(float), hipMemcpyDeviceToHost));
+  return LASER_HIP_OK;
+}
+// the checks the three row entry points share, in the order of the softmax entry point
+static int rows_check(const char *what, int64_t src_row_stride, int64_t rows, int64_t n) {
+  if (n < 1 || n > LASER_HIP_SOFTMAX_MAX_N) return fail(LASER_HIP_E_INVALID, "%s: row length %lld outside 1..2^26", what, (long long)n);
+  if (rows < 0) return fail(LASER_HIP_E_INVALID, "%s: negative row count", what);
+  if (src_row_stride < n)
+    return fail(LASER_HIP_E_INVALID, "%s: source row stride %lld below the row length %lld", what, (long long)src_row_stride, (long long)n);
+  return LASER_HIP_OK;
+}
+int laser_hip_logsumexp_rows_f32_dev(float *dst, int64_t dst_stride, const float *src, int64_t src_row_stride, int64_t rows,
+                                     int64_t n, void *stream) {
+  if (int rc = rows_check("logsumexp", src_row_stride, rows, n)) return rc;
+  if (dst_stride < 1) return fail(LASER_HIP_E_INVALID, "logsumexp: destination stride %lld below 1", (long long)dst_stride);
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0) return LASER_HIP_OK;
+  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "logsumexp: null buffer");
+  HIP_TRY(launch_logsumexp_rows_f32(dst, dst_stride, src, src_row_stride, rows, n, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_log_softmax_rows_f32_dev(float *dst, int64_t dst_row_stride, const float *src, int64_t src_row_stride, int64_t rows,
+                                       int64_t n, void *stream) {
+  if (int rc = rows_check("log_softmax", src_row_stride, rows, n)) return rc;
+  if (dst_row_stride < n)
+    return fail(LASER_HIP_E_INVALID, "log_softmax: destination row stride %lld below the row length %lld", (long long)dst_row_stride,
+                (long long)n);
+  if (dst == src && dst_row_stride != src_row_stride) return fail(LASER_HIP_E_INVALID, "log_softmax: in place needs equal row strides");
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0) return LASER_HIP_OK;
+  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "log_softmax: null buffer");
+  HIP_TRY(launch_log_softmax_rows_f32(dst, dst_row_stride, src, src_row_stride, rows, n, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_softmax_xent_rows_f32_dev(float *loss, int64_t loss_stride, float *grad, int64_t grad_row_stride, const float *src,
+                                        int64_t src_row_stride, const int32_t *labels, int64_t rows, int64_t n, float scale,
+                                        void *stream) {
+  if (int rc = rows_check("softmax_xent", src_row_stride, rows, n)) return rc;
+  if (!loss && !grad) return fail(LASER_HIP_E_INVALID, "softmax_xent: neither a loss nor a gradient to write");
+  if (loss && loss_stride < 1) return fail(LASER_HIP_E_INVALID, "softmax_xent: loss stride %lld below 1", (long long)loss_stride);
+  if (grad && grad_row_stride < n)
+    return fail(LASER_HIP_E_INVALID, "softmax_xent: gradient row stride %lld below the row length %lld", (long long)grad_row_stride,
+                (long long)n);
+  if (grad == src) return fail(LASER_HIP_E_INVALID, "softmax_xent: the gradient may not overwrite the logits (x[label] is read from them)");
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0) return LASER_HIP_OK;
+  if (!src || !labels) return fail(LASER_HIP_E_INVALID, "softmax_xent: null buffer");
+  HIP_TRY(launch_softmax_xent_rows_f32(loss, loss_stride, grad, grad_row_stride, src, src_row_stride, labels, rows, n, scale,
+                                       (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_softmax_rows_plan(int64_t rows, int64_t n, int vec, int64_t *out3) {
+  if (!out3) return fail(LASER_HIP_E_INVALID, "softmax_rows_plan: null out3");
+  long long p[3];
+  if (lh_softmax_rows_plan(rows, n, vec, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "softmax_rows_plan: rows %lld, n %lld outside what the row entry points take", (long long)rows,
+                (long long)n);
+  for (int i = 0; i < 3; i++) out3[i] = p[i];
   return LASER_HIP_OK;
 }
 

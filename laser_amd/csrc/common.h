@@ -235,6 +235,16 @@ hipError_t launch_softmax_axis_f32(float *dst, int64_t dst_outer_stride, int64_t
                                    int64_t src_outer_stride, int64_t src_axis_stride, int64_t outer, int64_t n, int64_t inner,
                                    hipStream_t s);
 extern std::atomic<int> g_last_softmax_kernel;
+// llog over strided views, and logsumexp, log-softmax and the softmax cross-entropy over rows (log_softmax.hip; log_core.h is
+// the definition of llog, softmax_rows_plan.h picks the kernel).  The cross-entropy writes loss, grad or both (null: not that one).
+hipError_t launch_log_f32(float *dst, const int64_t *dstrides, const float *src, const int64_t *sstrides, const int64_t *shape,
+                          int rank, hipStream_t s);
+hipError_t launch_logsumexp_rows_f32(float *dst, int64_t dstride, const float *src, int64_t sstride, int64_t rows, int64_t n,
+                                     hipStream_t s);
+hipError_t launch_log_softmax_rows_f32(float *dst, int64_t dstride, const float *src, int64_t sstride, int64_t rows, int64_t n,
+                                       hipStream_t s);
+hipError_t launch_softmax_xent_rows_f32(float *loss, int64_t loss_stride, float *grad, int64_t grad_stride, const float *src,
+                                        int64_t sstride, const int32_t *labels, int64_t rows, int64_t n, float scale, hipStream_t s);
 // the F+tree weighted sampler (sampler.hip; sampler_plan.h picks the build kernel): tree images of 2 P elements per row
 hipError_t launch_sampler_build_f32(float *tree, int64_t tree_row_stride, const float *w, int64_t w_row_stride, int64_t rows, int64_t n,
                                     hipStream_t s);

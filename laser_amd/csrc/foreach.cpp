@@ -28,7 +28,7 @@
 #include "capi_internal.h"
 #include "common.h"
 #include "foreach_template.h"  // generated from foreach_kernel.hip.in, foreach_reduce_kernel.hip.in, reduce_core.h and
-                                // exp_core.h: lh_foreach_template, lh_foreach_reduce_template, lh_reduce_core, lh_exp_core
+                                // exp_core.h, log_core.h: lh_foreach_template, lh_foreach_reduce_template, lh_reduce_core, lh_exp_core, lh_log_core
 
 using namespace laser_hip;
 
@@ -95,6 +95,7 @@ int check_name(const char *what, int i, const char *name) {
   if (s.rfind("lh_", 0) == 0 || s.rfind("__", 0) == 0)
     return fail(LASER_HIP_E_INVALID, "foreach: %s name '%s' is reserved (lh_ and __ prefixes)", what, name);
   if (s == "laser_exp") return fail(LASER_HIP_E_INVALID, "foreach: %s name 'laser_exp' is reserved (exp_core.h)", what);
+  if (s == "laser_log") return fail(LASER_HIP_E_INVALID, "foreach: %s name 'laser_log' is reserved (log_core.h)", what);
   return LASER_HIP_OK;
 }
 
@@ -188,9 +189,9 @@ std::string generate(const Spec &sp) {
          sp.merge + "\n;\n}\n";
   const std::string tpl = lh_foreach_template, mark = "\n@LH_SPEC@\n";
   const size_t at = tpl.find(mark) + 1;
-  // forEach's prelude, then lexp (exp_core.h: laser_exp for the bodies); forEachReduce: then the order (reduce_core.h); then
-  // the spec and the kernels
-  const std::string head = tpl.substr(0, at) + lh_exp_core + (sp.reduce ? std::string(lh_reduce_core) : std::string());
+  // forEach's prelude, then lexp and llog (exp_core.h, log_core.h: laser_exp and laser_log for the bodies); forEachReduce:
+  // then the order (reduce_core.h); then the spec and the kernels
+  const std::string head = tpl.substr(0, at) + lh_exp_core + lh_log_core + (sp.reduce ? std::string(lh_reduce_core) : std::string());
   // the lines after the body report their line in the generated source again
   const size_t line = std::count(head.begin(), head.end(), '\n') + std::count(s.begin(), s.end(), '\n') + 2;
   s += "#line " + std::to_string(line) + (sp.reduce ? " \"foreach_reduce.hip\"\n" : " \"foreach.hip\"\n");

@@ -1,15 +1,21 @@
 """Laser's table-driven exp and the row softmax on top of it (laser/primitives/simd_math/exp_log_*.nim; include/laser_hip.h
-"exp and row softmax"), float32:
+"exp and row softmax"), and the way from logits to a loss (include/laser_hip.h "log, logsumexp, log-softmax and
+cross-entropy"), float32:
 
     laser_amd.exp(t)        lexp of every element: the exported SIMD `exp*` of the reference, bit for bit
     laser_amd.softmax(t)    softmax over the rows of a 2-D tensor, summed in the fixed order of the reductions
     laser_amd.softmax(t, axis=k)   the same along any axis of a tensor of rank 1 .. 6: bit for bit what the row form gives the
                             same values as rows (not built: float64, backward)
+    laser_amd.log(t)        llog of every element: the bit-defined logarithm of laser_amd/csrc/log_core.h
+    laser_amd.logsumexp(t)  one value per row of a 2-D tensor: max + llog(sum), max and sum exactly the softmax's
+    laser_amd.log_softmax(t)       (x - max) - llog(sum) over the rows of a 2-D tensor
+    laser_amd.softmax_cross_entropy(logits, labels, grad=False, scale=1.0)   the per-row loss for int32 labels (-1: ignore),
+                            and with grad=True also (softmax - onehot) * scale
 
 An operand is a laser_amd.Tensor or a torch CUDA tensor (anything with __cuda_array_interface__); `exp` also takes a host
 float32 numpy array, like the reference's benchmark loop.  With out=None a device call returns a fresh row-major Tensor;
 with `out` it writes there (out may be the input) and returns it.  Device calls are asynchronous on the current torch
-stream.  Inside forEach / forEachReduce bodies the same function is `laser_exp(x)`.
+stream.  Inside forEach / forEachReduce bodies the same functions are `laser_exp(x)` and `laser_log(x)`.
 """
 import ctypes as C
 
@@ -27,8 +33,7 @@ def _f32(name, obj):
     return v
 
 
-def exp(t, out=None):
-    """lexp(t), elementwise.  `t` broadcasts against `out` like numpy; out=None: a fresh Tensor of t's shape."""
+def _elementwise(fn, t, out):
     if isinstance(t, np.ndarray):   # the host-pointer form: contiguous float32, synchronous
         if t.dtype != np.float32:
             raise TypeError(f"host arrays: float32 only (got {t.dtype})")
@@ -36,7 +41,7 @@ def exp(t, out=None):
             raise TypeError("out= is for device inputs; a host array returns its result")
         a = np.ascontiguousarray(t)
         r = np.empty_like(a)
-        _lib.check(_lib.lib().laser_hip_exp_f32(r.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), a.size))
+        _lib.check(getattr(_lib.lib(), f"laser_hip_{fn}_f32")(r.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), a.size))
         return r
     src = _f32("t", t)
     if out is None:
@@ -44,9 +49,21 @@ def exp(t, out=None):
     dst = _f32("out", out)
     r = dst.rank
     arr = lambda v: (C.c_int64 * max(r, 1))(*v)
-    _lib.check(_lib.lib().laser_hip_exp_f32_dev(C.c_void_p(dst.ptr), arr(dst.strides), C.c_void_p(src.ptr),
-                                                arr(_bcast_strides(src, dst.shape)), arr(dst.shape), r, _stream()))
+    _lib.check(getattr(_lib.lib(), f"laser_hip_{fn}_f32_dev")(C.c_void_p(dst.ptr), arr(dst.strides), C.c_void_p(src.ptr),
+                                                              arr(_bcast_strides(src, dst.shape)), arr(dst.shape), r, _stream()))
     return out
+
+
+def exp(t, out=None):
+    """lexp(t), elementwise.  `t` broadcasts against `out` like numpy; out=None: a fresh Tensor of t's shape."""
+    return _elementwise("exp", t, out)
+
+
+def log(t, out=None):
+    """llog(t), elementwise: the natural logarithm of laser_amd/csrc/log_core.h, faithful (error below one ulp) and monotone
+    over every positive float32; +-0 gives -Inf, a negative value NaN, a subnormal is taken as the number it is.  Operands
+    as `exp`: a device tensor (`t` broadcasts against `out`) or a host float32 array."""
+    return _elementwise("log", t, out)
 
 
 def _collapse(dims):
@@ -134,3 +151,113 @@ def _softmax_axis(t, out, axis):
     raise ValueError(f"softmax: axis {axis} of shapes {src.shape} with strides {src.strides} (t) and {dst.strides} (out): the dims "
                      "before the axis must collapse into one stride and the dims after it into one unit-stride run, in both "
                      "(make the tensor contiguous)")
+
+
+def _rows_view(op, name, v, axis):
+    """(rows, row stride, n) of `v` as rows of n contiguous elements: a 2-D operand with last stride 1, or with `axis` one
+    whose axis has stride 1 while all other dims collapse into one stride"""
+    if axis is None:
+        if v.rank != 2:
+            raise ValueError(f"{op}: {name} has rank {v.rank} (a 2-D tensor is needed)")
+        if v.shape[1] != 1 and v.strides[1] != 1:
+            raise ValueError(f"{op}: {name} has last stride {v.strides[1]} (the elements of a row must be contiguous)")
+        rows, n = v.shape
+        return rows, (v.strides[0] if rows > 1 else n), n
+    n = v.shape[axis]
+    if 0 in v.shape:
+        return 0, max(n, 1), n
+    fit = _axis_view(v, axis)[1]
+    if fit is None or (fit[0] > 1 and fit[1] < n):
+        raise ValueError(f"{op}: axis {axis} of {name} (shape {v.shape}, strides {v.strides}) is not the unit-stride one with all "
+                         "other dims collapsing into one row stride; these kernels run along contiguous rows only -- move the axis "
+                         "last first (transpose2D_batched)")
+    return fit[0], (fit[1] if fit[0] > 1 else n), n
+
+
+def _axis_arg(op, v, axis):
+    if axis is None:
+        return None
+    if not 1 <= v.rank <= 6:
+        raise ValueError(f"{op}: t has rank {v.rank} (1 .. 6 with axis=)")
+    if not isinstance(axis, (int, np.integer)) or not -v.rank <= axis < v.rank:
+        raise ValueError(f"{op}: axis {axis!r} outside a tensor of rank {v.rank}")
+    return int(axis) % v.rank
+
+
+def logsumexp(t, out=None, axis=None):
+    """One value per row of the 2-D `t` (last stride 1): max + llog(sum of lexp(x - max)), max and sum exactly those of
+    `softmax`, so it depends on the row's values and length alone.  A row whose maximum is +Inf gives +Inf, a row of all -Inf
+    gives -Inf, a NaN in the row NaN.  Returns (or fills `out`, of) shape (rows,).  `axis` is accepted where that axis has
+    stride 1 and all other dims collapse into one row stride (the result then has t's shape without the axis); any other
+    layout: ValueError -- move the axis last with transpose2D_batched."""
+    src = _f32("t", t)
+    axis = _axis_arg("logsumexp", src, axis)
+    rows, ss, n = _rows_view("logsumexp", "t", src, axis)
+    shape = (rows,) if axis is None else src.shape[:axis] + src.shape[axis + 1:]
+    if out is None:
+        out = newTensor(np.float32, *shape)
+    dst = _f32("out", out)
+    if dst.shape != tuple(shape):
+        raise ValueError(f"logsumexp: out has shape {dst.shape}, {tuple(shape)} is needed")
+    if n < 1:
+        raise ValueError("logsumexp: empty rows")
+    if rows == 0:
+        return out
+    one = _collapse(list(zip(dst.shape, dst.strides)))
+    if one is None:
+        raise ValueError(f"logsumexp: out (shape {dst.shape}, strides {dst.strides}) does not collapse into one stride")
+    ds = one[1] if one[1] is not None else 1
+    if ds < 1:
+        raise ValueError(f"logsumexp: out has stride {ds} (a positive stride is needed)")
+    _lib.check(_lib.lib().laser_hip_logsumexp_rows_f32_dev(C.c_void_p(dst.ptr), ds, C.c_void_p(src.ptr), ss, rows, n, _stream()))
+    return out
+
+
+def log_softmax(t, out=None, axis=None):
+    """log of the softmax over the rows of the 2-D `t` (last stride 1), without its underflow: y = (x - max) - llog(sum), two
+    rounded subtractions, max and sum exactly those of `softmax`.  Every finite result is <= 0; a NaN in a row or a row of all
+    -Inf gives a NaN row.  `out` may be `t`.  `axis` as in logsumexp (t and out must both fit)."""
+    src = _f32("t", t)
+    axis = _axis_arg("log_softmax", src, axis)
+    if out is None:
+        out = newTensor(np.float32, *src.shape)
+    dst = _f32("out", out)
+    if dst.shape != src.shape:
+        raise ValueError(f"log_softmax: out has shape {dst.shape}, t has {src.shape}")
+    rows, ss, n = _rows_view("log_softmax", "t", src, axis)
+    _, ds, _ = _rows_view("log_softmax", "out", dst, axis)
+    if n < 1:
+        raise ValueError("log_softmax: empty rows")
+    if rows == 0:
+        return out
+    _lib.check(_lib.lib().laser_hip_log_softmax_rows_f32_dev(C.c_void_p(dst.ptr), ds, C.c_void_p(src.ptr), ss, rows, n, _stream()))
+    return out
+
+
+def softmax_cross_entropy(logits, labels, grad=False, scale=1.0):
+    """The softmax cross-entropy of the rows of the 2-D `logits` (last stride 1) against integer `labels` (int32, one per row,
+    on the device: what the samplers return), in one launch: loss = llog(sum) - (x[label] - max), a fresh Tensor (rows,).
+    grad=True returns (loss, grad) with grad = (softmax(logits) - onehot(labels)) * scale, a fresh Tensor like logits whose
+    softmax has exactly the bits of `softmax`; scale is 1 for a summed loss and 1 / rows for a mean.  A label of -1 is
+    ignored (loss +0, gradient row +0); any other label outside [0, n) gives a NaN loss and a NaN gradient row."""
+    src = _f32("logits", logits)
+    rows, ss, n = _rows_view("softmax_cross_entropy", "logits", src, None)
+    lab = _View("labels", labels)
+    if lab.dtype != np.int32:
+        raise TypeError(f"softmax_cross_entropy: labels have element type {lab.dtype} (int32 only)")
+    one = _collapse(list(zip(lab.shape, lab.strides)))
+    count = 1
+    for e in lab.shape:
+        count *= e
+    if count != rows or lab.rank < 1 or one is None or one[1] not in (None, 1):
+        raise ValueError(f"softmax_cross_entropy: labels of shape {lab.shape}, strides {lab.strides} ({rows} contiguous labels, one per "
+                         "row, are needed)")
+    if n < 1:
+        raise ValueError("softmax_cross_entropy: empty rows")
+    loss = newTensor(np.float32, rows)
+    g = newTensor(np.float32, rows, n) if grad else None
+    if rows:
+        _lib.check(_lib.lib().laser_hip_softmax_xent_rows_f32_dev(
+            C.c_void_p(_View("loss", loss).ptr), 1, C.c_void_p(_View("grad", g).ptr) if grad else None, n, C.c_void_p(src.ptr), ss,
+            C.c_void_p(lab.ptr), rows, n, float(scale), _stream()))
+    return (loss, g) if grad else loss

@@ -657,6 +657,33 @@ proc softmaxAxis*(dst: DevicePtr[float32], dstOuterStride, dstAxisStride: int, s
   ## o * outerStride + k * axisStride + i (element strides); every column bit for bit what `softmax` gives it as a row
   check laser_hip_softmax_axis_f32_dev(cast[ptr float32](dst), int64(dstOuterStride), int64(dstAxisStride), cast[ptr float32](src), int64(srcOuterStride), int64(srcAxisStride), int64(outer), int64(n), int64(inner), stream)
 
+# ---- log, logsumexp, log-softmax and cross-entropy (include/laser_hip.h, the section of that name) ------------------------
+# log is llog of log_core.h: faithful and monotone over every positive float32.  The row procs use exactly the maximum and the
+# sum of `softmax`.
+proc laser_hip_log_f32(dst: ptr float32, src: ptr float32, len: int64): cint {.lh, importc: "laser_hip_log_f32".}
+proc laser_hip_log_f32_dev*(dst: ptr float32, dstStrides: ptr int64, src: ptr float32, srcStrides: ptr int64, shape: ptr int64, rank: cint, stream: pointer): cint {.lh, importc: "laser_hip_log_f32_dev".}
+proc laser_hip_logsumexp_rows_f32_dev*(dst: ptr float32, dstStride: int64, src: ptr float32, srcRowStride: int64, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_logsumexp_rows_f32_dev".}
+proc laser_hip_log_softmax_rows_f32_dev*(dst: ptr float32, dstRowStride: int64, src: ptr float32, srcRowStride: int64, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_log_softmax_rows_f32_dev".}
+proc laser_hip_softmax_xent_rows_f32_dev*(loss: ptr float32, lossStride: int64, grad: ptr float32, gradRowStride: int64, src: ptr float32, srcRowStride: int64, labels: ptr int32, rows: int64, n: int64, scale: float32, stream: pointer): cint {.lh, importc: "laser_hip_softmax_xent_rows_f32_dev".}
+proc laser_hip_softmax_rows_plan*(rows: int64, n: int64, vec: cint, out3: ptr int64): cint {.lh, importc: "laser_hip_softmax_rows_plan".}
+
+proc log*(dst, src: ptr (float32 or UncheckedArray[float32]), len: Natural) =
+  ## dst[i] = ln(src[i]) over a contiguous range of float32 (host memory; the GPU computes it)
+  check laser_hip_log_f32(cast[ptr float32](dst), cast[ptr float32](src), int64(len))
+
+proc logsumexp*(dst: DevicePtr[float32], dstStride: int, src: DevicePtr[float32], srcRowStride: int, rows, n: Natural, stream: pointer = nil) =
+  ## dst[row * dstStride] = max + ln(sum of exp(x - max)) of each row of a device matrix (row elements contiguous)
+  check laser_hip_logsumexp_rows_f32_dev(cast[ptr float32](dst), int64(dstStride), cast[ptr float32](src), int64(srcRowStride), int64(rows), int64(n), stream)
+
+proc logSoftmax*(dst: DevicePtr[float32], dstRowStride: int, src: DevicePtr[float32], srcRowStride: int, rows, n: Natural, stream: pointer = nil) =
+  ## y = (x - max) - ln(sum) over the rows of a device matrix; dst may be src
+  check laser_hip_log_softmax_rows_f32_dev(cast[ptr float32](dst), int64(dstRowStride), cast[ptr float32](src), int64(srcRowStride), int64(rows), int64(n), stream)
+
+proc softmaxCrossEntropy*(loss: DevicePtr[float32], lossStride: int, grad: DevicePtr[float32], gradRowStride: int, src: DevicePtr[float32], srcRowStride: int, labels: DevicePtr[int32], rows, n: Natural, scale: float32 = 1'f32, stream: pointer = nil) =
+  ## Arraymancer's sparse_softmax_cross_entropy and its gradient in one launch: loss per row and (softmax - onehot) * scale;
+  ## loss or grad may be nil (not both); label -1 is ignored, any other label outside 0 ..< n gives NaN
+  check laser_hip_softmax_xent_rows_f32_dev(cast[ptr float32](loss), int64(lossStride), cast[ptr float32](grad), int64(gradRowStride), cast[ptr float32](src), int64(srcRowStride), cast[ptr int32](labels), int64(rows), int64(n), scale, stream)
+
 # ---- F+tree weighted sampler (include/laser_hip.h "F+tree weighted sampler"): fenwicktree.nim over HipStorage -----------
 # One tree image of 2 P float32 per row (P = the next power of two >= n; the reference's array shifted up by one slot).  The
 # uniform numbers are the caller's, or come from a HipRng stream ("Random numbers" below): the overloads taking `rng`.
