@@ -648,6 +648,50 @@ inline Tensor<float> softmax_cross_entropy(const Tensor<float> &logits, const Te
   return loss;
 }
 
+// ---- activations (include/laser_hip.h "Activations") over device Tensors ----------------------------------------------------
+//   laser::tanh(y, x);  laser::sigmoid(y, x);  laser::activation(y, x, Activation::relu);
+//   laser::activation_grad(dx, dy, y, Activation::tanh);                           (asynchronous on `stream`)
+// tanh and sigmoid are ltanh and lsigmoid of act_core.h (faithful, monotone, tanh odd bit for bit); relu is the fused
+// epilogue's rule.  The gradient takes the forward OUTPUT y; its float32 operations are rounded one by one.  x (dy, y)
+// broadcast against the destination, which may be one of them.
+namespace detail {
+inline std::vector<int64_t> bcast_strides(const char *what, const Tensor<float> &dst, const Tensor<float> &src) {
+  const int r = dst.rank(), pad = r - src.rank();
+  if (pad < 0) throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": an operand has more dimensions than the destination").c_str());
+  std::vector<int64_t> ss((size_t)(r > 0 ? r : 1), 0);
+  for (int d = pad; d < r; d++) {  // numpy broadcasting: missing / extent-1 dimensions get stride 0
+    const int64_t e = src.shape[d - pad];
+    if (e != dst.shape[d] && e != 1) throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": an operand does not broadcast to the destination").c_str());
+    ss[d] = e == 1 ? 0 : src.strides[d - pad];
+  }
+  return ss;
+}
+}  // namespace detail
+inline void activation(Tensor<float> &dst, const Tensor<float> &src, Activation act, void *stream = nullptr) {
+  const std::vector<int64_t> ss = detail::bcast_strides("activation", dst, src);
+  check(laser_hip_act_f32_dev((int)act, dst.unsafe_raw_data(), dst.strides.data(), src.unsafe_raw_data(), ss.data(), dst.shape.data(),
+                              dst.rank(), stream));
+}
+inline Tensor<float> activation(const Tensor<float> &src, Activation act, void *stream = nullptr) {
+  Tensor<float> dst = exp_result_like(src);
+  activation(dst, src, act, stream);
+  return dst;
+}
+inline void tanh(Tensor<float> &dst, const Tensor<float> &src, void *stream = nullptr) { activation(dst, src, Activation::tanh, stream); }
+inline Tensor<float> tanh(const Tensor<float> &src, void *stream = nullptr) { return activation(src, Activation::tanh, stream); }
+inline void sigmoid(Tensor<float> &dst, const Tensor<float> &src, void *stream = nullptr) { activation(dst, src, Activation::sigmoid, stream); }
+inline Tensor<float> sigmoid(const Tensor<float> &src, void *stream = nullptr) { return activation(src, Activation::sigmoid, stream); }
+inline void activation_grad(Tensor<float> &dx, const Tensor<float> &dy, const Tensor<float> &y, Activation act, void *stream = nullptr) {
+  const std::vector<int64_t> gs = detail::bcast_strides("activation_grad", dx, dy), ys = detail::bcast_strides("activation_grad", dx, y);
+  check(laser_hip_act_grad_f32_dev((int)act, dx.unsafe_raw_data(), dx.strides.data(), dy.unsafe_raw_data(), gs.data(), y.unsafe_raw_data(),
+                                   ys.data(), dx.shape.data(), dx.rank(), stream));
+}
+inline Tensor<float> activation_grad(const Tensor<float> &dy, const Tensor<float> &y, Activation act, void *stream = nullptr) {
+  Tensor<float> dx = exp_result_like(y);
+  activation_grad(dx, dy, y, act, stream);
+  return dx;
+}
+
 // ---- Random numbers (include/laser_hip.h "Random numbers"): Philox4x32-10 streams and the reference's randomTensor ----------
 //   laser::Rng rng(seed, subseq);               names a stream; (seed, subseq, offset) live on the host, nothing on the device
 //   laser::randomTensor<T>({2, 3}, lo, hi, rng) uniform on the closed interval [lo, hi], T = float, double, int32_t, int64_t:

@@ -733,6 +733,74 @@ int laser_hip_softmax_xent_rows_f32_dev(float *d_loss, int64_t loss_stride, floa
                                         int64_t rows, int64_t n, float scale, void *stream);
 int laser_hip_softmax_rows_plan(int64_t rows, int64_t n, int vec, int64_t *out3);
 
+/* ---- Activations (f32): relu, tanh and sigmoid on a tensor, forward and backward, defined bit by bit ----------------------
+ * The reference's README lists optimised tanh and sigmoid beside exp and log, and the derivatives of relu, tanh and sigmoid
+ * for backward propagation.  ltanh and lsigmoid are defined the way lexp and llog are: one definition,
+ * laser_amd/csrc/act_core.h, shared by the kernels below and by the forEach bodies, built from integer operations, bit
+ * casts, one exact float32 -> float64 conversion, float64 + - x / each rounded on its own (no fused multiply-add in the
+ * polynomial parts, no libm, no device transcendental instruction), exactly one float64 division per result (IEEE
+ * correctly rounded) and one float64 -> float32 rounding to nearest even.
+ * Constants (float64): INV = float64(64 / ln 2); HI = float64(ln 2 / 64) with its low 24 significand bits cleared (k * HI is
+ *   exact); LO = float64(ln 2 / 64 - HI); T[j] = the correctly rounded float64 of 2^(j/64), j = 0..63; C2..C5 = float64(1/2,
+ *   1/6, 1/24, 1/120); D3, D5, D7 = float64(-1/3, 2/15, -17/315); R = 1.5 x 2^52.
+ * E(a) for a float64 a in [-208, 0]:
+ *   1. kf = (a * INV + R) - R: a * INV rounded to the nearest integer, ties to even, by two additions; k = int(kf).
+ *   2. r = (a - kf * HI) - kf * LO.
+ *   3. q = ((C5 r + C4) r + C3) r + C2.
+ *   4. p = r + (r * r) * q.
+ *   5. e = T[k & 63] + T[k & 63] * p.
+ *   6. E = e * bitcast<float64>(uint64((k >> 6) + 1023) << 52): an exact multiply by 2^(k >> 6) (arithmetic shift), never
+ *      subnormal in float64.
+ * lsigmoid(x) for a float32 x:
+ *   1. NaN gives NaN (payload unspecified).
+ *   2. c = min(float64(|x|), 104); +-Inf clamp like any other value.  e = E(-c), d = 1 + e.
+ *   3. Sign bit clear (+0 too): float32(1 / d).  Sign bit set (-0 too): float32(e / d).
+ *   lsigmoid(+-0) = 0.5.  For x in about [-103.97, -87.34] the result is a float32 subnormal, rounded once from the float64
+ *   quotient; no denormal is flushed.
+ * ltanh(x) for a float32 x:
+ *   1. NaN gives NaN (payload unspecified).
+ *   2. a = min(float64(|x|), 10).
+ *   3. a < 2^-6: s = a * a, q = ((D7 s + D5) s + D3) s, y = a + a * q.  Otherwise: e = E(-2 a), y = (1 - e) / (1 + e).
+ *   4. ltanh(x) = float32(y) with x's sign bit ORed into its bits: ltanh(-x) has the bits of -ltanh(x), ltanh(-0) = -0,
+ *      ltanh(+-Inf) = +-1, ltanh(x) = x for subnormal and tiny x.
+ * Properties, checked over every finite float32 on the CPU against tanhl / expl in 80-bit long double
+ * (tests/cpp/act_core_host.cpp "sweep"; profiles/activation/README.md has the output):
+ *   faithful: the result is one of the two float32 that bracket the true value, at every input (ltanh: the correctly rounded
+ *     float32 at every input, maximum error 0.500000 ulp; lsigmoid: maximum 0.500000 ulp, 73 of 4278190080 results are the
+ *     other neighbour of the true value instead of the nearest);
+ *   monotone: non-decreasing over all finite float32 in increasing order;
+ *   odd: ltanh(-x) has the bits of -ltanh(x);
+ *   bounded: |ltanh| <= 1, 0 <= lsigmoid <= 1, lsigmoid(+-0) = 0.5; ltanh is 1 from bits 0x41102cb4 (9.010914), lsigmoid is 1
+ *     from bits 0x418aa123 (17.32868) and 0 from bits 0xc2cff1b5 (-103.972084): where the true functions round to them.
+ * The rules by `act`; the gradients take the forward OUTPUT y, and their float32 operations are rounded one by one, never
+ * fused:
+ *   LASER_HIP_ACT_RELU     y = x > 0 ? x : +0 (NaN and -0 give +0)     dx = y > 0 ? dy : +0
+ *   LASER_HIP_ACT_TANH     y = ltanh(x)                                 t = y * y;  u = 1 - t;  dx = dy * u
+ *   LASER_HIP_ACT_SIGMOID  y = lsigmoid(x)                              u = 1 - y;  v = y * u;  dx = dy * v
+ *   Any other `act`, LASER_HIP_ACT_NONE and the PRE_ bits included, gives LASER_HIP_E_INVALID.
+ * The fused GEMM and conv epilogue (the `act` of the _ex entry points) is a different code path: its relu is this same rule,
+ *   so matmul(.., relu) has the bits of act(matmul(..), relu); its tanh and sigmoid stay the device math library's tanhf and
+ *   1 / (1 + expf(-x)), whose bits nothing defines and which may differ from ltanh and lsigmoid in the last bit.
+ * laser_hip_act_f32_dev: dst[idx] = act(src[idx]) for every index of `shape`; the contract of laser_hip_exp_f32_dev: rank
+ *   <= 6, ELEMENT strides, negative strides allowed, stride 0 (broadcast) on src only, dst == src with equal strides allowed
+ *   (any other overlap is not), a zero-size shape does nothing, any base alignment.  Asynchronous on `stream`.  C-contiguous
+ *   and 16-byte aligned on both sides: one 16-byte vector per lane and step.
+ * laser_hip_act_f32: host pointers, `len` contiguous elements, synchronous.
+ * laser_hip_act_grad_f32_dev: dx[idx] = the gradient rule above of (dy[idx], y[idx]); the same contract with two inputs:
+ *   stride 0 on dy and y only, dx may equal dy or y (or both) with equal strides.
+ * laser_tanh(x) and laser_sigmoid(x) are callable in forEach / forEachReduce bodies: the prelude embeds act_core.h after
+ *   log_core.h.  The names are reserved like laser_log.
+ * Not built: these rules as new codes of the GEMM / conv epilogue (the float64 bodies would land in every fused-epilogue
+ *   instantiation, their register and code-size cost there is unmeasured; profiles/activation/README.md has the per-element
+ *   figures that decision needs); float64; softplus, log-sigmoid, binary cross-entropy, GELU and SiLU (the last two are
+ *   one-line forEach bodies over the two names); bias gradients and any reduction along an axis.
+ * No gfx950 device: LASER_HIP_E_NODEVICE. */
+int laser_hip_act_f32_dev(int act, float *d_dst, const int64_t *dst_strides, const float *d_src, const int64_t *src_strides,
+                          const int64_t *shape, int rank, void *stream);
+int laser_hip_act_f32(int act, float *dst, const float *src, int64_t len);
+int laser_hip_act_grad_f32_dev(int act, float *d_dx, const int64_t *dx_strides, const float *d_dy, const int64_t *dy_strides,
+                               const float *d_y, const int64_t *y_strides, const int64_t *shape, int rank, void *stream);
+
 /* ---- F+tree weighted sampler (f32): benchmarks/random_sampling/fenwicktree.nim, bench_multinomial_samplers.nim --------
  * The reference's `Sampler` over device rows: from a row of weights (the softmax above, or anything non-negative) to drawn
  * indices without leaving the device.  All float32, every operation rounded to float32 on its own, no denormal flushed.

@@ -140,6 +140,9 @@ def lib():
     L.laser_hip_log_softmax_rows_f32_dev.argtypes = [vp, i64, vp, i64, i64, i64, vp]
     L.laser_hip_softmax_xent_rows_f32_dev.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, C.c_float, vp]
     L.laser_hip_softmax_rows_plan.argtypes = [i64, i64, ci, pi]
+    L.laser_hip_act_f32_dev.argtypes = [ci, vp, pi, vp, pi, pi, ci, vp]
+    L.laser_hip_act_f32.argtypes = [ci, vp, vp, i64]
+    L.laser_hip_act_grad_f32_dev.argtypes = [ci, vp, pi, vp, pi, vp, pi, pi, ci, vp]
     L.laser_hip_sampler_tree_elems.argtypes = [i64, pi]
     L.laser_hip_sampler_plan.argtypes = [i64, i64, pi]
     L.laser_hip_sampler_build_f32_dev.argtypes = [vp, i64, vp, i64, i64, i64, vp]
@@ -201,6 +204,7 @@ def declared_symbols():
              "laser_hip_softmax_axis_f32_dev", "laser_hip_softmax_axis_plan",
              "laser_hip_log_f32_dev", "laser_hip_log_f32", "laser_hip_logsumexp_rows_f32_dev",
              "laser_hip_log_softmax_rows_f32_dev", "laser_hip_softmax_xent_rows_f32_dev", "laser_hip_softmax_rows_plan",
+             "laser_hip_act_f32_dev", "laser_hip_act_f32", "laser_hip_act_grad_f32_dev",
              "laser_hip_sampler_tree_elems", "laser_hip_sampler_plan", "laser_hip_sampler_build_f32_dev",
              "laser_hip_sampler_sample_f32_dev", "laser_hip_sampler_sample_remove_f32_dev", "laser_hip_sampler_update_f32_dev",
              "laser_hip_sampler_sample_rng_f32_dev", "laser_hip_sampler_sample_remove_rng_f32_dev",

@@ -1468,6 +1468,61 @@ int laser_hip_log_f32(float *dst, const float *src, int64_t len) {
   HIP_TRY(hipMemcpy(dst, d_buf, (size_t)len * sizeof(float), hipMemcpyDeviceToHost));
   return LASER_HIP_OK;
 }
+// ---- relu, ltanh, lsigmoid and their gradients from the output (act_core.h, activation.hip) -----------------------------------
+static int act_check(const char *what, int act, int nin, const int64_t *const *strides, const int64_t *shape, int rank, int64_t *total) {
+  if (act != LASER_HIP_ACT_RELU && act != LASER_HIP_ACT_TANH && act != LASER_HIP_ACT_SIGMOID)
+    return fail(LASER_HIP_E_INVALID, "%s: act %d is not LASER_HIP_ACT_RELU, _TANH or _SIGMOID", what, act);
+  if (rank < 0 || rank > kMaxRank) return fail(LASER_HIP_E_INVALID, "%s: rank %d outside 0..%d (LASER_MAXRANK)", what, rank, kMaxRank);
+  if (rank > 0 && !shape) return fail(LASER_HIP_E_INVALID, "%s: null shape / strides", what);
+  for (int i = 0; i <= nin && rank > 0; i++)
+    if (!strides[i]) return fail(LASER_HIP_E_INVALID, "%s: null shape / strides", what);
+  *total = 1;
+  for (int d = 0; d < rank; d++) {
+    if (shape[d] < 0) return fail(LASER_HIP_E_INVALID, "%s: negative extent", what);
+    if (shape[d] > 1 && strides[0][d] == 0) return fail(LASER_HIP_E_INVALID, "%s: stride 0 on the destination (dimension %d)", what, d);
+    *total *= shape[d];
+  }
+  return LASER_HIP_OK;
+}
+int laser_hip_act_f32_dev(int act, float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
+                          void *stream) {
+  const int64_t *st[2] = {ds, ss};
+  int64_t total;
+  if (int rc = act_check("act", act, 1, st, shape, rank, &total)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (total == 0) return LASER_HIP_OK;
+  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "act: null buffer");
+  HIP_TRY(launch_act_f32(act, dst, ds, src, ss, shape, rank, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+// the host-pointer form: through device scratch, in place there, synchronous; the same kernel as the _dev form
+int laser_hip_act_f32(int act, float *dst, const float *src, int64_t len) {
+  if (act != LASER_HIP_ACT_RELU && act != LASER_HIP_ACT_TANH && act != LASER_HIP_ACT_SIGMOID)
+    return fail(LASER_HIP_E_INVALID, "act: act %d is not LASER_HIP_ACT_RELU, _TANH or _SIGMOID", act);
+  if (len < 0 || (len > 0 && (!dst || !src))) return fail(LASER_HIP_E_INVALID, "act: bad argument");
+  if (int rc = ensure_init()) return rc;
+  if (len == 0) return LASER_HIP_OK;
+  HostCall hc;
+  if (hc.rc) return hc.rc;
+  void *d_buf;
+  if (int rc = scratch_get(0, (size_t)len * sizeof(float), &d_buf)) return rc;
+  HIP_TRY(hipMemcpy(d_buf, src, (size_t)len * sizeof(float), hipMemcpyHostToDevice));
+  const int64_t stride = 1;
+  HIP_TRY(launch_act_f32(act, (float *)d_buf, &stride, (const float *)d_buf, &stride, &len, 1, nullptr));
+  HIP_TRY(hipMemcpy(dst, d_buf, (size_t)len * sizeof(float), hipMemcpyDeviceToHost));
+  return LASER_HIP_OK;
+}
+int laser_hip_act_grad_f32_dev(int act, float *dx, const int64_t *dxs, const float *dy, const int64_t *dys, const float *y,
+                               const int64_t *ys, const int64_t *shape, int rank, void *stream) {
+  const int64_t *st[3] = {dxs, dys, ys};
+  int64_t total;
+  if (int rc = act_check("act_grad", act, 2, st, shape, rank, &total)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (total == 0) return LASER_HIP_OK;
+  if (!dx || !dy || !y) return fail(LASER_HIP_E_INVALID, "act_grad: null buffer");
+  HIP_TRY(launch_act_grad_f32(act, dx, dxs, dy, dys, y, ys, shape, rank, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
 // the checks the three row entry points share, in the order of the softmax entry point
 static int rows_check(const char *what, int64_t src_row_stride, int64_t rows, int64_t n) {
   if (n < 1 || n > LASER_HIP_SOFTMAX_MAX_N) return fail(LASER_HIP_E_INVALID, "%s: row length %lld outside 1..2^26", what, (long long)n);

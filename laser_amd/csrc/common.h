@@ -245,6 +245,12 @@ hipError_t launch_log_softmax_rows_f32(float *dst, int64_t dstride, const float 
                                        hipStream_t s);
 hipError_t launch_softmax_xent_rows_f32(float *loss, int64_t loss_stride, float *grad, int64_t grad_stride, const float *src,
                                         int64_t sstride, const int32_t *labels, int64_t rows, int64_t n, float scale, hipStream_t s);
+// relu, ltanh and lsigmoid over strided views and their gradients from the forward output (activation.hip; act_core.h is the
+// definition of ltanh and lsigmoid); act is LASER_HIP_ACT_RELU / TANH / SIGMOID, anything else hipErrorInvalidValue
+hipError_t launch_act_f32(int act, float *dst, const int64_t *dstrides, const float *src, const int64_t *sstrides, const int64_t *shape,
+                          int rank, hipStream_t s);
+hipError_t launch_act_grad_f32(int act, float *dx, const int64_t *dxstrides, const float *dy, const int64_t *dystrides, const float *y,
+                               const int64_t *ystrides, const int64_t *shape, int rank, hipStream_t s);
 // the F+tree weighted sampler (sampler.hip; sampler_plan.h picks the build kernel): tree images of 2 P elements per row
 hipError_t launch_sampler_build_f32(float *tree, int64_t tree_row_stride, const float *w, int64_t w_row_stride, int64_t rows, int64_t n,
                                     hipStream_t s);

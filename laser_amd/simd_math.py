@@ -1,6 +1,6 @@
 """Laser's table-driven exp and the row softmax on top of it (laser/primitives/simd_math/exp_log_*.nim; include/laser_hip.h
-"exp and row softmax"), and the way from logits to a loss (include/laser_hip.h "log, logsumexp, log-softmax and
-cross-entropy"), float32:
+"exp and row softmax"), the way from logits to a loss (include/laser_hip.h "log, logsumexp, log-softmax and
+cross-entropy") and the activations with their gradients (include/laser_hip.h "Activations"), float32:
 
     laser_amd.exp(t)        lexp of every element: the exported SIMD `exp*` of the reference, bit for bit
     laser_amd.softmax(t)    softmax over the rows of a 2-D tensor, summed in the fixed order of the reductions
@@ -11,11 +11,17 @@ cross-entropy"), float32:
     laser_amd.log_softmax(t)       (x - max) - llog(sum) over the rows of a 2-D tensor
     laser_amd.softmax_cross_entropy(logits, labels, grad=False, scale=1.0)   the per-row loss for int32 labels (-1: ignore),
                             and with grad=True also (softmax - onehot) * scale
+    laser_amd.tanh(t)       ltanh of every element: the bit-defined tanh of laser_amd/csrc/act_core.h
+    laser_amd.sigmoid(t)    lsigmoid of every element: the bit-defined logistic function of the same header
+    laser_amd.activation(t, kind, out=None)          kind "relu", "tanh" or "sigmoid": relu is x > 0 ? x : +0
+    laser_amd.activation_grad(dy, y, kind, out=None)   the gradient from the forward OUTPUT y: relu y > 0 ? dy : +0,
+                            tanh dy * (1 - y * y), sigmoid dy * (y * (1 - y)), every float32 operation rounded on its own
 
 An operand is a laser_amd.Tensor or a torch CUDA tensor (anything with __cuda_array_interface__); `exp` also takes a host
 float32 numpy array, like the reference's benchmark loop.  With out=None a device call returns a fresh row-major Tensor;
 with `out` it writes there (out may be the input) and returns it.  Device calls are asynchronous on the current torch
-stream.  Inside forEach / forEachReduce bodies the same functions are `laser_exp(x)` and `laser_log(x)`.
+stream.  Inside forEach / forEachReduce bodies the same functions are `laser_exp(x)`, `laser_log(x)`, `laser_tanh(x)` and
+`laser_sigmoid(x)`.
 """
 import ctypes as C
 
@@ -33,7 +39,8 @@ def _f32(name, obj):
     return v
 
 
-def _elementwise(fn, t, out):
+def _elementwise(fn, t, out, lead=()):
+    """`lead`: arguments of the entry point before its operands (the activation code)"""
     if isinstance(t, np.ndarray):   # the host-pointer form: contiguous float32, synchronous
         if t.dtype != np.float32:
             raise TypeError(f"host arrays: float32 only (got {t.dtype})")
@@ -41,7 +48,7 @@ def _elementwise(fn, t, out):
             raise TypeError("out= is for device inputs; a host array returns its result")
         a = np.ascontiguousarray(t)
         r = np.empty_like(a)
-        _lib.check(getattr(_lib.lib(), f"laser_hip_{fn}_f32")(r.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), a.size))
+        _lib.check(getattr(_lib.lib(), f"laser_hip_{fn}_f32")(*lead, r.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), a.size))
         return r
     src = _f32("t", t)
     if out is None:
@@ -49,7 +56,7 @@ def _elementwise(fn, t, out):
     dst = _f32("out", out)
     r = dst.rank
     arr = lambda v: (C.c_int64 * max(r, 1))(*v)
-    _lib.check(getattr(_lib.lib(), f"laser_hip_{fn}_f32_dev")(C.c_void_p(dst.ptr), arr(dst.strides), C.c_void_p(src.ptr),
+    _lib.check(getattr(_lib.lib(), f"laser_hip_{fn}_f32_dev")(*lead, C.c_void_p(dst.ptr), arr(dst.strides), C.c_void_p(src.ptr),
                                                               arr(_bcast_strides(src, dst.shape)), arr(dst.shape), r, _stream()))
     return out
 
@@ -64,6 +71,51 @@ def log(t, out=None):
     over every positive float32; +-0 gives -Inf, a negative value NaN, a subnormal is taken as the number it is.  Operands
     as `exp`: a device tensor (`t` broadcasts against `out`) or a host float32 array."""
     return _elementwise("log", t, out)
+
+
+_ACT_CODES = {"relu": 1, "tanh": 2, "sigmoid": 3}      # LASER_HIP_ACT_RELU / _TANH / _SIGMOID
+
+
+def _act_code(kind):
+    if kind not in _ACT_CODES:
+        raise ValueError(f"activation: kind {kind!r} (one of {sorted(_ACT_CODES)})")
+    return _ACT_CODES[kind]
+
+
+def activation(t, kind, out=None):
+    """relu, ltanh or lsigmoid of every element (kind "relu", "tanh", "sigmoid").  relu is x > 0 ? x : +0, the rule of the
+    fused GEMM / conv epilogue (NaN and -0 give +0); ltanh and lsigmoid are laser_amd/csrc/act_core.h's: faithful, monotone,
+    ltanh odd bit for bit, lsigmoid(0) = 0.5.  Operands as `exp`: a device tensor or view (`t` broadcasts against `out`, `out`
+    may be `t`) or a host float32 array."""
+    return _elementwise("act", t, out, (_act_code(kind),))
+
+
+def tanh(t, out=None):
+    """ltanh(t), elementwise: activation(t, "tanh")"""
+    return activation(t, "tanh", out)
+
+
+def sigmoid(t, out=None):
+    """lsigmoid(t), elementwise: activation(t, "sigmoid")"""
+    return activation(t, "sigmoid", out)
+
+
+def activation_grad(dy, y, kind, out=None):
+    """The gradient of activation(x, kind) from the incoming gradient `dy` and the forward OUTPUT `y`: relu y > 0 ? dy : +0,
+    tanh t = y * y, u = 1 - t, dy * u; sigmoid u = 1 - y, v = y * u, dy * v -- float32 operations rounded one by one.  `dy`
+    and `y` are device tensors or views and broadcast against `out`; out=None: a fresh Tensor of their broadcast shape; `out`
+    may be `dy` or `y`."""
+    code = _act_code(kind)
+    g, o = _f32("dy", dy), _f32("y", y)
+    if out is None:
+        out = newTensor(np.float32, *np.broadcast_shapes(g.shape, o.shape))
+    dst = _f32("out", out)
+    r = dst.rank
+    arr = lambda v: (C.c_int64 * max(r, 1))(*v)
+    _lib.check(_lib.lib().laser_hip_act_grad_f32_dev(code, C.c_void_p(dst.ptr), arr(dst.strides), C.c_void_p(g.ptr),
+                                                     arr(_bcast_strides(g, dst.shape)), C.c_void_p(o.ptr),
+                                                     arr(_bcast_strides(o, dst.shape)), arr(dst.shape), r, _stream()))
+    return out
 
 
 def _collapse(dims):

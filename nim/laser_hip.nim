@@ -684,6 +684,34 @@ proc softmaxCrossEntropy*(loss: DevicePtr[float32], lossStride: int, grad: Devic
   ## loss or grad may be nil (not both); label -1 is ignored, any other label outside 0 ..< n gives NaN
   check laser_hip_softmax_xent_rows_f32_dev(cast[ptr float32](loss), int64(lossStride), cast[ptr float32](grad), int64(gradRowStride), cast[ptr float32](src), int64(srcRowStride), cast[ptr int32](labels), int64(rows), int64(n), scale, stream)
 
+# ---- activations (include/laser_hip.h "Activations"): relu, tanh, sigmoid and their gradients from the output -----------
+# tanh and sigmoid are ltanh and lsigmoid of act_core.h: faithful, monotone, tanh odd bit for bit, sigmoid(0) = 0.5; relu is the
+# fused epilogue's rule (x > 0 ? x : +0).  `Activation` is the enum of the fused epilogue; actNone is not accepted here.
+proc laser_hip_act_f32(act: cint, dst: ptr float32, src: ptr float32, len: int64): cint {.lh, importc: "laser_hip_act_f32".}
+proc laser_hip_act_f32_dev*(act: cint, dst: ptr float32, dstStrides: ptr int64, src: ptr float32, srcStrides: ptr int64, shape: ptr int64, rank: cint, stream: pointer): cint {.lh, importc: "laser_hip_act_f32_dev".}
+proc laser_hip_act_grad_f32_dev*(act: cint, dx: ptr float32, dxStrides: ptr int64, dy: ptr float32, dyStrides: ptr int64, y: ptr float32, yStrides: ptr int64, shape: ptr int64, rank: cint, stream: pointer): cint {.lh, importc: "laser_hip_act_grad_f32_dev".}
+
+proc tanh*(dst, src: ptr (float32 or UncheckedArray[float32]), len: Natural) =
+  ## dst[i] = tanh(src[i]) over a contiguous range of float32 (host memory; the GPU computes it)
+  check laser_hip_act_f32(cint(ord(actTanh)), cast[ptr float32](dst), cast[ptr float32](src), int64(len))
+
+proc sigmoid*(dst, src: ptr (float32 or UncheckedArray[float32]), len: Natural) =
+  ## dst[i] = 1 / (1 + exp(-src[i])) over a contiguous range of float32 (host memory; the GPU computes it)
+  check laser_hip_act_f32(cint(ord(actSigmoid)), cast[ptr float32](dst), cast[ptr float32](src), int64(len))
+
+proc activation*(kind: Activation, dst, src: DevicePtr[float32], len: Natural, stream: pointer = nil) =
+  ## dst[i] = kind(src[i]) over `len` contiguous device elements; dst may be src
+  var stride = 1'i64
+  var n = int64(len)
+  check laser_hip_act_f32_dev(cint(ord(kind)), cast[ptr float32](dst), stride.addr, cast[ptr float32](src), stride.addr, n.addr, 1, stream)
+
+proc activationGrad*(kind: Activation, dx, dy, y: DevicePtr[float32], len: Natural, stream: pointer = nil) =
+  ## the gradient of `kind` from dy and the forward OUTPUT y over `len` contiguous device elements: relu y > 0 ? dy : 0,
+  ## tanh dy * (1 - y * y), sigmoid dy * (y * (1 - y)), each float32 operation rounded on its own; dx may be dy or y
+  var stride = 1'i64
+  var n = int64(len)
+  check laser_hip_act_grad_f32_dev(cint(ord(kind)), cast[ptr float32](dx), stride.addr, cast[ptr float32](dy), stride.addr, cast[ptr float32](y), stride.addr, n.addr, 1, stream)
+
 # ---- F+tree weighted sampler (include/laser_hip.h "F+tree weighted sampler"): fenwicktree.nim over HipStorage -----------
 # One tree image of 2 P float32 per row (P = the next power of two >= n; the reference's array shifted up by one slot).  The
 # uniform numbers are the caller's, or come from a HipRng stream ("Random numbers" below): the overloads taking `rng`.
