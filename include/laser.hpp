@@ -12,6 +12,7 @@
 #include <vector>
 #include <string>
 #include <type_traits>
+#include <utility>
 
 #include "laser_hip.h"
 
@@ -692,6 +693,40 @@ inline Tensor<float> activation_grad(const Tensor<float> &dy, const Tensor<float
   return dx;
 }
 
+// ---- sine and cosine (include/laser_hip.h "Sine and cosine") over device Tensors -----------------------------------------------
+//   laser::sin(y, x);  laser::cos(y, x);  laser::sincos(s, c, x);   y = laser::sin(x);              (asynchronous on `stream`)
+// lsin and lcos of sincos_core.h: faithful for every finite float32, lsin odd and lcos even bit for bit, NaN for NaN and +-Inf.
+// x broadcasts against the destination, which may be x itself; sincos shares one argument reduction and gives the same bits.
+inline void sin(Tensor<float> &dst, const Tensor<float> &src, void *stream = nullptr) {
+  const std::vector<int64_t> ss = detail::bcast_strides("sin", dst, src);
+  check(laser_hip_sin_f32_dev(dst.unsafe_raw_data(), dst.strides.data(), src.unsafe_raw_data(), ss.data(), dst.shape.data(), dst.rank(), stream));
+}
+inline Tensor<float> sin(const Tensor<float> &src, void *stream = nullptr) {
+  Tensor<float> dst = exp_result_like(src);
+  sin(dst, src, stream);
+  return dst;
+}
+inline void cos(Tensor<float> &dst, const Tensor<float> &src, void *stream = nullptr) {
+  const std::vector<int64_t> ss = detail::bcast_strides("cos", dst, src);
+  check(laser_hip_cos_f32_dev(dst.unsafe_raw_data(), dst.strides.data(), src.unsafe_raw_data(), ss.data(), dst.shape.data(), dst.rank(), stream));
+}
+inline Tensor<float> cos(const Tensor<float> &src, void *stream = nullptr) {
+  Tensor<float> dst = exp_result_like(src);
+  cos(dst, src, stream);
+  return dst;
+}
+inline void sincos(Tensor<float> &s, Tensor<float> &c, const Tensor<float> &src, void *stream = nullptr) {
+  if (s.shape != c.shape) throw Error(LASER_HIP_E_INVALID, "sincos: the two destinations differ in shape");
+  const std::vector<int64_t> ss = detail::bcast_strides("sincos", s, src);
+  check(laser_hip_sincos_f32_dev(s.unsafe_raw_data(), s.strides.data(), c.unsafe_raw_data(), c.strides.data(), src.unsafe_raw_data(),
+                                 ss.data(), s.shape.data(), s.rank(), stream));
+}
+inline std::pair<Tensor<float>, Tensor<float>> sincos(const Tensor<float> &src, void *stream = nullptr) {
+  Tensor<float> s = exp_result_like(src), c = exp_result_like(src);
+  sincos(s, c, src, stream);
+  return {std::move(s), std::move(c)};
+}
+
 // ---- Random numbers (include/laser_hip.h "Random numbers"): Philox4x32-10 streams and the reference's randomTensor ----------
 //   laser::Rng rng(seed, subseq);               names a stream; (seed, subseq, offset) live on the host, nothing on the device
 //   laser::randomTensor<T>({2, 3}, lo, hi, rng) uniform on the closed interval [lo, hi], T = float, double, int32_t, int64_t:
@@ -699,6 +734,8 @@ inline Tensor<float> activation_grad(const Tensor<float> &dy, const Tensor<float
 //                                               the 64-bit types); the rng advances by the words used
 //   laser::randomTensor<T>({2, 3}, max, rng)    [0, max], the reference's second form
 //   laser::randomBits(n, rng)                   n raw words as a Tensor<int32_t> holding the bits
+//   rng.randomNormalTensor({2, 3}, mean, std)   float normal draws (Box-Muller on pairs of words, normal_core.h): element k from
+//   laser::randomNormalTensor({2, 3}, mean, std, rng)       stream position rng.offset + k; the rng advances by the element count
 // A result is a function of (seed, subseq, offset) and the arguments alone.  Asynchronous on `stream`.
 struct Rng {
   uint64_t seed = 0, subseq = 0, offset = 0;
@@ -708,7 +745,17 @@ struct Rng {
     offset += words;
     return before;
   }
+  Tensor<float> randomNormalTensor(std::initializer_list<int64_t> shape, float mean = 0.0f, float std = 1.0f, void *stream = nullptr) {
+    Tensor<float> t = newTensor<float>(shape);
+    const int64_t n = t.size();
+    check(laser_hip_random_normal_f32_dev(t.unsafe_raw_data(), n, mean, std, (int64_t)seed, (int64_t)subseq, (int64_t)offset, stream));
+    advance((uint64_t)n);
+    return t;
+  }
 };
+inline Tensor<float> randomNormalTensor(std::initializer_list<int64_t> shape, float mean, float std, Rng &rng, void *stream = nullptr) {
+  return rng.randomNormalTensor(shape, mean, std, stream);
+}
 template <typename T>
 Tensor<T> randomTensor(std::initializer_list<int64_t> shape, T lo, T hi, Rng &rng, void *stream = nullptr) {
   static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value || std::is_same<T, int32_t>::value ||

@@ -801,6 +801,52 @@ int laser_hip_act_f32(int act, float *dst, const float *src, int64_t len);
 int laser_hip_act_grad_f32_dev(int act, float *d_dx, const int64_t *dx_strides, const float *d_dy, const int64_t *dy_strides,
                                const float *d_y, const int64_t *y_strides, const int64_t *shape, int rank, void *stream);
 
+/* ---- Sine and cosine (f32): lsin and lcos, defined bit by bit ------------------------------------------------------------
+ * The reference's forEach material uses exactly these two (`o = x + y - sin z` in benchmarks/loop_iteration/iter_bench.nim,
+ * `sin(s) + cos(s)` in examples/ex02 and ex03); through the device library's sinf their bits are nobody's.  lsin and lcos are
+ * one definition, laser_amd/csrc/sincos_core.h, for the host, these kernels, the normal random fill below and forEach bodies;
+ * tests/sincos_model.py is the numpy model and scripts/gen_sincos_constants.py makes the constants from integer arithmetic.
+ * Inside: integer operations, bit casts, one exact float32 -> float64 conversion, float64 + - x each rounded on its own (no
+ * fused multiply-add, no division, no library call) and one rounding to float32.  Reduction to a quadrant and an argument in
+ * about [-pi/4, pi/4]: below 2^20 with pi/2 in three parts (24 + 24 + 53 bits; the first two products and subtractions are
+ * exact), from 2^20 on by Payne-Hanek in integers on a 128-bit window of the bits of 2/pi (a 288-bit table; at least 43 guard
+ * bits below the 53 that are kept).  Then a sine kernel (odd series to r^15) or a cosine kernel (even series to r^16), chosen
+ * and signed by the quadrant.
+ * The contract, for every float32 x:
+ *   Faithful      the result is one of the two float32 that bracket the true value: the error is below one ulp for every
+ *                 finite input, however large.
+ *   Symmetry      lsin(-x) has the bits of -lsin(x); lcos(-x) has the bits of lcos(x).
+ *   Zeros, tiny   lsin(+-0) = +-0, lcos(+-0) = 1.  lsin(x) = x exactly and lcos(x) = 1 wherever the true result rounds to that
+ *                 (lsin: every |x| up to bits 0x39e89768, lcos: up to 2^-12, and beyond where rounding says so); this
+ *                 includes every subnormal, and nothing is flushed.
+ *   Range         |result| <= 1 always.
+ *   Monotonicity  over the float32 values in [0, pi/2] lsin is non-decreasing and lcos non-increasing.
+ *   Specials      +-Inf and NaN give the NaN with bits 0x7fc00000 (whatever the input's sign and payload).
+ *   All of it is measured over every finite float32 against 80-bit sinl / cosl (profiles/sincos/README.md): maximum error 0.5
+ *   ulp, and 2 (lsin) and 8 (lcos) of the 4278190080 results are not the nearest float32.
+ * laser_hip_sin_f32_dev / laser_hip_cos_f32_dev: dst[idx] = lsin(src[idx]) / lcos(src[idx]) for every index of `shape`; the
+ *   contract of laser_hip_act_f32_dev: rank <= 6, ELEMENT strides, negative strides allowed, stride 0 (broadcast) on src only,
+ *   dst == src with equal strides allowed (any other overlap is not), a zero-size shape does nothing, any base alignment.
+ *   Asynchronous on `stream`.  C-contiguous and 16-byte aligned on both sides: one 16-byte vector per lane and step.
+ * laser_hip_sincos_f32_dev: both from one argument reduction, with the bits of the two calls above; either destination may be
+ *   src (equal strides), the two destinations must not overlap each other (the same base pointer is LASER_HIP_E_INVALID).
+ * laser_hip_sin_f32 / laser_hip_cos_f32: host pointers, `len` contiguous elements, synchronous.
+ * LASER_HIP_E_INVALID as for the activations: rank outside 0 .. 6, null shape / strides, a negative extent, stride 0 on a
+ *   destination; then the device is looked for (LASER_HIP_E_NODEVICE without a gfx950); then a zero-size shape does nothing;
+ *   then a null buffer is LASER_HIP_E_INVALID.
+ * laser_sin(x) and laser_cos(x) are callable in forEach / forEachReduce bodies (`o = x + y - laser_sin(z)`): the prelude
+ *   embeds sincos_core.h after act_core.h when the body or the merge names one of them, and only then, so other bodies
+ *   compile as fast as before.  The names are reserved like laser_log.
+ * Not built: float64 sin and cos, tan, sinpi / cospi, gradients, these as fused-epilogue codes. */
+int laser_hip_sin_f32_dev(float *d_dst, const int64_t *dst_strides, const float *d_src, const int64_t *src_strides,
+                          const int64_t *shape, int rank, void *stream);
+int laser_hip_cos_f32_dev(float *d_dst, const int64_t *dst_strides, const float *d_src, const int64_t *src_strides,
+                          const int64_t *shape, int rank, void *stream);
+int laser_hip_sincos_f32_dev(float *d_sin, const int64_t *sin_strides, float *d_cos, const int64_t *cos_strides,
+                             const float *d_src, const int64_t *src_strides, const int64_t *shape, int rank, void *stream);
+int laser_hip_sin_f32(float *dst, const float *src, int64_t len);
+int laser_hip_cos_f32(float *dst, const float *src, int64_t len);
+
 /* ---- F+tree weighted sampler (f32): benchmarks/random_sampling/fenwicktree.nim, bench_multinomial_samplers.nim --------
  * The reference's `Sampler` over device rows: from a row of weights (the softmax above, or anything non-negative) to drawn
  * indices without leaving the device.  All float32, every operation rounded to float32 on its own, no denormal flushed.
@@ -970,7 +1016,7 @@ int laser_hip_cdf_sample_remove_rng_f32_dev(int32_t *d_idx, float *d_w, int64_t 
                                             int64_t cdf_row_stride, int64_t seed, int64_t subseq, int64_t offset,
                                             int64_t rows, int64_t n, int64_t k, void *stream);
 
-/* ---- Random numbers: Philox4x32-10 and randomTensor's uniform fills -- the `randomTensor(shape, valrange)` and
+/* ---- Random numbers: Philox4x32-10, randomTensor's uniform fills and normal fills -- the `randomTensor(shape, valrange)` and
  * `randomTensor(shape, max)` that open the reference's benchmarks (bench_exp.nim:17, reduction_bench.nim:40, ...) ----------
  * A counter-based generator (Salmon, Moraes, Dror, Shaw, SC'11): word w of a stream is a function of (seed, subseq, w) and of
  * nothing else.  No state lives on the device; a call captured in a graph replays the same numbers; a result never depends on
@@ -1007,8 +1053,22 @@ int laser_hip_cdf_sample_remove_rng_f32_dev(int32_t *d_idx, float *d_w, int64_t 
  *   compute units); the most blocks one lane walks; the index of the first block, offset >> 2}.  words_per_elem: 1 for the 32-bit
  *   types, 2 for the 64-bit ones.  The fills plan for 256 compute units on every device.  The logic is
  *   laser_amd/csrc/random_plan.h, which has no HIP dependency.
- * Not built: normal and other non-uniform distributions (they need a bit-defined sincos beside llog first), the other six element
- *   types, strided destinations, a laser_rand callable in forEach bodies. */
+ * normal_f32: Box-Muller on the same streams, fixed so that a fill can be cut anywhere (laser_amd/csrc/normal_core.h;
+ *   tests/normal_model.py is the numpy model).  One word per element: element i is stream position p = offset + i, offsets count
+ *   elements as for the 32-bit uniform fills and the next call continues at offset + n.  Pair q = p >> 1 owns words w0 = word(2q)
+ *   and w1 = word(2q + 1); an even p is the pair's cosine branch, an odd p its sine branch, and a fill that starts or ends inside
+ *   a pair stores only its half.
+ *     radius  u = float((w0 >> 8) + 1) * 2^-24 in (0, 1];  L = llog(u);  r = sqrt(|-2 L|), a correctly rounded float32 square root
+ *             (u = 1 gives +0)
+ *     angle   k = w1 >> 8, the angle is 2 pi k / 2^24: reduced exactly on the integer to a quadrant and a fraction f in
+ *             [-2^21, 2^21), a = (float64(f) * 2^-22) * float64(pi/2) (one rounding), t = float32(lsin's / lcos' own float64 sine
+ *             or cosine kernel at a, chosen and signed by the quadrant)
+ *     result  z = r * t;  out = mean + std * z: three float32 roundings, never contracted.  |z| <= sqrt(48 ln 2) < 5.77, every
+ *             result is finite.  Valid: mean finite, std finite and >= 0 (checked where the uniform fills check their bounds).
+ *   The kernel is the uniform fills' and random_plan.h plans it with one word per element: with 16-byte stores a lane turns one
+ *   Philox block into two pairs, four results, the radius and the angle reduction shared inside each pair.
+ * Not built: float64 normals, other distributions, the other six element types, strided destinations, a laser_rand callable in
+ *   forEach bodies. */
 #define LASER_HIP_RANDOM_MAX_N (1ll << 60)
 int laser_hip_random_plan(int64_t n, int words_per_elem, int64_t offset, int dst_misaligned, int cus, int64_t *out4);
 int laser_hip_random_bits_u32_dev(uint32_t *d_dst, int64_t n, int64_t seed, int64_t subseq, int64_t offset, void *stream);
@@ -1020,6 +1080,8 @@ int laser_hip_random_uniform_i32_dev(int32_t *d_dst, int64_t n, int32_t lo, int3
                                      int64_t offset, void *stream);
 int laser_hip_random_uniform_i64_dev(int64_t *d_dst, int64_t n, int64_t lo, int64_t hi, int64_t seed, int64_t subseq,
                                      int64_t offset, void *stream);
+int laser_hip_random_normal_f32_dev(float *d_dst, int64_t n, float mean, float std, int64_t seed, int64_t subseq,
+                                    int64_t offset, void *stream);
 
 /* ---- forEachReduce: forEach with a private accumulator per lane, merged at the end ---------------------------------
  * The device form of forEachStaged (laser/strided_iteration/foreach_staged.nim:318), e.g. a dot product:

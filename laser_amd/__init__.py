@@ -12,8 +12,9 @@ from .foreach import forEach  # noqa: F401
 from .reduce import reduce_sum, reduce_min, reduce_max, forEachReduce  # noqa: F401
 from .simd_math import exp, softmax, log, logsumexp, log_softmax, softmax_cross_entropy  # noqa: F401
 from .simd_math import tanh, sigmoid, activation, activation_grad  # noqa: F401
+from .simd_math import sin, cos, sincos  # noqa: F401
 from .sampling import Sampler, newSampler, multinomial  # noqa: F401
-from .random import Rng, randomTensor  # noqa: F401
+from .random import Rng, randomTensor, randomNormalTensor  # noqa: F401
 from .scan import cumsum, searchsorted, cdfSample, cdfSampleAndRemove  # noqa: F401
 from .sharded import (shard_plan, set_shard_devices, get_shard_devices, gemm_strided_sharded, matmul_sharded,  # noqa: F401
                       gemm_strided_sharded_dev, shard_rows, GATHER_NONE, GATHER_PEER, GATHER_RCCL, SHARD_PIN_TILE)

@@ -143,6 +143,10 @@ def lib():
     L.laser_hip_act_f32_dev.argtypes = [ci, vp, pi, vp, pi, pi, ci, vp]
     L.laser_hip_act_f32.argtypes = [ci, vp, vp, i64]
     L.laser_hip_act_grad_f32_dev.argtypes = [ci, vp, pi, vp, pi, vp, pi, pi, ci, vp]
+    for fn in ("sin", "cos"):
+        getattr(L, f"laser_hip_{fn}_f32_dev").argtypes = [vp, pi, vp, pi, pi, ci, vp]
+        getattr(L, f"laser_hip_{fn}_f32").argtypes = [vp, vp, i64]
+    L.laser_hip_sincos_f32_dev.argtypes = [vp, pi, vp, pi, vp, pi, pi, ci, vp]
     L.laser_hip_sampler_tree_elems.argtypes = [i64, pi]
     L.laser_hip_sampler_plan.argtypes = [i64, i64, pi]
     L.laser_hip_sampler_build_f32_dev.argtypes = [vp, i64, vp, i64, i64, i64, vp]
@@ -162,6 +166,7 @@ def lib():
     L.laser_hip_cdf_sample_remove_rng_f32_dev.argtypes = [vp, vp, i64, vp, i64, u64, u64, u64, i64, i64, i64, vp]
     L.laser_hip_random_plan.argtypes = [i64, ci, u64, ci, ci, pi]
     L.laser_hip_random_bits_u32_dev.argtypes = [vp, i64, u64, u64, u64, vp]
+    L.laser_hip_random_normal_f32_dev.argtypes = [vp, i64, C.c_float, C.c_float, u64, u64, u64, vp]
     for sfx, ct in _CT.items():
         getattr(L, f"laser_hip_random_uniform_{sfx}_dev").argtypes = [vp, i64, ct, ct, u64, u64, u64, vp]
     L.laser_hip_cblas_sgemm.argtypes = [ci, ci, ci, i64, i64, i64, C.c_float, vp, i64, vp, i64, C.c_float, vp, i64]
@@ -205,10 +210,11 @@ def declared_symbols():
              "laser_hip_log_f32_dev", "laser_hip_log_f32", "laser_hip_logsumexp_rows_f32_dev",
              "laser_hip_log_softmax_rows_f32_dev", "laser_hip_softmax_xent_rows_f32_dev", "laser_hip_softmax_rows_plan",
              "laser_hip_act_f32_dev", "laser_hip_act_f32", "laser_hip_act_grad_f32_dev",
+             "laser_hip_sin_f32_dev", "laser_hip_cos_f32_dev", "laser_hip_sincos_f32_dev", "laser_hip_sin_f32", "laser_hip_cos_f32",
              "laser_hip_sampler_tree_elems", "laser_hip_sampler_plan", "laser_hip_sampler_build_f32_dev",
              "laser_hip_sampler_sample_f32_dev", "laser_hip_sampler_sample_remove_f32_dev", "laser_hip_sampler_update_f32_dev",
              "laser_hip_sampler_sample_rng_f32_dev", "laser_hip_sampler_sample_remove_rng_f32_dev",
-             "laser_hip_random_plan", "laser_hip_random_bits_u32_dev",
+             "laser_hip_random_plan", "laser_hip_random_bits_u32_dev", "laser_hip_random_normal_f32_dev",
              "laser_hip_cumsum_plan", "laser_hip_cdf_sample_f32_dev", "laser_hip_cdf_sample_remove_f32_dev",
              "laser_hip_cdf_sample_rng_f32_dev", "laser_hip_cdf_sample_remove_rng_f32_dev"]
     for s in _CT:

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "normal_core.h"
 #include "philox_core.h"
 #include "random_plan.h"
 #include "sampler_plan.h"
@@ -1523,6 +1524,71 @@ int laser_hip_act_grad_f32_dev(int act, float *dx, const int64_t *dxs, const flo
   HIP_TRY(launch_act_grad_f32(act, dx, dxs, dy, dys, y, ys, shape, rank, (hipStream_t)stream));
   return LASER_HIP_OK;
 }
+// ---- lsin, lcos and both at once (sincos_core.h, sincos.hip) ---------------------------------------------------------------------
+// the checks of the activation entry points; strides[0 .. ndst - 1] are destinations
+static int sincos_check(const char *what, int ndst, int nops, const int64_t *const *strides, const int64_t *shape, int rank, int64_t *total) {
+  if (rank < 0 || rank > kMaxRank) return fail(LASER_HIP_E_INVALID, "%s: rank %d outside 0..%d (LASER_MAXRANK)", what, rank, kMaxRank);
+  if (rank > 0 && !shape) return fail(LASER_HIP_E_INVALID, "%s: null shape / strides", what);
+  for (int i = 0; i < nops && rank > 0; i++)
+    if (!strides[i]) return fail(LASER_HIP_E_INVALID, "%s: null shape / strides", what);
+  *total = 1;
+  for (int d = 0; d < rank; d++) {
+    if (shape[d] < 0) return fail(LASER_HIP_E_INVALID, "%s: negative extent", what);
+    for (int i = 0; i < ndst; i++)
+      if (shape[d] > 1 && strides[i][d] == 0) return fail(LASER_HIP_E_INVALID, "%s: stride 0 on a destination (dimension %d)", what, d);
+    *total *= shape[d];
+  }
+  return LASER_HIP_OK;
+}
+static int sin_or_cos_dev(bool cosine, float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
+                          void *stream) {
+  const char *what = cosine ? "cos" : "sin";
+  const int64_t *st[2] = {ds, ss};
+  int64_t total;
+  if (int rc = sincos_check(what, 1, 2, st, shape, rank, &total)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (total == 0) return LASER_HIP_OK;
+  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "%s: null buffer", what);
+  HIP_TRY((cosine ? launch_cos_f32 : launch_sin_f32)(dst, ds, src, ss, shape, rank, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_sin_f32_dev(float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
+                          void *stream) {
+  return sin_or_cos_dev(false, dst, ds, src, ss, shape, rank, stream);
+}
+int laser_hip_cos_f32_dev(float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
+                          void *stream) {
+  return sin_or_cos_dev(true, dst, ds, src, ss, shape, rank, stream);
+}
+int laser_hip_sincos_f32_dev(float *sin_dst, const int64_t *sin_strides, float *cos_dst, const int64_t *cos_strides, const float *src,
+                             const int64_t *ss, const int64_t *shape, int rank, void *stream) {
+  const int64_t *st[3] = {sin_strides, cos_strides, ss};
+  int64_t total;
+  if (int rc = sincos_check("sincos", 2, 3, st, shape, rank, &total)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (total == 0) return LASER_HIP_OK;
+  if (!sin_dst || !cos_dst || !src) return fail(LASER_HIP_E_INVALID, "sincos: null buffer");
+  if (sin_dst == cos_dst) return fail(LASER_HIP_E_INVALID, "sincos: the two destinations are the same buffer");
+  HIP_TRY(launch_sincos_f32(sin_dst, sin_strides, cos_dst, cos_strides, src, ss, shape, rank, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+// the host-pointer forms: through device scratch, in place there, synchronous; the same kernels as the _dev forms
+static int sin_or_cos_host(bool cosine, float *dst, const float *src, int64_t len) {
+  if (len < 0 || (len > 0 && (!dst || !src))) return fail(LASER_HIP_E_INVALID, "%s: bad argument", cosine ? "cos" : "sin");
+  if (int rc = ensure_init()) return rc;
+  if (len == 0) return LASER_HIP_OK;
+  HostCall hc;
+  if (hc.rc) return hc.rc;
+  void *d_buf;
+  if (int rc = scratch_get(0, (size_t)len * sizeof(float), &d_buf)) return rc;
+  HIP_TRY(hipMemcpy(d_buf, src, (size_t)len * sizeof(float), hipMemcpyHostToDevice));
+  const int64_t stride = 1;
+  HIP_TRY((cosine ? launch_cos_f32 : launch_sin_f32)((float *)d_buf, &stride, (const float *)d_buf, &stride, &len, 1, nullptr));
+  HIP_TRY(hipMemcpy(dst, d_buf, (size_t)len * sizeof(float), hipMemcpyDeviceToHost));
+  return LASER_HIP_OK;
+}
+int laser_hip_sin_f32(float *dst, const float *src, int64_t len) { return sin_or_cos_host(false, dst, src, len); }
+int laser_hip_cos_f32(float *dst, const float *src, int64_t len) { return sin_or_cos_host(true, dst, src, len); }
 // the checks the three row entry points share, in the order of the softmax entry point
 static int rows_check(const char *what, int64_t src_row_stride, int64_t rows, int64_t n) {
   if (n < 1 || n > LASER_HIP_SOFTMAX_MAX_N) return fail(LASER_HIP_E_INVALID, "%s: row length %lld outside 1..2^26", what, (long long)n);
@@ -1750,7 +1816,7 @@ int laser_hip_cdf_sample_remove_rng_f32_dev(int32_t *idx, float *w, int64_t w_ro
   return LASER_HIP_OK;
 }
 
-// ---- random numbers: Philox4x32-10 and the uniform fills (random.hip, philox_core.h, random_plan.h) -------------------------
+// ---- random numbers: Philox4x32-10, the uniform and the normal fills (random.hip, philox_core.h, normal_core.h, random_plan.h)
 int laser_hip_random_plan(int64_t n, int words_per_elem, int64_t offset, int dst_misaligned, int cus, int64_t *out4) {
   if (!out4) return fail(LASER_HIP_E_INVALID, "random_plan: null out4");
   long long p[4];
@@ -1792,6 +1858,13 @@ int laser_hip_random_uniform_i32_dev(int32_t *dst, int64_t n, int32_t lo, int32_
 int laser_hip_random_uniform_i64_dev(int64_t *dst, int64_t n, int64_t lo, int64_t hi, int64_t seed, int64_t subseq, int64_t offset, void *stream) {
   if (int rc = random_args("random_uniform_i64", dst, n, lo <= hi)) return rc < 0 ? LASER_HIP_OK : rc;
   HIP_TRY(launch_random_uniform_i64(dst, n, lo, hi, (uint64_t)seed, (uint64_t)subseq, (uint64_t)offset, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_random_normal_f32_dev(float *dst, int64_t n, float mean, float std, int64_t seed, int64_t subseq, int64_t offset, void *stream) {
+  if (n >= 0 && n <= LH_RANDOM_MAX_N && !lh_normal_params_ok_f32(mean, std))
+    return fail(LASER_HIP_E_INVALID, "random_normal_f32: mean must be finite, std finite and >= 0");
+  if (int rc = random_args("random_normal_f32", dst, n, true)) return rc < 0 ? LASER_HIP_OK : rc;
+  HIP_TRY(launch_random_normal_f32(dst, n, mean, std, (uint64_t)seed, (uint64_t)subseq, (uint64_t)offset, (hipStream_t)stream));
   return LASER_HIP_OK;
 }
 

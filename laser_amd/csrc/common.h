@@ -251,6 +251,13 @@ hipError_t launch_act_f32(int act, float *dst, const int64_t *dstrides, const fl
                           int rank, hipStream_t s);
 hipError_t launch_act_grad_f32(int act, float *dx, const int64_t *dxstrides, const float *dy, const int64_t *dystrides, const float *y,
                                const int64_t *ystrides, const int64_t *shape, int rank, hipStream_t s);
+// lsin, lcos and both from one reduction over strided views (sincos.hip; sincos_core.h is the definition)
+hipError_t launch_sin_f32(float *dst, const int64_t *dstrides, const float *src, const int64_t *sstrides, const int64_t *shape, int rank,
+                          hipStream_t s);
+hipError_t launch_cos_f32(float *dst, const int64_t *dstrides, const float *src, const int64_t *sstrides, const int64_t *shape, int rank,
+                          hipStream_t s);
+hipError_t launch_sincos_f32(float *sin_dst, const int64_t *sin_strides, float *cos_dst, const int64_t *cos_strides, const float *src,
+                             const int64_t *sstrides, const int64_t *shape, int rank, hipStream_t s);
 // the F+tree weighted sampler (sampler.hip; sampler_plan.h picks the build kernel): tree images of 2 P elements per row
 hipError_t launch_sampler_build_f32(float *tree, int64_t tree_row_stride, const float *w, int64_t w_row_stride, int64_t rows, int64_t n,
                                     hipStream_t s);
@@ -296,6 +303,9 @@ hipError_t launch_random_uniform_i32(int32_t *dst, int64_t n, int32_t lo, int32_
                                      hipStream_t s);
 hipError_t launch_random_uniform_i64(int64_t *dst, int64_t n, int64_t lo, int64_t hi, uint64_t seed, uint64_t subseq, uint64_t offset,
                                      hipStream_t s);
+// the normal fill (normal_core.h): Box-Muller pairs on the same streams, one word per element
+hipError_t launch_random_normal_f32(float *dst, int64_t n, float mean, float std, uint64_t seed, uint64_t subseq, uint64_t offset,
+                                    hipStream_t s);
 template <typename T>
 hipError_t launch_pack_pad(T *dst, int64_t Rpad, int64_t Cpad, const T *src, int64_t R,
                            int64_t Ccols, int64_t rs, int64_t cs, hipStream_t s, int relu = 0);

@@ -28,7 +28,7 @@
 #include "capi_internal.h"
 #include "common.h"
 #include "foreach_template.h"  // generated from foreach_kernel.hip.in, foreach_reduce_kernel.hip.in, reduce_core.h and
-                                // exp_core.h, log_core.h, act_core.h: lh_foreach_template, lh_foreach_reduce_template, lh_reduce_core, lh_exp_core, lh_log_core, lh_act_core
+                                // exp_core.h, log_core.h, act_core.h, sincos_core.h: lh_foreach_template, lh_foreach_reduce_template, lh_reduce_core, lh_exp_core, lh_log_core, lh_act_core, lh_sincos_core
 
 using namespace laser_hip;
 
@@ -98,6 +98,8 @@ int check_name(const char *what, int i, const char *name) {
   if (s == "laser_log") return fail(LASER_HIP_E_INVALID, "foreach: %s name 'laser_log' is reserved (log_core.h)", what);
   if (s == "laser_tanh" || s == "laser_sigmoid")
     return fail(LASER_HIP_E_INVALID, "foreach: %s name '%s' is reserved (act_core.h)", what, name);
+  if (s == "laser_sin" || s == "laser_cos")
+    return fail(LASER_HIP_E_INVALID, "foreach: %s name '%s' is reserved (sincos_core.h)", what, name);
   return LASER_HIP_OK;
 }
 
@@ -192,8 +194,14 @@ std::string generate(const Spec &sp) {
   const std::string tpl = lh_foreach_template, mark = "\n@LH_SPEC@\n";
   const size_t at = tpl.find(mark) + 1;
   // forEach's prelude, then lexp and llog (exp_core.h, log_core.h: laser_exp and laser_log for the bodies); forEachReduce:
-  // then the order (reduce_core.h); then the spec and the kernels
-  const std::string head = tpl.substr(0, at) + lh_exp_core + lh_log_core + lh_act_core + (sp.reduce ? std::string(lh_reduce_core) : std::string());
+  // then the order (reduce_core.h); then the spec and the kernels.  lsin and lcos (sincos_core.h: laser_sin, laser_cos) follow
+  // act_core.h only when the body or the merge names one of them: no other kernel pays for compiling them
+  const std::string text = sp.body + "\n" + sp.merge;
+  const bool trig = text.find("laser_sin") != std::string::npos || text.find("laser_cos") != std::string::npos ||
+                    text.find("lh_sin") != std::string::npos || text.find("lh_cos") != std::string::npos ||
+                    text.find("lh_sc_") != std::string::npos;
+  const std::string head = tpl.substr(0, at) + lh_exp_core + lh_log_core + lh_act_core + (trig ? std::string(lh_sincos_core) : std::string()) +
+                           (sp.reduce ? std::string(lh_reduce_core) : std::string());
   // the lines after the body report their line in the generated source again
   const size_t line = std::count(head.begin(), head.end(), '\n') + std::count(s.begin(), s.end(), '\n') + 2;
   s += "#line " + std::to_string(line) + (sp.reduce ? " \"foreach_reduce.hip\"\n" : " \"foreach.hip\"\n");

@@ -29,8 +29,10 @@
 // The integer multiply-shift is not exactly uniform: a value is hit by floor or ceil of 2^32 / span words (2^64 / span), so a
 // probability is off by at most a factor 1 +- span / 2^32 (i32) or span / 2^64 (i64).  There is no rejection loop: an element
 // costs a fixed number of words, which is what makes offsets and chunked fills add up.
-// Not built: normal and other non-uniform distributions (they need a bit-defined sincos beside llog first), the other six element
-// types, strided destinations, a laser_rand callable in forEach bodies.
+// The normal distribution (float32, Box-Muller on pairs of words) is normal_core.h, on top of this file, log_core.h and
+// sincos_core.h.
+// Not built: float64 normals, other distributions, the other six element types, strided destinations, a laser_rand callable in
+// forEach bodies.
 //
 // Plain C++ with no includes.  A host build needs -ffp-contract=off (the pragma below covers clang).  Names start with lh_.
 #ifndef LASER_HIP_PHILOX_CORE_H

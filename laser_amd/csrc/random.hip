@@ -1,15 +1,19 @@
-// laser_amd/csrc/random.hip -- fills of device arrays with uniform random numbers (include/laser_hip.h "Random numbers").
-// The generator and the distributions are philox_core.h; which lane owns which block, and the grid, are random_plan.h.
+// laser_amd/csrc/random.hip -- fills of device arrays with uniform and normal random numbers (include/laser_hip.h "Random
+// numbers").  The generator and the uniform distributions are philox_core.h, the normal distribution is normal_core.h; which
+// lane owns which block, and the grid, are random_plan.h.
 //
 // One lane computes one Philox4x32-10 block per step -- about forty 32-bit multiplies and as many xors and adds for 16 bytes of
 // output -- and stores the elements that start in it: four 32-bit elements or two 64-bit ones, 16 contiguous bytes.  The lanes
 // of a wave own consecutive blocks, so on the vector path a wave writes 1 KiB contiguous per step.  A block only partly
 // inside [0, n) (the head when offset & 3 != 0, the tail) is stored element by element; so is everything when the runs do not
 // start on 16-byte boundaries.  Block indices wrap mod 2^62 like the words they hold wrap mod 2^64.
+// The normal fill is one word per element like the 32-bit uniform ones: a block is two Box-Muller pairs, (o[0], o[1]) and
+// (o[2], o[3]), each giving its cosine and its sine branch, with the radius and the angle reduction computed once per pair.
 #include <hip/hip_runtime.h>
 
 #include "../../include/laser_hip.h"
 #include "common.h"
+#include "normal_core.h"
 #include "philox_core.h"
 #include "random_plan.h"
 
@@ -20,35 +24,55 @@ namespace {
 
 typedef unsigned long long u64;
 
-// element i = op(x) of its word (WPE = 1) or of its pair of words, low word first (WPE = 2)
+// element i = op(x) of its word (WPE = 1) or of its pair of words, low word first (WPE = 2); BLOCK: op(o, v) turns the four
+// words of a block into its four elements at once (WPE = 1)
 struct BitsU32 {
   typedef uint32_t T;
   static constexpr int WPE = 1;
+  static constexpr bool BLOCK = false;
   __device__ __forceinline__ T operator()(const unsigned int x) const { return x; }
 };
 struct UniformF32 {
   typedef float T;
   static constexpr int WPE = 1;
+  static constexpr bool BLOCK = false;
   float lo, hi;
   __device__ __forceinline__ T operator()(const unsigned int x) const { return lh_uniform_f32(x, lo, hi); }
 };
 struct UniformI32 {
   typedef int32_t T;
   static constexpr int WPE = 1;
+  static constexpr bool BLOCK = false;
   int32_t lo, hi;
   __device__ __forceinline__ T operator()(const unsigned int x) const { return lh_uniform_i32(x, lo, hi); }
 };
 struct UniformF64 {
   typedef double T;
   static constexpr int WPE = 2;
+  static constexpr bool BLOCK = false;
   double lo, hi;
   __device__ __forceinline__ T operator()(const u64 x) const { return lh_uniform_f64(x, lo, hi); }
 };
 struct UniformI64 {
   typedef int64_t T;
   static constexpr int WPE = 2;
+  static constexpr bool BLOCK = false;
   int64_t lo, hi;
   __device__ __forceinline__ T operator()(const u64 x) const { return (int64_t)lh_uniform_i64(x, lo, hi); }
+};
+
+struct NormalF32 {
+  typedef float T;
+  static constexpr int WPE = 1;
+  static constexpr bool BLOCK = true;
+  float mean, std;
+  __device__ __forceinline__ void operator()(const unsigned int o[4], float v[4]) const {
+    float z[4];
+    lh_normal_pair(o[0], o[1], &z[0], &z[1]);
+    lh_normal_pair(o[2], o[3], &z[2], &z[3]);
+#pragma unroll
+    for (int j = 0; j < 4; j++) v[j] = lh_normal_scale_f32(z[j], mean, std);
+  }
 };
 
 template <typename T>
@@ -69,7 +93,9 @@ __global__ void __launch_bounds__(256) random_fill_kernel(typename Op::T *dst, c
     lh_philox_block(seed, subseq, (b0 + (u64)k) & mask62, o);
     const long long e0 = (4 * k + unit - head) / WPE;  // the run's first element: may be < 0 (head) or end past n (tail); exact
     T v[EPB];
-    if constexpr (WPE == 1) {
+    if constexpr (Op::BLOCK) {
+      op(o, v);
+    } else if constexpr (WPE == 1) {
 #pragma unroll
       for (int j = 0; j < 4; j++) v[j] = op(o[j]);
     } else {
@@ -137,6 +163,11 @@ hipError_t launch_random_uniform_i32(int32_t *dst, int64_t n, int32_t lo, int32_
 hipError_t launch_random_uniform_i64(int64_t *dst, int64_t n, int64_t lo, int64_t hi, uint64_t seed, uint64_t subseq, uint64_t offset,
                                      hipStream_t s) {
   return fill(dst, n, seed, subseq, offset, UniformI64{lo, hi}, s);
+}
+
+hipError_t launch_random_normal_f32(float *dst, int64_t n, float mean, float std, uint64_t seed, uint64_t subseq, uint64_t offset,
+                                    hipStream_t s) {
+  return fill(dst, n, seed, subseq, offset, NormalF32{mean, std}, s);
 }
 
 }  // namespace laser_hip

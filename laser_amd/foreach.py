@@ -7,7 +7,8 @@ The body is HIP C++ compiled at run time (laser_hip_foreach_* in include/laser_h
 examples is valid C++, and the device math library (expf, logf, sqrtf, fmaxf, ...) can be called, as can laser_exp(x),
 Laser's own table-driven exp (laser_amd/csrc/exp_core.h, the function behind laser_amd.exp), and laser_log(x), the
 bit-defined logarithm behind laser_amd.log (laser_amd/csrc/log_core.h), and laser_tanh(x) and laser_sigmoid(x), the functions
-behind laser_amd.tanh and laser_amd.sigmoid (laser_amd/csrc/act_core.h).  An operand is anything
+behind laser_amd.tanh and laser_amd.sigmoid (laser_amd/csrc/act_core.h), and laser_sin(x) and laser_cos(x), the bit-defined
+sine and cosine behind laser_amd.sin and laser_amd.cos (laser_amd/csrc/sincos_core.h).  An operand is anything
 with __cuda_array_interface__ -- a laser_amd.Tensor or a torch CUDA tensor -- of one of ten element types (f32, f64,
 int8..int64, uint8..uint64), mixed freely.  The first operand gives the iteration shape and is the writable one unless
 `writable` names others; writable operands have exactly that shape, read-only ones broadcast like numpy.  `params` are

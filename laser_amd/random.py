@@ -8,6 +8,11 @@
                                                    uniform on the closed interval (lo, hi), a bare max means (0, max);
                                                    dtype float32, float64, int32 or int64
     laser_amd.randomTensor(shape, valrange_or_max, dtype, *, seed, subseq=0, offset=0)      the same as a pure function
+    rng.randomNormalTensor(shape, mean=0.0, std=1.0)
+                                                   float32 normal draws: Box-Muller on pairs of words of the same stream
+                                                   (laser_amd/csrc/normal_core.h; tests/normal_model.py is the numpy model),
+                                                   one word per element: the offset advances by the element count
+    laser_amd.randomNormalTensor(shape, mean, std, *, seed, subseq=0, offset=0)             the same as a pure function
 
 Word w of a stream is a function of (seed, subseq, w) alone: no state lives on the device, every draw advances the host-side
 offset by the words it used (one per 32-bit element, two per 64-bit element), so two successive draws are one draw of the
@@ -103,6 +108,20 @@ class Rng:
         self.advance(out.size * (dt.itemsize // 4))
         return out
 
+    def randomNormalTensor(self, shape, mean=0.0, std=1.0):
+        """normal with the given mean and standard deviation: a row-major float32 Tensor of `shape`, element k of the flat order
+        from stream position offset + k (even positions are the cosine branch of their Box-Muller pair, odd ones the sine
+        branch); the offset advances by the element count, so a following draw of any kind continues the stream"""
+        shape = _shape(shape)
+        mean, std = np.float32(mean), np.float32(std)
+        if not (np.isfinite(mean) and np.isfinite(std) and std >= 0):
+            raise ValueError(f"randomNormalTensor: mean {mean}, std {std}: mean must be finite, std finite and >= 0 in float32")
+        out = newTensor(np.float32, *shape)
+        _lib.check(_lib.lib().laser_hip_random_normal_f32_dev(C.c_void_p(out.unsafe_raw_data()), out.size, float(mean), float(std),
+                                                              self.seed, self.subseq, self.offset, _stream()))
+        self.advance(out.size)
+        return out
+
     def __repr__(self):
         return f"Rng(seed={self.seed:#x}, subseq={self.subseq:#x}, offset={self.offset})"
 
@@ -110,3 +129,8 @@ class Rng:
 def randomTensor(shape, valrange_or_max, dtype=np.float32, *, seed, subseq=0, offset=0):
     """randomTensor as a pure function of its arguments: Rng(seed, subseq, offset).randomTensor(shape, valrange_or_max, dtype)"""
     return Rng(seed, subseq, offset).randomTensor(shape, valrange_or_max, dtype)
+
+
+def randomNormalTensor(shape, mean=0.0, std=1.0, *, seed, subseq=0, offset=0):
+    """randomNormalTensor as a pure function of its arguments: Rng(seed, subseq, offset).randomNormalTensor(shape, mean, std)"""
+    return Rng(seed, subseq, offset).randomNormalTensor(shape, mean, std)

@@ -1,6 +1,7 @@
 """Laser's table-driven exp and the row softmax on top of it (laser/primitives/simd_math/exp_log_*.nim; include/laser_hip.h
 "exp and row softmax"), the way from logits to a loss (include/laser_hip.h "log, logsumexp, log-softmax and
-cross-entropy") and the activations with their gradients (include/laser_hip.h "Activations"), float32:
+cross-entropy"), the activations with their gradients (include/laser_hip.h "Activations") and the bit-defined sine and
+cosine (include/laser_hip.h "Sine and cosine"), float32:
 
     laser_amd.exp(t)        lexp of every element: the exported SIMD `exp*` of the reference, bit for bit
     laser_amd.softmax(t)    softmax over the rows of a 2-D tensor, summed in the fixed order of the reductions
@@ -16,12 +17,15 @@ cross-entropy") and the activations with their gradients (include/laser_hip.h "A
     laser_amd.activation(t, kind, out=None)          kind "relu", "tanh" or "sigmoid": relu is x > 0 ? x : +0
     laser_amd.activation_grad(dy, y, kind, out=None)   the gradient from the forward OUTPUT y: relu y > 0 ? dy : +0,
                             tanh dy * (1 - y * y), sigmoid dy * (y * (1 - y)), every float32 operation rounded on its own
+    laser_amd.sin(t), laser_amd.cos(t)    lsin / lcos of every element: the bit-defined sine and cosine of
+                            laser_amd/csrc/sincos_core.h (faithful for every finite float32, lsin odd and lcos even bit for bit)
+    laser_amd.sincos(t, out=None)         (lsin(t), lcos(t)) from one argument reduction, the same bits; out=(s, c)
 
 An operand is a laser_amd.Tensor or a torch CUDA tensor (anything with __cuda_array_interface__); `exp` also takes a host
 float32 numpy array, like the reference's benchmark loop.  With out=None a device call returns a fresh row-major Tensor;
 with `out` it writes there (out may be the input) and returns it.  Device calls are asynchronous on the current torch
-stream.  Inside forEach / forEachReduce bodies the same functions are `laser_exp(x)`, `laser_log(x)`, `laser_tanh(x)` and
-`laser_sigmoid(x)`.
+stream.  Inside forEach / forEachReduce bodies the same functions are `laser_exp(x)`, `laser_log(x)`, `laser_tanh(x)`,
+`laser_sigmoid(x)`, `laser_sin(x)` and `laser_cos(x)`.
 """
 import ctypes as C
 
@@ -116,6 +120,35 @@ def activation_grad(dy, y, kind, out=None):
                                                      arr(_bcast_strides(g, dst.shape)), C.c_void_p(o.ptr),
                                                      arr(_bcast_strides(o, dst.shape)), arr(dst.shape), r, _stream()))
     return out
+
+
+def sin(t, out=None):
+    """lsin(t), elementwise: the bit-defined float32 sine of laser_amd/csrc/sincos_core.h -- faithful for every finite input,
+    odd bit for bit, lsin(x) = x for tiny and subnormal x, NaN (bits 0x7fc00000) for NaN and +-Inf.  Operands as `exp`: a
+    device tensor or view (`t` broadcasts against `out`, `out` may be `t`) or a host float32 array."""
+    return _elementwise("sin", t, out)
+
+
+def cos(t, out=None):
+    """lcos(t), elementwise: the bit-defined float32 cosine of the same header -- faithful, even bit for bit, 1 for tiny x"""
+    return _elementwise("cos", t, out)
+
+
+def sincos(t, out=None):
+    """(lsin(t), lcos(t)) of a device tensor or view from one argument reduction: the bits of sin(t) and cos(t).  out=None:
+    two fresh row-major Tensors; out=(s, c): written there (either may be `t`; they must not overlap each other)"""
+    src = _f32("t", t)
+    if out is None:
+        out = (newTensor(np.float32, *src.shape), newTensor(np.float32, *src.shape))
+    s, c = out
+    ds, dc = _f32("out[0]", s), _f32("out[1]", c)
+    if ds.shape != dc.shape:
+        raise ValueError(f"sincos: the two destinations have shapes {ds.shape} and {dc.shape}")
+    r = ds.rank
+    arr = lambda v: (C.c_int64 * max(r, 1))(*v)
+    _lib.check(_lib.lib().laser_hip_sincos_f32_dev(C.c_void_p(ds.ptr), arr(ds.strides), C.c_void_p(dc.ptr), arr(dc.strides),
+                                                   C.c_void_p(src.ptr), arr(_bcast_strides(src, ds.shape)), arr(ds.shape), r, _stream()))
+    return s, c
 
 
 def _collapse(dims):

@@ -712,6 +712,40 @@ proc activationGrad*(kind: Activation, dx, dy, y: DevicePtr[float32], len: Natur
   var n = int64(len)
   check laser_hip_act_grad_f32_dev(cint(ord(kind)), cast[ptr float32](dx), stride.addr, cast[ptr float32](dy), stride.addr, cast[ptr float32](y), stride.addr, n.addr, 1, stream)
 
+# ---- sine and cosine (include/laser_hip.h "Sine and cosine"): lsin and lcos of sincos_core.h -----------------------------
+# faithful for every finite float32, lsin odd and lcos even bit for bit, lsin(x) = x for tiny x, NaN for NaN and +-Inf
+proc laser_hip_sin_f32(dst: ptr float32, src: ptr float32, len: int64): cint {.lh, importc: "laser_hip_sin_f32".}
+proc laser_hip_cos_f32(dst: ptr float32, src: ptr float32, len: int64): cint {.lh, importc: "laser_hip_cos_f32".}
+proc laser_hip_sin_f32_dev*(dst: ptr float32, dstStrides: ptr int64, src: ptr float32, srcStrides: ptr int64, shape: ptr int64, rank: cint, stream: pointer): cint {.lh, importc: "laser_hip_sin_f32_dev".}
+proc laser_hip_cos_f32_dev*(dst: ptr float32, dstStrides: ptr int64, src: ptr float32, srcStrides: ptr int64, shape: ptr int64, rank: cint, stream: pointer): cint {.lh, importc: "laser_hip_cos_f32_dev".}
+proc laser_hip_sincos_f32_dev*(sinDst: ptr float32, sinStrides: ptr int64, cosDst: ptr float32, cosStrides: ptr int64, src: ptr float32, srcStrides: ptr int64, shape: ptr int64, rank: cint, stream: pointer): cint {.lh, importc: "laser_hip_sincos_f32_dev".}
+
+proc sin*(dst, src: ptr (float32 or UncheckedArray[float32]), len: Natural) =
+  ## dst[i] = sin(src[i]) over a contiguous range of float32 (host memory; the GPU computes it)
+  check laser_hip_sin_f32(cast[ptr float32](dst), cast[ptr float32](src), int64(len))
+
+proc cos*(dst, src: ptr (float32 or UncheckedArray[float32]), len: Natural) =
+  ## dst[i] = cos(src[i]) over a contiguous range of float32 (host memory; the GPU computes it)
+  check laser_hip_cos_f32(cast[ptr float32](dst), cast[ptr float32](src), int64(len))
+
+proc sin*(dst, src: DevicePtr[float32], len: Natural, stream: pointer = nil) =
+  ## dst[i] = sin(src[i]) over `len` contiguous device elements; dst may be src
+  var stride = 1'i64
+  var n = int64(len)
+  check laser_hip_sin_f32_dev(cast[ptr float32](dst), stride.addr, cast[ptr float32](src), stride.addr, n.addr, 1, stream)
+
+proc cos*(dst, src: DevicePtr[float32], len: Natural, stream: pointer = nil) =
+  ## dst[i] = cos(src[i]) over `len` contiguous device elements; dst may be src
+  var stride = 1'i64
+  var n = int64(len)
+  check laser_hip_cos_f32_dev(cast[ptr float32](dst), stride.addr, cast[ptr float32](src), stride.addr, n.addr, 1, stream)
+
+proc sincos*(sinDst, cosDst, src: DevicePtr[float32], len: Natural, stream: pointer = nil) =
+  ## both from one argument reduction, the same bits as sin and cos; either destination may be src
+  var stride = 1'i64
+  var n = int64(len)
+  check laser_hip_sincos_f32_dev(cast[ptr float32](sinDst), stride.addr, cast[ptr float32](cosDst), stride.addr, cast[ptr float32](src), stride.addr, n.addr, 1, stream)
+
 # ---- F+tree weighted sampler (include/laser_hip.h "F+tree weighted sampler"): fenwicktree.nim over HipStorage -----------
 # One tree image of 2 P float32 per row (P = the next power of two >= n; the reference's array shifted up by one slot).  The
 # uniform numbers are the caller's, or come from a HipRng stream ("Random numbers" below): the overloads taking `rng`.
@@ -759,6 +793,7 @@ proc laser_hip_random_uniform_f32_dev*(dst: ptr float32, n: int64, lo: float32, 
 proc laser_hip_random_uniform_f64_dev*(dst: ptr float64, n: int64, lo: float64, hi: float64, seed: int64, subseq: int64, offset: int64, stream: pointer): cint {.lh, importc: "laser_hip_random_uniform_f64_dev".}
 proc laser_hip_random_uniform_i32_dev*(dst: ptr int32, n: int64, lo: int32, hi: int32, seed: int64, subseq: int64, offset: int64, stream: pointer): cint {.lh, importc: "laser_hip_random_uniform_i32_dev".}
 proc laser_hip_random_uniform_i64_dev*(dst: ptr int64, n: int64, lo: int64, hi: int64, seed: int64, subseq: int64, offset: int64, stream: pointer): cint {.lh, importc: "laser_hip_random_uniform_i64_dev".}
+proc laser_hip_random_normal_f32_dev*(dst: ptr float32, n: int64, mean: float32, std: float32, seed: int64, subseq: int64, offset: int64, stream: pointer): cint {.lh, importc: "laser_hip_random_normal_f32_dev".}
 proc laser_hip_sampler_sample_rng_f32_dev*(idx: ptr int32, tree: ptr float32, treeRowStride: int64, seed: int64, subseq: int64, offset: int64, rows: int64, n: int64, m: int64, stream: pointer): cint {.lh, importc: "laser_hip_sampler_sample_rng_f32_dev".}
 proc laser_hip_sampler_sample_remove_rng_f32_dev*(idx: ptr int32, tree: ptr float32, treeRowStride: int64, seed: int64, subseq: int64, offset: int64, rows: int64, n: int64, k: int64, stream: pointer): cint {.lh, importc: "laser_hip_sampler_sample_remove_rng_f32_dev".}
 
@@ -792,6 +827,15 @@ proc randomTensor*[T](shape: openarray[int], valrange: Slice[T], rng: var HipRng
 proc randomTensor*[T](shape: openarray[int], max: T, rng: var HipRng): HipStorage[T] =
   ## randomTensor(shape, max) (reduction_bench.nim:40): uniform on 0 .. max
   randomTensor(shape, T(0)..max, rng)
+
+proc randomNormalTensor*(shape: openarray[int], mean, std: float32, rng: var HipRng): HipStorage[float32] =
+  ## prod(shape) float32 normal draws in row-major order (Box-Muller on pairs of words of the stream, normal_core.h): element k
+  ## from stream position rng.offset + k; the offset advances by the element count
+  var size = 1
+  for s in shape: size *= s
+  allocHipStorage(result, size)
+  check laser_hip_random_normal_f32_dev(cast[ptr float32](result.raw_buffer), int64(size), mean, std, cast[int64](rng.seed), cast[int64](rng.subseq), cast[int64](rng.offset), nil)
+  rng.offset += uint64(size)
 
 proc randomBits*(n: Natural, rng: var HipRng): HipStorage[uint32] =
   ## the next n words of the stream
