@@ -1345,26 +1345,39 @@ int laser_hip_reduce_sum_f32(const float *data, int64_t len, float *out) { retur
 int laser_hip_reduce_min_f32(const float *data, int64_t len, float *out) { return reduce_host_f32(1, data, len, out); }
 int laser_hip_reduce_max_f32(const float *data, int64_t len, float *out) { return reduce_host_f32(2, data, len, out); }
 
-// ---- lexp and the row softmax: laser/primitives/simd_math/exp_log_*.nim (exp_core.h, exp_softmax.hip) -----------------
-int laser_hip_exp_f32_dev(float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
-                          void *stream) {
-  if (rank < 0 || rank > kMaxRank) return fail(LASER_HIP_E_INVALID, "exp: rank %d outside 0..%d (LASER_MAXRANK)", rank, kMaxRank);
-  if (rank > 0 && (!ds || !ss || !shape)) return fail(LASER_HIP_E_INVALID, "exp: null shape / strides");
-  int64_t total = 1;
+// ---- the elementwise functions on pointwise.h: lexp, llog, the activations with their gradients, lsin / lcos ---------------
+// The checks their device entry points share, over nops operands of which strides[0 .. ndst - 1] belong to destinations.
+static int pointwise_check(const char *what, int ndst, int nops, const int64_t *const *strides, const int64_t *shape, int rank,
+                           int64_t *total) {
+  if (rank < 0 || rank > kMaxRank) return fail(LASER_HIP_E_INVALID, "%s: rank %d outside 0..%d (LASER_MAXRANK)", what, rank, kMaxRank);
+  if (rank > 0 && !shape) return fail(LASER_HIP_E_INVALID, "%s: null shape / strides", what);
+  for (int i = 0; i < nops && rank > 0; i++)
+    if (!strides[i]) return fail(LASER_HIP_E_INVALID, "%s: null shape / strides", what);
+  *total = 1;
   for (int d = 0; d < rank; d++) {
-    if (shape[d] < 0) return fail(LASER_HIP_E_INVALID, "exp: negative extent");
-    if (shape[d] > 1 && ds[d] == 0) return fail(LASER_HIP_E_INVALID, "exp: stride 0 on the destination (dimension %d)", d);
-    total *= shape[d];
+    if (shape[d] < 0) return fail(LASER_HIP_E_INVALID, "%s: negative extent", what);
+    for (int i = 0; i < ndst; i++)
+      if (shape[d] > 1 && strides[i][d] == 0) return fail(LASER_HIP_E_INVALID, "%s: stride 0 on a destination (dimension %d)", what, d);
+    *total *= shape[d];
   }
-  if (int rc = ensure_init()) return rc;
-  if (total == 0) return LASER_HIP_OK;
-  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "exp: null buffer");
-  HIP_TRY(launch_exp_f32(dst, ds, src, ss, shape, rank, (hipStream_t)stream));
   return LASER_HIP_OK;
 }
-// the host-pointer form: through device scratch, in place there, synchronous; the same kernel as the _dev form
-int laser_hip_exp_f32(float *dst, const float *src, int64_t len) {
-  if (len < 0 || (len > 0 && (!dst || !src))) return fail(LASER_HIP_E_INVALID, "exp: bad argument");
+// a device entry point with one source and one destination, around its launch_*_f32
+typedef std::function<hipError_t(float *, const int64_t *, const float *, const int64_t *, const int64_t *, int, hipStream_t)> UnaryLaunch;
+static int unary_dev(const char *what, float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
+                     void *stream, const UnaryLaunch &launch) {
+  const int64_t *st[2] = {ds, ss};
+  int64_t total;
+  if (int rc = pointwise_check(what, 1, 2, st, shape, rank, &total)) return rc;
+  if (int rc = ensure_init()) return rc;
+  if (total == 0) return LASER_HIP_OK;
+  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "%s: null buffer", what);
+  HIP_TRY(launch(dst, ds, src, ss, shape, rank, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+// the host-pointer form of the same: through device scratch, in place there, synchronous; the same kernel as the _dev form
+static int unary_host(const char *what, float *dst, const float *src, int64_t len, const UnaryLaunch &launch) {
+  if (len < 0 || (len > 0 && (!dst || !src))) return fail(LASER_HIP_E_INVALID, "%s: bad argument", what);
   if (int rc = ensure_init()) return rc;
   if (len == 0) return LASER_HIP_OK;
   HostCall hc;
@@ -1373,10 +1386,17 @@ int laser_hip_exp_f32(float *dst, const float *src, int64_t len) {
   if (int rc = scratch_get(0, (size_t)len * sizeof(float), &d_buf)) return rc;
   HIP_TRY(hipMemcpy(d_buf, src, (size_t)len * sizeof(float), hipMemcpyHostToDevice));
   const int64_t stride = 1;
-  HIP_TRY(launch_exp_f32((float *)d_buf, &stride, (const float *)d_buf, &stride, &len, 1, nullptr));
+  HIP_TRY(launch((float *)d_buf, &stride, (const float *)d_buf, &stride, &len, 1, nullptr));
   HIP_TRY(hipMemcpy(dst, d_buf, (size_t)len * sizeof(float), hipMemcpyDeviceToHost));
   return LASER_HIP_OK;
 }
+
+// ---- lexp and the row softmax: laser/primitives/simd_math/exp_log_*.nim (exp_core.h, exp_softmax.hip) -----------------
+int laser_hip_exp_f32_dev(float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
+                          void *stream) {
+  return unary_dev("exp", dst, ds, src, ss, shape, rank, stream, launch_exp_f32);
+}
+int laser_hip_exp_f32(float *dst, const float *src, int64_t len) { return unary_host("exp", dst, src, len, launch_exp_f32); }
 int laser_hip_softmax_rows_f32_dev(float *dst, int64_t dst_row_stride, const float *src, int64_t src_row_stride, int64_t rows,
                                    int64_t n, void *stream) {
   if (n < 1 || n > LASER_HIP_SOFTMAX_MAX_N) return fail(LASER_HIP_E_INVALID, "softmax: row length %lld outside 1..2^26", (long long)n);
@@ -1440,84 +1460,30 @@ int laser_hip_softmax_axis_plan(int64_t outer, int64_t n, int64_t inner, int vec
 // ---- llog, logsumexp, log-softmax and the softmax cross-entropy (log_core.h, log_softmax.hip, softmax_rows_plan.h) --------
 int laser_hip_log_f32_dev(float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
                           void *stream) {
-  if (rank < 0 || rank > kMaxRank) return fail(LASER_HIP_E_INVALID, "log: rank %d outside 0..%d (LASER_MAXRANK)", rank, kMaxRank);
-  if (rank > 0 && (!ds || !ss || !shape)) return fail(LASER_HIP_E_INVALID, "log: null shape / strides");
-  int64_t total = 1;
-  for (int d = 0; d < rank; d++) {
-    if (shape[d] < 0) return fail(LASER_HIP_E_INVALID, "log: negative extent");
-    if (shape[d] > 1 && ds[d] == 0) return fail(LASER_HIP_E_INVALID, "log: stride 0 on the destination (dimension %d)", d);
-    total *= shape[d];
-  }
-  if (int rc = ensure_init()) return rc;
-  if (total == 0) return LASER_HIP_OK;
-  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "log: null buffer");
-  HIP_TRY(launch_log_f32(dst, ds, src, ss, shape, rank, (hipStream_t)stream));
-  return LASER_HIP_OK;
+  return unary_dev("log", dst, ds, src, ss, shape, rank, stream, launch_log_f32);
 }
-// the host-pointer form: through device scratch, in place there, synchronous; the same kernel as the _dev form
-int laser_hip_log_f32(float *dst, const float *src, int64_t len) {
-  if (len < 0 || (len > 0 && (!dst || !src))) return fail(LASER_HIP_E_INVALID, "log: bad argument");
-  if (int rc = ensure_init()) return rc;
-  if (len == 0) return LASER_HIP_OK;
-  HostCall hc;
-  if (hc.rc) return hc.rc;
-  void *d_buf;
-  if (int rc = scratch_get(0, (size_t)len * sizeof(float), &d_buf)) return rc;
-  HIP_TRY(hipMemcpy(d_buf, src, (size_t)len * sizeof(float), hipMemcpyHostToDevice));
-  const int64_t stride = 1;
-  HIP_TRY(launch_log_f32((float *)d_buf, &stride, (const float *)d_buf, &stride, &len, 1, nullptr));
-  HIP_TRY(hipMemcpy(dst, d_buf, (size_t)len * sizeof(float), hipMemcpyDeviceToHost));
-  return LASER_HIP_OK;
-}
+int laser_hip_log_f32(float *dst, const float *src, int64_t len) { return unary_host("log", dst, src, len, launch_log_f32); }
 // ---- relu, ltanh, lsigmoid and their gradients from the output (act_core.h, activation.hip) -----------------------------------
-static int act_check(const char *what, int act, int nin, const int64_t *const *strides, const int64_t *shape, int rank, int64_t *total) {
+static int act_code_check(const char *what, int act) {
   if (act != LASER_HIP_ACT_RELU && act != LASER_HIP_ACT_TANH && act != LASER_HIP_ACT_SIGMOID)
     return fail(LASER_HIP_E_INVALID, "%s: act %d is not LASER_HIP_ACT_RELU, _TANH or _SIGMOID", what, act);
-  if (rank < 0 || rank > kMaxRank) return fail(LASER_HIP_E_INVALID, "%s: rank %d outside 0..%d (LASER_MAXRANK)", what, rank, kMaxRank);
-  if (rank > 0 && !shape) return fail(LASER_HIP_E_INVALID, "%s: null shape / strides", what);
-  for (int i = 0; i <= nin && rank > 0; i++)
-    if (!strides[i]) return fail(LASER_HIP_E_INVALID, "%s: null shape / strides", what);
-  *total = 1;
-  for (int d = 0; d < rank; d++) {
-    if (shape[d] < 0) return fail(LASER_HIP_E_INVALID, "%s: negative extent", what);
-    if (shape[d] > 1 && strides[0][d] == 0) return fail(LASER_HIP_E_INVALID, "%s: stride 0 on the destination (dimension %d)", what, d);
-    *total *= shape[d];
-  }
   return LASER_HIP_OK;
 }
 int laser_hip_act_f32_dev(int act, float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
                           void *stream) {
-  const int64_t *st[2] = {ds, ss};
-  int64_t total;
-  if (int rc = act_check("act", act, 1, st, shape, rank, &total)) return rc;
-  if (int rc = ensure_init()) return rc;
-  if (total == 0) return LASER_HIP_OK;
-  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "act: null buffer");
-  HIP_TRY(launch_act_f32(act, dst, ds, src, ss, shape, rank, (hipStream_t)stream));
-  return LASER_HIP_OK;
+  if (int rc = act_code_check("act", act)) return rc;
+  return unary_dev("act", dst, ds, src, ss, shape, rank, stream, [act](auto... a) { return launch_act_f32(act, a...); });
 }
-// the host-pointer form: through device scratch, in place there, synchronous; the same kernel as the _dev form
 int laser_hip_act_f32(int act, float *dst, const float *src, int64_t len) {
-  if (act != LASER_HIP_ACT_RELU && act != LASER_HIP_ACT_TANH && act != LASER_HIP_ACT_SIGMOID)
-    return fail(LASER_HIP_E_INVALID, "act: act %d is not LASER_HIP_ACT_RELU, _TANH or _SIGMOID", act);
-  if (len < 0 || (len > 0 && (!dst || !src))) return fail(LASER_HIP_E_INVALID, "act: bad argument");
-  if (int rc = ensure_init()) return rc;
-  if (len == 0) return LASER_HIP_OK;
-  HostCall hc;
-  if (hc.rc) return hc.rc;
-  void *d_buf;
-  if (int rc = scratch_get(0, (size_t)len * sizeof(float), &d_buf)) return rc;
-  HIP_TRY(hipMemcpy(d_buf, src, (size_t)len * sizeof(float), hipMemcpyHostToDevice));
-  const int64_t stride = 1;
-  HIP_TRY(launch_act_f32(act, (float *)d_buf, &stride, (const float *)d_buf, &stride, &len, 1, nullptr));
-  HIP_TRY(hipMemcpy(dst, d_buf, (size_t)len * sizeof(float), hipMemcpyDeviceToHost));
-  return LASER_HIP_OK;
+  if (int rc = act_code_check("act", act)) return rc;
+  return unary_host("act", dst, src, len, [act](auto... a) { return launch_act_f32(act, a...); });
 }
 int laser_hip_act_grad_f32_dev(int act, float *dx, const int64_t *dxs, const float *dy, const int64_t *dys, const float *y,
                                const int64_t *ys, const int64_t *shape, int rank, void *stream) {
+  if (int rc = act_code_check("act_grad", act)) return rc;
   const int64_t *st[3] = {dxs, dys, ys};
   int64_t total;
-  if (int rc = act_check("act_grad", act, 2, st, shape, rank, &total)) return rc;
+  if (int rc = pointwise_check("act_grad", 1, 3, st, shape, rank, &total)) return rc;
   if (int rc = ensure_init()) return rc;
   if (total == 0) return LASER_HIP_OK;
   if (!dx || !dy || !y) return fail(LASER_HIP_E_INVALID, "act_grad: null buffer");
@@ -1525,46 +1491,19 @@ int laser_hip_act_grad_f32_dev(int act, float *dx, const int64_t *dxs, const flo
   return LASER_HIP_OK;
 }
 // ---- lsin, lcos and both at once (sincos_core.h, sincos.hip) ---------------------------------------------------------------------
-// the checks of the activation entry points; strides[0 .. ndst - 1] are destinations
-static int sincos_check(const char *what, int ndst, int nops, const int64_t *const *strides, const int64_t *shape, int rank, int64_t *total) {
-  if (rank < 0 || rank > kMaxRank) return fail(LASER_HIP_E_INVALID, "%s: rank %d outside 0..%d (LASER_MAXRANK)", what, rank, kMaxRank);
-  if (rank > 0 && !shape) return fail(LASER_HIP_E_INVALID, "%s: null shape / strides", what);
-  for (int i = 0; i < nops && rank > 0; i++)
-    if (!strides[i]) return fail(LASER_HIP_E_INVALID, "%s: null shape / strides", what);
-  *total = 1;
-  for (int d = 0; d < rank; d++) {
-    if (shape[d] < 0) return fail(LASER_HIP_E_INVALID, "%s: negative extent", what);
-    for (int i = 0; i < ndst; i++)
-      if (shape[d] > 1 && strides[i][d] == 0) return fail(LASER_HIP_E_INVALID, "%s: stride 0 on a destination (dimension %d)", what, d);
-    *total *= shape[d];
-  }
-  return LASER_HIP_OK;
-}
-static int sin_or_cos_dev(bool cosine, float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
-                          void *stream) {
-  const char *what = cosine ? "cos" : "sin";
-  const int64_t *st[2] = {ds, ss};
-  int64_t total;
-  if (int rc = sincos_check(what, 1, 2, st, shape, rank, &total)) return rc;
-  if (int rc = ensure_init()) return rc;
-  if (total == 0) return LASER_HIP_OK;
-  if (!dst || !src) return fail(LASER_HIP_E_INVALID, "%s: null buffer", what);
-  HIP_TRY((cosine ? launch_cos_f32 : launch_sin_f32)(dst, ds, src, ss, shape, rank, (hipStream_t)stream));
-  return LASER_HIP_OK;
-}
 int laser_hip_sin_f32_dev(float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
                           void *stream) {
-  return sin_or_cos_dev(false, dst, ds, src, ss, shape, rank, stream);
+  return unary_dev("sin", dst, ds, src, ss, shape, rank, stream, launch_sin_f32);
 }
 int laser_hip_cos_f32_dev(float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
                           void *stream) {
-  return sin_or_cos_dev(true, dst, ds, src, ss, shape, rank, stream);
+  return unary_dev("cos", dst, ds, src, ss, shape, rank, stream, launch_cos_f32);
 }
 int laser_hip_sincos_f32_dev(float *sin_dst, const int64_t *sin_strides, float *cos_dst, const int64_t *cos_strides, const float *src,
                              const int64_t *ss, const int64_t *shape, int rank, void *stream) {
   const int64_t *st[3] = {sin_strides, cos_strides, ss};
   int64_t total;
-  if (int rc = sincos_check("sincos", 2, 3, st, shape, rank, &total)) return rc;
+  if (int rc = pointwise_check("sincos", 2, 3, st, shape, rank, &total)) return rc;
   if (int rc = ensure_init()) return rc;
   if (total == 0) return LASER_HIP_OK;
   if (!sin_dst || !cos_dst || !src) return fail(LASER_HIP_E_INVALID, "sincos: null buffer");
@@ -1572,23 +1511,8 @@ int laser_hip_sincos_f32_dev(float *sin_dst, const int64_t *sin_strides, float *
   HIP_TRY(launch_sincos_f32(sin_dst, sin_strides, cos_dst, cos_strides, src, ss, shape, rank, (hipStream_t)stream));
   return LASER_HIP_OK;
 }
-// the host-pointer forms: through device scratch, in place there, synchronous; the same kernels as the _dev forms
-static int sin_or_cos_host(bool cosine, float *dst, const float *src, int64_t len) {
-  if (len < 0 || (len > 0 && (!dst || !src))) return fail(LASER_HIP_E_INVALID, "%s: bad argument", cosine ? "cos" : "sin");
-  if (int rc = ensure_init()) return rc;
-  if (len == 0) return LASER_HIP_OK;
-  HostCall hc;
-  if (hc.rc) return hc.rc;
-  void *d_buf;
-  if (int rc = scratch_get(0, (size_t)len * sizeof(float), &d_buf)) return rc;
-  HIP_TRY(hipMemcpy(d_buf, src, (size_t)len * sizeof(float), hipMemcpyHostToDevice));
-  const int64_t stride = 1;
-  HIP_TRY((cosine ? launch_cos_f32 : launch_sin_f32)((float *)d_buf, &stride, (const float *)d_buf, &stride, &len, 1, nullptr));
-  HIP_TRY(hipMemcpy(dst, d_buf, (size_t)len * sizeof(float), hipMemcpyDeviceToHost));
-  return LASER_HIP_OK;
-}
-int laser_hip_sin_f32(float *dst, const float *src, int64_t len) { return sin_or_cos_host(false, dst, src, len); }
-int laser_hip_cos_f32(float *dst, const float *src, int64_t len) { return sin_or_cos_host(true, dst, src, len); }
+int laser_hip_sin_f32(float *dst, const float *src, int64_t len) { return unary_host("sin", dst, src, len, launch_sin_f32); }
+int laser_hip_cos_f32(float *dst, const float *src, int64_t len) { return unary_host("cos", dst, src, len, launch_cos_f32); }
 // the checks the three row entry points share, in the order of the softmax entry point
 static int rows_check(const char *what, int64_t src_row_stride, int64_t rows, int64_t n) {
   if (n < 1 || n > LASER_HIP_SOFTMAX_MAX_N) return fail(LASER_HIP_E_INVALID, "%s: row length %lld outside 1..2^26", what, (long long)n);

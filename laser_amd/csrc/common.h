@@ -225,7 +225,8 @@ typedef std::function<hipError_t(int64_t blocks, void *dst)> ReduceLevel0;
 typedef std::function<hipError_t(const void *in, int64_t count, int64_t blocks, void *dst)> ReducePartials;
 hipError_t reduce_levels(int64_t n, int e0, int acc_size, void *out, hipStream_t s, const ReduceLevel0 &level0,
                          const ReducePartials &partials);
-// lexp over strided views and the deterministic row softmax (exp_softmax.hip; exp_core.h is the definition of lexp)
+// lexp over strided views (exp_softmax.hip; exp_core.h is the definition of lexp) and the deterministic row softmax (the kSm
+// ending of log_softmax.hip's row kernels)
 hipError_t launch_exp_f32(float *dst, const int64_t *dstrides, const float *src, const int64_t *sstrides, const int64_t *shape,
                           int rank, hipStream_t s);
 hipError_t launch_softmax_rows_f32(float *dst, int64_t dstride, const float *src, int64_t sstride, int64_t rows, int64_t n,

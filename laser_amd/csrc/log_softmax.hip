@@ -1,22 +1,29 @@
-// laser_amd/csrc/log_softmax.hip -- llog over strided device views, and the row kernels that take logits to a loss:
-// logsumexp, log-softmax and the softmax cross-entropy with integer labels (include/laser_hip.h, "log, logsumexp,
-// log-softmax and cross-entropy").
+// laser_amd/csrc/log_softmax.hip -- llog over strided device views, and the row kernels: the deterministic row softmax
+// (include/laser_hip.h, "exp and row softmax") and what takes logits to a loss, logsumexp, log-softmax and the softmax
+// cross-entropy with integer labels (include/laser_hip.h, "log, logsumexp, log-softmax and cross-entropy").
 //
-// llog is log_core.h's.  For a row, m and s are exactly the row softmax's (exp_softmax.hip): m = the maximum under
-// lh_reduce_max, s = the sum of lexp(x[j] - m) in reduce_core.h's order applied to the row as a 1-D array of n float32, so
-// every result is a function of the row's values, n (and the label) alone.  The lane mappings are the softmax's three, chosen
-// by n alone (softmax_rows_plan.h), each with a 16-byte-vector and a single-element instance; only the endings differ:
+// llog is log_core.h's, lexp exp_core.h's.  For a row, m = the maximum under lh_reduce_max and s = the sum of lexp(x[j] - m)
+// in reduce_core.h's order applied to the row as a 1-D array of n float32 (E = 4, W = 256 lanes, R = 8 steps, init +0), so
+// every result is a function of the row's values, n (and the label) alone.  Three lane mappings, chosen by n alone
+// (softmax_rows_plan.h), each with a 16-byte-vector instance (row bases 16-byte aligned) and a single-element one: same
+// values, same order.  Only the endings differ:
 //   kLse   per_row[row] = m + llog(s)                          (m = +-Inf: m itself)
 //   kLsm   y[j] = (x[j] - m) - llog(s)                         two separately rounded subtractions
 //   kXent  loss = llog(s) - (x[label] - m),  grad[j] = (lexp(x[j] - m) / s - [j == label]) * scale;  either may be absent.
 //          label -1: +0 everywhere; any other label outside [0, n): NaN everywhere
+//   kSm    y[j] = lexp(x[j] - m) / s                           the softmax; the division is __fdiv_rn
 // s >= 1 (the maximal element adds lexp(0) = 1), so llog(s) >= 0 with no cancellation.
-//   log_vec_kernel / log_strided_kernel   the elementwise llog, the shapes of exp_vec_kernel / exp_strided_kernel; no table
-//                                         in LDS: llog's 256 bytes of constants stay in two cache lines
-//   rows_wave_kernel    n <= 1024: one wave per row, four rows per workgroup, the row in registers
-//   rows_block_kernel   n <= 8192: one workgroup per row, the row in registers
-//   rows_long_kernel    longer rows: max pass, chunk partials of the sum in LDS, then (kLsm, kXent with grad) one more pass.
-//                       LDS as softmax_long_kernel: 4 KiB table + 1 KiB fold scratch + 32 KiB partials
+//   LogOp               the elementwise llog as an Op of pointwise.h, which holds the kernels, the grid and the vector choice;
+//                       no table in LDS: llog's 256 bytes of constants stay in two cache lines
+//   rows_wave_kernel    n <= 1024: one wave per row, four rows per workgroup.  Lane l holds the order's lanes l, l + 64,
+//                       l + 128, l + 192 (four elements each), folds lanes 128 and 64 apart in registers and the rest with
+//                       cross-lane moves; the row never leaves the registers.
+//   rows_block_kernel   n <= 8192 (one chunk): one workgroup per row, lane t = the order's lane t, 8 steps x 4 elements in
+//                       registers between the passes; the lane fold goes through LDS.
+//   rows_long_kernel    longer rows: one workgroup walks the row's chunks: the maximum, the chunk partials of the sum (folded
+//                       by the same rule from LDS), then (kLsm, kSm, kXent with grad) once more for the results.
+//                       LDS: 4 KiB table + 1 KiB fold scratch + 32 KiB partials
+// Every kernel copies the 4 KiB table of lexp into LDS once per workgroup and gathers from there (exp_softmax.hip says why).
 // No workgroup waits on another; no atomics, no flags.
 #include <hip/hip_runtime.h>
 
@@ -25,6 +32,7 @@
 #include "../../include/laser_hip.h"
 #include "common.h"
 #include "log_core.h"
+#include "pointwise.h"
 #include "softmax_common.h"
 #include "softmax_rows_plan.h"
 
@@ -37,45 +45,12 @@ namespace laser_hip {
 namespace {
 
 // ---- log ----------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) log_vec_kernel(float *dst, const float *src, const long long n) {
-  const long long nvec = n / 4, step = (long long)gridDim.x * 256;
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  for (long long v = gid; v < nvec; v += step) {
-    F4 x = ((const F4 *)src)[v];
-#pragma unroll
-    for (int j = 0; j < 4; j++) x.v[j] = lh_log(x.v[j]);
-    ((F4 *)dst)[v] = x;
-  }
-  const long long t = nvec * 4 + gid;  // the last n % 4 elements
-  if (t < n) dst[t] = lh_log(src[t]);
-}
-
-struct LogArgs {
-  float *dst;
-  const float *src;
-  long long n, rank;
-  long long shape[kMaxRank], sd[kMaxRank], ss[kMaxRank];  // merged extents and element strides
+struct LogOp : PointwiseOp<1, 1> {
+  __device__ __forceinline__ void apply(const float (&x)[1], float (&y)[1]) const { y[0] = lh_log(x[0]); }
 };
 
-__global__ void __launch_bounds__(256) log_strided_kernel(const LogArgs a) {
-  const long long step = (long long)gridDim.x * 256;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += step) {
-    long long rem = i, od = 0, os = 0;
-#pragma unroll
-    for (int d = kMaxRank - 1; d >= 0; d--) {
-      if (d < a.rank) {
-        const long long q = d ? rem / a.shape[d] : 0, idx = rem - q * a.shape[d];
-        od += idx * a.sd[d];
-        os += idx * a.ss[d];
-        rem = q;
-      }
-    }
-    a.dst[od] = lh_log(a.src[os]);
-  }
-}
-
 // ---- the row kernels ----------------------------------------------------------------------------------------------------
-enum { kLse = 0, kLsm = 1, kXent = 2 };
+enum { kLse = 0, kLsm = 1, kXent = 2, kSm = 3 };
 
 struct RowArgs {
   float *row_out;  // kLsm: y; kXent: grad or null
@@ -158,6 +133,8 @@ __global__ void __launch_bounds__(256) rows_wave_kernel(const RowArgs a) {
       for (int j = 0; j < 4; j++) {
         if (OP == kLsm) {
           e[k][j] = e[k][j] - l;
+        } else if (OP == kSm) {
+          e[k][j] = __fdiv_rn(e[k][j], s);
         } else {
           const float g = __fdiv_rn(e[k][j], s) - (k * 256 + lane * 4 + j == lab ? 1.0f : 0.0f);
           e[k][j] = g * a.scale;
@@ -176,7 +153,7 @@ __global__ void __launch_bounds__(256) rows_block_kernel(const RowArgs a) {
   unsigned int *lut = (unsigned int *)lut4;
   lut_to_lds(lut);
   const int t = threadIdx.x;
-  const int n = (int)a.n;
+  const long long n = a.n;  // (64-bit as load4 / store4 take it: 13 to 26 fewer registers than an int in the kLse and kSm instances)
   const float ninf = -__builtin_inff();
   for (long long row = blockIdx.x; row < a.rows; row += gridDim.x) {
     const float *x = a.src + row * a.sstride;
@@ -219,6 +196,8 @@ __global__ void __launch_bounds__(256) rows_block_kernel(const RowArgs a) {
       for (int j = 0; j < 4; j++) {
         if (OP == kLsm) {
           e[r][j] = e[r][j] - l;
+        } else if (OP == kSm) {
+          e[r][j] = __fdiv_rn(e[r][j], s);
         } else {
           const float g = __fdiv_rn(e[r][j], s) - (r * 1024 + t * 4 + j == lab ? 1.0f : 0.0f);
           e[r][j] = g * a.scale;
@@ -297,6 +276,8 @@ __global__ void __launch_bounds__(256) rows_long_kernel(const RowArgs a) {
         const float d = q[j] - m;
         if (OP == kLsm) {
           q[j] = d - l;
+        } else if (OP == kSm) {
+          q[j] = __fdiv_rn(lh_exp_with(d, lut), s);
         } else {
           const float g = __fdiv_rn(lh_exp_with(d, lut), s) - (base + j == lab ? 1.0f : 0.0f);
           q[j] = g * a.scale;
@@ -307,8 +288,9 @@ __global__ void __launch_bounds__(256) rows_long_kernel(const RowArgs a) {
   }
 }
 
+// `code`: where the plan's kernel code goes once the launch is made (null: nowhere)
 template <int OP>
-hipError_t launch_rows(const RowArgs &a, const bool vec, hipStream_t s) {
+hipError_t launch_rows(const RowArgs &a, const bool vec, hipStream_t s, int *code = nullptr) {
   if (a.rows == 0) return hipSuccess;
   long long p[3];
   if (lh_softmax_rows_plan(a.rows, a.n, vec ? 1 : 0, p) != 0) return hipErrorInvalidValue;
@@ -328,44 +310,34 @@ hipError_t launch_rows(const RowArgs &a, const bool vec, hipStream_t s) {
     default:
       return hipErrorInvalidValue;
   }
-  return hipGetLastError();
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess && code) *code = (int)p[0];
+  return e;
 }
 
-// the alignment rule of launch_softmax_rows_f32, over the row operands a call has
+// 16-byte vectors need every row operand of a call to pass this
 bool rows_aligned(const void *p, int64_t stride, int64_t rows) { return (uintptr_t)p % 16 == 0 && (rows == 1 || stride % 4 == 0); }
 
 }  // namespace
 
 hipError_t launch_log_f32(float *dst, const int64_t *dstrides, const float *src, const int64_t *sstrides, const int64_t *shape,
                           int rank, hipStream_t s) {
-  int64_t both[2 * kMaxRank], st[2][kMaxRank] = {}, sh[kMaxRank] = {};
-  int64_t n = 1;
-  for (int d = 0; d < rank; d++) {
-    both[d] = dstrides[d];
-    both[rank + d] = sstrides[d];
-    n *= shape[d];
-  }
-  if (n == 0) return hipSuccess;
-  const int r = merge_dims(2, both, shape, rank, st, sh);
-  const bool contiguous = r == 1 && st[0][0] == 1 && st[1][0] == 1;
-  if (contiguous && (uintptr_t)dst % 16 == 0 && (uintptr_t)src % 16 == 0) {
-    const int64_t blocks = std::min<int64_t>(kMaxBlocks, std::max<int64_t>(1, (n / 4 + 255) / 256));
-    hipLaunchKernelGGL(log_vec_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dst, src, (long long)n);
-    return hipGetLastError();
-  }
-  LogArgs a = {};
-  a.dst = dst;
+  return launch_pointwise<LogOp>({dst}, {dstrides}, {src}, {sstrides}, shape, rank, s);
+}
+
+hipError_t launch_softmax_rows_f32(float *dst, int64_t dstride, const float *src, int64_t sstride, int64_t rows, int64_t n,
+                                   hipStream_t s) {
+  RowArgs a = {};
+  a.row_out = dst;
+  a.ostride = dstride;
   a.src = src;
+  a.sstride = sstride;
+  a.rows = rows;
   a.n = n;
-  a.rank = r;
-  for (int d = 0; d < r; d++) {
-    a.shape[d] = sh[d];
-    a.sd[d] = st[0][d];
-    a.ss[d] = st[1][d];
-  }
-  const int64_t blocks = std::min<int64_t>(kMaxBlocks, (n + 255) / 256);
-  hipLaunchKernelGGL(log_strided_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
-  return hipGetLastError();
+  int code = -1;
+  const hipError_t e = launch_rows<kSm>(a, rows_aligned(src, sstride, rows) && rows_aligned(dst, dstride, rows), s, &code);
+  if (code >= 0) g_last_softmax_kernel = code;  // (option "last_softmax_kernel")
+  return e;
 }
 
 hipError_t launch_logsumexp_rows_f32(float *dst, int64_t dstride, const float *src, int64_t sstride, int64_t rows, int64_t n,

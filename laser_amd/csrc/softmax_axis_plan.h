@@ -1,5 +1,5 @@
 // laser_amd/csrc/softmax_axis_plan.h -- which kernel laser_hip_softmax_axis_f32_dev launches for a shape, with what strip
-// width, grid and LDS (include/laser_hip.h "exp and row softmax"; the kernels are in softmax_axis.hip and exp_softmax.hip).
+// width, grid and LDS (include/laser_hip.h "exp and row softmax"; the kernels are in softmax_axis.hip and log_softmax.hip).
 // Plain C++ with no includes and no HIP: the library's launcher and a host program read the same function.
 //
 // The operand is (outer, n, inner) with the softmax along n.  inner == 1 is the row case (codes 0 .. 2 of the row kernels,

@@ -1,6 +1,7 @@
-// laser_amd/csrc/softmax_common.h -- what the row kernels (exp_softmax.hip) and the column-strip kernels (softmax_axis.hip)
-// share: the 16-byte vector types, the table copy into LDS, the bounded 4-element loads and stores, the order-free maximum
-// and the folds of reduce_core.h's order over the 256 lanes of a workgroup.  Device code only; every function is inlined.
+// laser_amd/csrc/softmax_common.h -- what the row kernels (log_softmax.hip), the column-strip kernels
+// (softmax_axis.hip) and the elementwise template (pointwise.h: the vector types, the workgroup cap, the table copy) share:
+// the 16-byte vector types, the table copy into LDS, the bounded 4-element loads and stores, the order-free maximum and the
+// folds of reduce_core.h's order over the 256 lanes of a workgroup.  Device code only; every function is inlined.
 #ifndef LASER_HIP_SOFTMAX_COMMON_H
 #define LASER_HIP_SOFTMAX_COMMON_H
 

@@ -1,8 +1,8 @@
-// laser_amd/csrc/softmax_rows_plan.h -- which kernel the row launchers of log_softmax.hip (logsumexp, log-softmax, softmax
-// cross-entropy) start for a shape, with what grid and LDS (include/laser_hip.h "log, logsumexp, log-softmax and
+// laser_amd/csrc/softmax_rows_plan.h -- which kernel the row launchers of log_softmax.hip (softmax, logsumexp, log-softmax,
+// softmax cross-entropy) start for a shape, with what grid and LDS (include/laser_hip.h "log, logsumexp, log-softmax and
 // cross-entropy").  Plain C++ with no includes and no HIP: the library's launchers and a host program read the same function.
 //
-// The three lane mappings are those of the row softmax (exp_softmax.hip), chosen by n alone:
+// Three lane mappings, chosen by n alone:
 //   0  n <= 1024: one wave per row, four rows per workgroup of 256 lanes
 //   1  n <= 8192 (one chunk of the order): one workgroup per row, the row in registers
 //   2  longer rows, n <= 2^26: one workgroup streams the row, chunk partials in LDS

@@ -43,9 +43,27 @@ def _f32(name, obj):
     return v
 
 
-def _elementwise(fn, t, out, lead=()):
-    """`lead`: arguments of the entry point before its operands (the activation code)"""
-    if isinstance(t, np.ndarray):   # the host-pointer form: contiguous float32, synchronous
+def _elementwise(fn, outs, ins, lead=()):
+    """laser_hip_{fn}_f32_dev over device operands: `outs` and `ins` are tuples of (name, operand).  The inputs broadcast
+    against the outputs; an output given as None is a fresh Tensor of the inputs' broadcast shape.  `lead`: arguments of the
+    entry point before its operands (the activation code).  Returns the outputs as a tuple."""
+    src = [_f32(name, obj) for name, obj in ins]
+    fresh = lambda: newTensor(np.float32, *np.broadcast_shapes(*(v.shape for v in src)))
+    outs = [(name, fresh() if obj is None else obj) for name, obj in outs]
+    dst = [_f32(name, obj) for name, obj in outs]
+    if any(d.shape != dst[0].shape for d in dst):
+        raise ValueError(f"{fn}: the two destinations have shapes {dst[0].shape} and {dst[1].shape}")
+    shape, r = dst[0].shape, dst[0].rank
+    arr = lambda v: (C.c_int64 * max(r, 1))(*v)
+    ops = [a for d in dst for a in (C.c_void_p(d.ptr), arr(d.strides))]
+    ops += [a for v in src for a in (C.c_void_p(v.ptr), arr(_bcast_strides(v, shape)))]
+    _lib.check(getattr(_lib.lib(), f"laser_hip_{fn}_f32_dev")(*lead, *ops, arr(shape), r, _stream()))
+    return tuple(obj for _, obj in outs)
+
+
+def _unary(fn, t, out, lead=()):
+    """one input, one output; a host array goes through the host-pointer form: contiguous float32, synchronous"""
+    if isinstance(t, np.ndarray):
         if t.dtype != np.float32:
             raise TypeError(f"host arrays: float32 only (got {t.dtype})")
         if out is not None:
@@ -54,27 +72,19 @@ def _elementwise(fn, t, out, lead=()):
         r = np.empty_like(a)
         _lib.check(getattr(_lib.lib(), f"laser_hip_{fn}_f32")(*lead, r.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), a.size))
         return r
-    src = _f32("t", t)
-    if out is None:
-        out = newTensor(np.float32, *src.shape)
-    dst = _f32("out", out)
-    r = dst.rank
-    arr = lambda v: (C.c_int64 * max(r, 1))(*v)
-    _lib.check(getattr(_lib.lib(), f"laser_hip_{fn}_f32_dev")(*lead, C.c_void_p(dst.ptr), arr(dst.strides), C.c_void_p(src.ptr),
-                                                              arr(_bcast_strides(src, dst.shape)), arr(dst.shape), r, _stream()))
-    return out
+    return _elementwise(fn, (("out", out),), (("t", t),), lead)[0]
 
 
 def exp(t, out=None):
     """lexp(t), elementwise.  `t` broadcasts against `out` like numpy; out=None: a fresh Tensor of t's shape."""
-    return _elementwise("exp", t, out)
+    return _unary("exp", t, out)
 
 
 def log(t, out=None):
     """llog(t), elementwise: the natural logarithm of laser_amd/csrc/log_core.h, faithful (error below one ulp) and monotone
     over every positive float32; +-0 gives -Inf, a negative value NaN, a subnormal is taken as the number it is.  Operands
     as `exp`: a device tensor (`t` broadcasts against `out`) or a host float32 array."""
-    return _elementwise("log", t, out)
+    return _unary("log", t, out)
 
 
 _ACT_CODES = {"relu": 1, "tanh": 2, "sigmoid": 3}      # LASER_HIP_ACT_RELU / _TANH / _SIGMOID
@@ -91,7 +101,7 @@ def activation(t, kind, out=None):
     fused GEMM / conv epilogue (NaN and -0 give +0); ltanh and lsigmoid are laser_amd/csrc/act_core.h's: faithful, monotone,
     ltanh odd bit for bit, lsigmoid(0) = 0.5.  Operands as `exp`: a device tensor or view (`t` broadcasts against `out`, `out`
     may be `t`) or a host float32 array."""
-    return _elementwise("act", t, out, (_act_code(kind),))
+    return _unary("act", t, out, (_act_code(kind),))
 
 
 def tanh(t, out=None):
@@ -109,46 +119,26 @@ def activation_grad(dy, y, kind, out=None):
     tanh t = y * y, u = 1 - t, dy * u; sigmoid u = 1 - y, v = y * u, dy * v -- float32 operations rounded one by one.  `dy`
     and `y` are device tensors or views and broadcast against `out`; out=None: a fresh Tensor of their broadcast shape; `out`
     may be `dy` or `y`."""
-    code = _act_code(kind)
-    g, o = _f32("dy", dy), _f32("y", y)
-    if out is None:
-        out = newTensor(np.float32, *np.broadcast_shapes(g.shape, o.shape))
-    dst = _f32("out", out)
-    r = dst.rank
-    arr = lambda v: (C.c_int64 * max(r, 1))(*v)
-    _lib.check(_lib.lib().laser_hip_act_grad_f32_dev(code, C.c_void_p(dst.ptr), arr(dst.strides), C.c_void_p(g.ptr),
-                                                     arr(_bcast_strides(g, dst.shape)), C.c_void_p(o.ptr),
-                                                     arr(_bcast_strides(o, dst.shape)), arr(dst.shape), r, _stream()))
-    return out
+    return _elementwise("act_grad", (("out", out),), (("dy", dy), ("y", y)), (_act_code(kind),))[0]
 
 
 def sin(t, out=None):
     """lsin(t), elementwise: the bit-defined float32 sine of laser_amd/csrc/sincos_core.h -- faithful for every finite input,
     odd bit for bit, lsin(x) = x for tiny and subnormal x, NaN (bits 0x7fc00000) for NaN and +-Inf.  Operands as `exp`: a
     device tensor or view (`t` broadcasts against `out`, `out` may be `t`) or a host float32 array."""
-    return _elementwise("sin", t, out)
+    return _unary("sin", t, out)
 
 
 def cos(t, out=None):
     """lcos(t), elementwise: the bit-defined float32 cosine of the same header -- faithful, even bit for bit, 1 for tiny x"""
-    return _elementwise("cos", t, out)
+    return _unary("cos", t, out)
 
 
 def sincos(t, out=None):
     """(lsin(t), lcos(t)) of a device tensor or view from one argument reduction: the bits of sin(t) and cos(t).  out=None:
     two fresh row-major Tensors; out=(s, c): written there (either may be `t`; they must not overlap each other)"""
-    src = _f32("t", t)
-    if out is None:
-        out = (newTensor(np.float32, *src.shape), newTensor(np.float32, *src.shape))
-    s, c = out
-    ds, dc = _f32("out[0]", s), _f32("out[1]", c)
-    if ds.shape != dc.shape:
-        raise ValueError(f"sincos: the two destinations have shapes {ds.shape} and {dc.shape}")
-    r = ds.rank
-    arr = lambda v: (C.c_int64 * max(r, 1))(*v)
-    _lib.check(_lib.lib().laser_hip_sincos_f32_dev(C.c_void_p(ds.ptr), arr(ds.strides), C.c_void_p(dc.ptr), arr(dc.strides),
-                                                   C.c_void_p(src.ptr), arr(_bcast_strides(src, ds.shape)), arr(ds.shape), r, _stream()))
-    return s, c
+    s, c = (None, None) if out is None else out
+    return _elementwise("sincos", (("out[0]", s), ("out[1]", c)), (("t", t),))
 
 
 def _collapse(dims):

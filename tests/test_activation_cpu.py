@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import code_objects
 from tests import act_model as A
 from tests.test_foreach_cpu import code, disasm, spec
 
@@ -359,43 +360,21 @@ def test_precompiled_kernels_vectorise_and_the_gradients_hold_no_fused_multiply_
     bytes per lane, the gradient kernels hold float32 multiplies and adds and nothing fused (the vector ones: the strided ones
     share the same inlined rule, but their 64-bit index divisions are lowered through float fmas), the forward kernels divide
     once per element in float64 and call no device exponential"""
-    import struct
-    blob = open(SO, "rb").read()
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    found = None
-    at = blob.find(magic)
-    while at >= 0 and found is None:
-        n = struct.unpack_from("<Q", blob, at + 24)[0]
-        off = at + 32
-        for _ in range(n):
-            o, size, ts = struct.unpack_from("<QQQ", blob, off)
-            triple = blob[off + 24: off + 24 + ts]
-            off += 24 + ts
-            elf = blob[at + o: at + o + size]
-            if size and b"gfx950" in triple and b"act_grad_vec_kernel" in elf:
-                found = elf
-        at = blob.find(magic, at + 24)
-    assert found is not None, "no gfx950 code object with act_grad_vec_kernel in the library"
-    (tmp_path / "k.co").write_bytes(found)
-    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", str(tmp_path / "k.co")], check=True, capture_output=True,
-                         text=True).stdout
     seen = 0
-    for m in re.finditer(r"<(\w*act_grad_vec_kernelILi([123])E\w*)>:\n(.*?)s_endpgm", out, re.S):
+    for name, k in code_objects.kernels(b"ActGradOp", r"\w*pointwise_vec_kernelINS\w*ActGradOpILi[123]E\w*", tmp_path):
         seen += 1
-        k = m.group(3)
-        assert not re.search(FMA, k) and not re.search(r"_f64", k), m.group(1)
-        if m.group(2) != "1":
-            assert re.search(r"v_(pk_)?mul_f32", k) and re.search(r"v_(pk_)?(add|sub)_f32", k), m.group(1)
-        assert re.search(r"global_load_dwordx4", k) and re.search(r"global_store_dwordx4", k), m.group(1)
+        assert not re.search(FMA, k) and not re.search(r"_f64", k), name
+        if re.search(r"ActGradOpILi([123])E", name).group(1) != "1":
+            assert re.search(r"v_(pk_)?mul_f32", k) and re.search(r"v_(pk_)?(add|sub)_f32", k), name
+        assert re.search(r"global_load_dwordx4", k) and re.search(r"global_store_dwordx4", k), name
     assert seen == 3
     seen = 0
-    for m in re.finditer(r"<(\w*act_vec_kernelILi([123])E\w*)>:\n(.*?)s_endpgm", out, re.S):
+    for name, k in code_objects.kernels(b"ActGradOp", r"\w*pointwise_vec_kernelINS\w*ActOpILi[123]E\w*", tmp_path):
         seen += 1
-        k = m.group(3)
-        assert re.search(r"global_load_dwordx4", k) and re.search(r"global_store_dwordx4", k), m.group(1)
-        assert not re.search(r"v_exp_f32|v_(pk_)?fma_f32|v_fmac_f32|v_mad_f32|v_mac_f32", k), m.group(1)
-        if m.group(2) != "1":
-            assert len(re.findall(r"v_div_fixup_f64", k)) == 5 and re.search(r"v_mul_f64", k), m.group(1)   # 4 of a vector + the tail
+        assert re.search(r"global_load_dwordx4", k) and re.search(r"global_store_dwordx4", k), name
+        assert not re.search(r"v_exp_f32|v_(pk_)?fma_f32|v_fmac_f32|v_mad_f32|v_mac_f32", k), name
+        if re.search(r"ActOpILi([123])E", name).group(1) != "1":
+            assert len(re.findall(r"v_div_fixup_f64", k)) == 5 and re.search(r"v_mul_f64", k), name   # 4 of a vector + the tail
     assert seen == 3
 
 

@@ -12,7 +12,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-from tests import exp_model
+from tests import code_objects, exp_model
 from tests.test_foreach_cpu import code, disasm, spec
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -230,31 +230,11 @@ def test_body_with_laser_exp_compiles_without_fused_multiply_adds(L, tmp_path):
 
 
 def test_precompiled_exp_kernel_has_no_fused_multiply_adds(tmp_path):
-    """exp_vec_kernel is lexp and nothing else: multiplies, a subtract and an add per element, never an fma; it moves 16 bytes
-    per lane.  (The gfx950 code objects are cut out of the library's offload bundles.)"""
-    import struct
-    blob = open(SO, "rb").read()
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    found = None
-    at = blob.find(magic)
-    while at >= 0 and found is None:
-        n = struct.unpack_from("<Q", blob, at + 24)[0]
-        off = at + 32
-        for _ in range(n):
-            o, size, ts = struct.unpack_from("<QQQ", blob, off)
-            triple = blob[off + 24: off + 24 + ts]
-            off += 24 + ts
-            elf = blob[at + o: at + o + size]
-            if size and b"gfx950" in triple and b"exp_vec_kernel" in elf:
-                found = elf
-        at = blob.find(magic, at + 24)
-    assert found is not None, "no gfx950 code object with exp_vec_kernel in the library"
-    (tmp_path / "k.co").write_bytes(found)
-    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", str(tmp_path / "k.co")], check=True, capture_output=True,
-                         text=True).stdout
-    m = re.search(r"<\w*exp_vec_kernel\w*>:\n(.*?)s_endpgm", out, re.S)
-    assert m, "exp_vec_kernel not disassembled"
-    k = m.group(1)
+    """pointwise_vec_kernel<ExpOp> is lexp and nothing else: multiplies, a subtract and an add per element, never an fma; it
+    moves 16 bytes per lane.  (The gfx950 code objects are cut out of the library's offload bundles: tests/code_objects.py.)"""
+    found = code_objects.kernels(b"ExpOp", r"\w*pointwise_vec_kernelINS\w*ExpOp\w*", tmp_path)
+    assert len(found) == 1, "the vector instance of ExpOp not disassembled"
+    k = found[0][1]
     assert re.search(r"global_load_dwordx4", k) and re.search(r"global_store_dwordx4", k)
     assert re.search(r"v_rndne_f32", k) and re.search(r"ds_read", k)      # rounds to nearest even, gathers from LDS
     assert not re.search(r"v_(pk_)?fma|v_fmac|v_fmamk|v_fmaak|v_mad_f32|v_mac_f32", k)

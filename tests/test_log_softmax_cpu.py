@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import code_objects
 from tests import log_model as G
 from tests.test_foreach_cpu import code, disasm, spec
 
@@ -200,7 +201,7 @@ def test_plan_entry_point_and_the_launchers_use_the_header(L):
     hip = open(os.path.join(CSRC, "log_softmax.hip")).read()
     assert hip.count("lh_softmax_rows_plan(") == 1 and '#include "softmax_rows_plan.h"' in hip
     assert "atomic" not in re.sub(r"//[^\n]*", "", hip)               # no workgroup waits on another
-    # the softmax launcher and its kernels are where they were
+    # the row launchers are all in that one file: exp_softmax.hip holds the elementwise lexp alone
     assert "softmax_rows_plan" not in open(os.path.join(CSRC, "exp_softmax.hip")).read()
 
 
@@ -314,41 +315,21 @@ def test_body_with_laser_log_compiles_without_fused_multiply_adds(L, tmp_path):
 
 
 def test_precompiled_log_kernels_have_no_fused_multiply_adds(tmp_path):
-    """log_vec_kernel is llog and nothing else, 16 bytes per lane; the logsumexp and log-softmax kernels have no division, so
-    they hold no fma either (the cross-entropy's gradient divides as the softmax does: a correctly rounded division is built
-    from fmas).  The gfx950 code objects are cut out of the library's offload bundles."""
-    import struct
-    blob = open(SO, "rb").read()
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    found = None
-    at = blob.find(magic)
-    while at >= 0 and found is None:
-        n = struct.unpack_from("<Q", blob, at + 24)[0]
-        off = at + 32
-        for _ in range(n):
-            o, size, ts = struct.unpack_from("<QQQ", blob, off)
-            triple = blob[off + 24: off + 24 + ts]
-            off += 24 + ts
-            elf = blob[at + o: at + o + size]
-            if size and b"gfx950" in triple and b"log_vec_kernel" in elf:
-                found = elf
-        at = blob.find(magic, at + 24)
-    assert found is not None, "no gfx950 code object with log_vec_kernel in the library"
-    (tmp_path / "k.co").write_bytes(found)
-    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", str(tmp_path / "k.co")], check=True, capture_output=True,
-                         text=True).stdout
+    """pointwise_vec_kernel<LogOp> is llog and nothing else, 16 bytes per lane; the logsumexp and log-softmax kernels have no
+    division, so they hold no fma either (the cross-entropy's gradient divides as the softmax does: a correctly rounded
+    division is built from fmas).  The gfx950 code objects are cut out of the library's offload bundles (tests/code_objects.py)."""
     fma = r"v_(pk_)?fma|v_fmac|v_fmamk|v_fmaak|v_mad_f32|v_mac_f32"
-    m = re.search(r"<\w*log_vec_kernel\w*>:\n(.*?)s_endpgm", out, re.S)
-    assert m, "log_vec_kernel not disassembled"
-    k = m.group(1)
+    found = code_objects.kernels(b"LogOp", r"\w*pointwise_vec_kernelINS\w*LogOp\w*", tmp_path)
+    assert len(found) == 1, "the vector instance of LogOp not disassembled"
+    k = found[0][1]
     assert re.search(r"global_load_dwordx4", k) and re.search(r"global_store_dwordx4", k) and re.search(r"v_mul_f64", k)
     assert not re.search(fma, k) and not re.search(r"v_log_f32", k)
     seen = 0
-    for m in re.finditer(r"<(\w*rows_(?:wave|block|long)_kernelILb[01]ELi([012])E\w*)>:\n(.*?)s_endpgm", out, re.S):
+    for name, k in code_objects.kernels(b"LogOp", r"\w*rows_(?:wave|block|long)_kernelILb[01]ELi[012]E\w*", tmp_path):
         seen += 1
-        if m.group(2) in "01":                                           # logsumexp, log-softmax
-            assert not re.search(fma, m.group(3)), m.group(1)
-        assert re.search(r"v_mul_f64", m.group(3)) and not re.search(r"v_log_f32", m.group(3)), m.group(1)
+        if re.search(r"_kernelILb[01]ELi([012])E", name).group(1) in "01":   # logsumexp, log-softmax
+            assert not re.search(fma, k), name
+        assert re.search(r"v_mul_f64", k) and not re.search(r"v_log_f32", k), name
     assert seen == 18
 
 

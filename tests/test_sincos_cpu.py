@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import code_objects
 from tests import sincos_model as S
 from tests.test_foreach_cpu import code, disasm, spec
 
@@ -364,35 +365,14 @@ def test_the_reference_bodies_compile(L, tmp_path, body, ops):
 def test_precompiled_kernels_vectorise_and_hold_no_fused_multiply_adds(tmp_path):
     """the gfx950 code object with the sincos kernels, cut out of the library's offload bundles: the vector kernels move 16 bytes
     per lane and hold float64 multiplies and adds, nothing fused, no device trigonometry"""
-    import struct
-    blob = open(SO, "rb").read()
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    found = None
-    at = blob.find(magic)
-    while at >= 0 and found is None:
-        n = struct.unpack_from("<Q", blob, at + 24)[0]
-        off = at + 32
-        for _ in range(n):
-            o, size, ts = struct.unpack_from("<QQQ", blob, off)
-            triple = blob[off + 24: off + 24 + ts]
-            off += 24 + ts
-            elf = blob[at + o: at + o + size]
-            if size and b"gfx950" in triple and b"sincos_vec_kernel" in elf:
-                found = elf
-        at = blob.find(magic, at + 24)
-    assert found is not None, "no gfx950 code object with sincos_vec_kernel in the library"
-    (tmp_path / "k.co").write_bytes(found)
-    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", str(tmp_path / "k.co")], check=True, capture_output=True,
-                         text=True).stdout
     seen = 0
-    for m in re.finditer(r"<(\w*sincos_vec_kernelILi([012])E\w*)>:\n(.*?)s_endpgm", out, re.S):
+    for name, k in code_objects.kernels(b"SinCosOp", r"\w*pointwise_vec_kernelINS\w*SinCosOpILi[012]E\w*", tmp_path):
         seen += 1
-        k = m.group(3)
-        assert re.search(r"global_load_dwordx4", k) and re.search(r"global_store_dwordx4", k), m.group(1)
-        assert re.search(r"v_mul_f64", k) and re.search(r"v_add_f64", k) and re.search(r"v_cvt_f32_f64", k), m.group(1)
-        assert not re.search(FMA, k) and not re.search(r"v_sin_f32|v_cos_f32|v_div_|v_rcp_", k), m.group(1)
-        if m.group(2) == "2":
-            assert len(re.findall(r"global_store_dwordx4", k)) == 2, m.group(1)
+        assert re.search(r"global_load_dwordx4", k) and re.search(r"global_store_dwordx4", k), name
+        assert re.search(r"v_mul_f64", k) and re.search(r"v_add_f64", k) and re.search(r"v_cvt_f32_f64", k), name
+        assert not re.search(FMA, k) and not re.search(r"v_sin_f32|v_cos_f32|v_div_|v_rcp_", k), name
+        if re.search(r"SinCosOpILi([012])E", name).group(1) == "2":
+            assert len(re.findall(r"global_store_dwordx4", k)) == 2, name
     assert seen == 3
 
 
