@@ -693,6 +693,54 @@ inline Tensor<float> activation_grad(const Tensor<float> &dy, const Tensor<float
   return dx;
 }
 
+// ---- dense-layer backward (include/laser_hip.h "Dense-layer backward") over device Tensors -----------------------------------
+//   laser::bias_grad(db, &dz, dy, &y, Activation::tanh);                           (asynchronous on `stream`)
+//   auto g = laser::linear_backward(x, w, dy, &y, Activation::tanh);               g.dx, g.dw, g.db
+// dz = dy * f'(y) by activation_grad's rule (dz = dy with Activation::none, y may be null) and db[j] = reduce_sum of dz's column
+// j, from one read of dy and y.  2-D (rows, n) Tensors or views with unit column stride; dz null: only db; dz may be dy or y.
+namespace detail {
+inline int64_t grad_rows(const char *what, const Tensor<float> &t, const Tensor<float> &like) {
+  if (t.rank() != 2 || t.shape != like.shape || (t.shape[1] > 1 && t.strides[1] != 1))
+    throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": 2-D operands of one shape with unit column stride are needed").c_str());
+  return t.shape[0] > 1 ? t.strides[0] : t.shape[1];  // (the stride of a lone row is never applied)
+}
+}  // namespace detail
+inline void bias_grad(Tensor<float> &db, Tensor<float> *dz, const Tensor<float> &dy, const Tensor<float> *y, Activation act,
+                      void *stream = nullptr) {
+  const int64_t dys = detail::grad_rows("bias_grad", dy, dy), rows = dy.shape[0], n = dy.shape[1];
+  const bool has_y = act != Activation::none;
+  if (has_y && !y) throw Error(LASER_HIP_E_INVALID, "bias_grad: an activation needs the forward output y");
+  if (db.rank() != 1 || db.shape[0] != n) throw Error(LASER_HIP_E_INVALID, "bias_grad: db must be a 1-D tensor of n elements");
+  check(laser_hip_bias_grad_f32_dev(db.unsafe_raw_data(), n > 1 ? db.strides[0] : 1, dz ? dz->unsafe_raw_data() : nullptr,
+                                    dz ? detail::grad_rows("bias_grad", *dz, dy) : 0, dy.unsafe_raw_data(), dys,
+                                    has_y ? y->unsafe_raw_data() : nullptr, has_y ? detail::grad_rows("bias_grad", *y, dy) : 0, rows, n,
+                                    (int)act, stream));
+}
+struct LinearGrads {
+  Tensor<float> dx, dw, db;  // dx is empty (no storage) when it was not asked for
+};
+// the layer Y = act(X W + b), X (M, K), W (K, N): one bias_grad call, then dw = X^T dZ and dx = dZ W^T on the strided GEMM in
+// the current float mode, the transposes as strides (no operand is copied)
+inline LinearGrads linear_backward(const Tensor<float> &x, const Tensor<float> &w, const Tensor<float> &dy, const Tensor<float> *y,
+                                   Activation act, bool need_dx = true, void *stream = nullptr) {
+  if (x.rank() != 2 || w.rank() != 2 || dy.rank() != 2 || x.shape[0] != dy.shape[0] || w.shape[1] != dy.shape[1] || x.shape[1] != w.shape[0])
+    throw Error(LASER_HIP_E_INVALID, "linear_backward: x (M, K), w (K, N) and dy (M, N) are needed");
+  const int64_t M = x.shape[0], K = x.shape[1], N = w.shape[1];
+  LinearGrads g;
+  g.db = newTensor<float>({N});
+  Tensor<float> dz = newTensor<float>({M, N});
+  bias_grad(g.db, &dz, dy, y, act, stream);
+  g.dw = newTensor<float>({K, N});
+  gemm_strided_dev<float>(K, N, M, 1.0f, x.unsafe_raw_data(), x.strides[1], x.strides[0], dz.unsafe_raw_data(), dz.strides[0], dz.strides[1],
+                          0.0f, g.dw.unsafe_raw_data(), g.dw.strides[0], g.dw.strides[1], stream);
+  if (need_dx) {
+    g.dx = newTensor<float>({M, K});
+    gemm_strided_dev<float>(M, K, N, 1.0f, dz.unsafe_raw_data(), dz.strides[0], dz.strides[1], w.unsafe_raw_data(), w.strides[1], w.strides[0],
+                            0.0f, g.dx.unsafe_raw_data(), g.dx.strides[0], g.dx.strides[1], stream);
+  }
+  return g;
+}
+
 // ---- sine and cosine (include/laser_hip.h "Sine and cosine") over device Tensors -----------------------------------------------
 //   laser::sin(y, x);  laser::cos(y, x);  laser::sincos(s, c, x);   y = laser::sin(x);              (asynchronous on `stream`)
 // lsin and lcos of sincos_core.h: faithful for every finite float32, lsin odd and lcos even bit for bit, NaN for NaN and +-Inf.

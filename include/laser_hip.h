@@ -793,13 +793,57 @@ int laser_hip_softmax_rows_plan(int64_t rows, int64_t n, int vec, int64_t *out3)
  * Not built: these rules as new codes of the GEMM / conv epilogue (the float64 bodies would land in every fused-epilogue
  *   instantiation, their register and code-size cost there is unmeasured; profiles/activation/README.md has the per-element
  *   figures that decision needs); float64; softplus, log-sigmoid, binary cross-entropy, GELU and SiLU (the last two are
- *   one-line forEach bodies over the two names); bias gradients and any reduction along an axis.
+ *   one-line forEach bodies over the two names); reductions along an axis other than the bias gradient of "Dense-layer backward".
  * No gfx950 device: LASER_HIP_E_NODEVICE. */
 int laser_hip_act_f32_dev(int act, float *d_dst, const int64_t *dst_strides, const float *d_src, const int64_t *src_strides,
                           const int64_t *shape, int rank, void *stream);
 int laser_hip_act_f32(int act, float *dst, const float *src, int64_t len);
 int laser_hip_act_grad_f32_dev(int act, float *d_dx, const int64_t *dx_strides, const float *d_dy, const int64_t *dy_strides,
                                const float *d_y, const int64_t *y_strides, const int64_t *shape, int rank, void *stream);
+
+/* ---- Dense-layer backward (f32): dZ = dY (.) f'(Y) and the bias gradient in one pass ------------------------------------------
+ * For the layer Y = act(X W + b), backward propagation needs dZ = dY (.) f'(Y), db[j] = the sum of dZ[0..rows, j], dW = X^T dZ
+ * and dX = dZ W^T.  The two products run on gemm_strided (transposed views are strides); this call is the rest.
+ * laser_hip_bias_grad_f32_dev: row r of dy is the n contiguous floats at d_dy + r * dy_row_stride; y and dz are addressed the
+ *   same way (ELEMENT strides, each >= n).  `act` is LASER_HIP_ACT_NONE, _RELU, _TANH or _SIGMOID.
+ *   1. dz[r, j] = the gradient rule of "Activations" for `act` applied to (dy[r, j], y[r, j]): exactly what
+ *      laser_hip_act_grad_f32_dev gives, every float32 operation rounded on its own, never fused.  LASER_HIP_ACT_NONE:
+ *      dz = dy, and d_y is ignored and may be NULL.
+ *   2. d_db[j * db_stride] = the sum of the 1-D array dz[0..rows, j] in the order of "Reductions" applied to that column as
+ *      an array of `rows` float32 (E = 4, init +0): db[j] is reduce_sum of the column.  The sum tree in terms of the row
+ *      index r: within a chunk of 8192 rows, row k of the chunk goes to leaf a = k mod 1024; a leaf starts at +0 and takes its
+ *      up to 8 elements in ascending k; the 1024 leaves are folded by adding the higher index into the lower for index pairs
+ *      that differ in bit 1, then bit 0, then bit 9, 8, .., 2; the chunk partials (at most 8192: one chunk) are folded by the
+ *      same rule as one more such array.  rows = 0 gives db = +0; n = 0 does nothing.
+ *   d_dz may be NULL: only db is written (with LASER_HIP_ACT_NONE the call is then a plain column sum).  d_dz may equal d_dy
+ *   or d_y when the row strides are equal; no other overlap is allowed, and d_db may not overlap anything.
+ *   Valid: 0 <= rows <= LASER_HIP_BIAS_GRAD_MAX_ROWS (the chunk partials of a column fit one chunk: two levels at most),
+ *   n >= 0, any base alignment; anything else -- a row stride below n, an unknown `act`, a NULL d_db, a NULL d_dy, a NULL d_y
+ *   with an activation -- gives LASER_HIP_E_INVALID before any pointer is touched.  (A buffer that is never touched may be
+ *   NULL: all of them when n = 0, d_dy and d_y when rows = 0.)  Asynchronous on `stream`.
+ *   A column's bits depend on its own values and `rows` alone: never on n, the neighbouring columns, the strides, the base
+ *   alignment, the grid or the stream.  A NaN in a column makes that db[j] NaN and no other.
+ *   A workgroup of 256 lanes owns a (chunk of 8192 rows, strip of 16 columns) unit: 64 contiguous bytes per row, read once;
+ *   rows <= 8192 is one launch, longer columns write chunk partials to stream-ordered scratch and the same kernel folds
+ *   them: two launches.  No atomics, no workgroup waits on another.
+ * laser_hip_bias_grad_last_kernel: the plan's kernel code of the last laser_hip_bias_grad_f32_dev launch of this process:
+ *   0 = the vector instance (16-byte accesses wherever 4 columns lie inside n; bases 16-byte aligned, row strides multiples
+ *   of 4), 1 = single elements -- same bits both; -1 = none yet.  (A function of its own, not a name of laser_hip_get_option:
+ *   the option table is a recorded set.)
+ * laser_hip_bias_grad_plan: what the call above would launch for a shape, without a device: out4 = {kernel code, workgroups
+ *   of the first launch = min(2048, chunks * strips), launches, scratch floats = chunks * n when there are two launches}.
+ *   vec: 1 when bases and strides allow 16-byte vectors; cus: the device's compute units, taken for symmetry with
+ *   laser_hip_plan_f32: the plan does not depend on it.  n = 0: {code, 0, 0, 0}.  The logic is
+ *   laser_amd/csrc/bias_grad_plan.h, which has no HIP dependency.
+ * Not built: float64; f' fused into the GEMM's loader; sums along other axes or of other types, mean, argmin and argmax;
+ *   convolution backward; optimizers (forEach writes w -= lr * dw); weight layouts other than matmul's.
+ * No gfx950 device: LASER_HIP_E_NODEVICE. */
+#define LASER_HIP_BIAS_GRAD_MAX_ROWS (1ll << 26)
+int laser_hip_bias_grad_f32_dev(float *d_db, int64_t db_stride, float *d_dz, int64_t dz_row_stride, const float *d_dy,
+                                int64_t dy_row_stride, const float *d_y, int64_t y_row_stride, int64_t rows, int64_t n, int act,
+                                void *stream);
+int laser_hip_bias_grad_plan(int64_t rows, int64_t n, int vec, int cus, int64_t *out4);
+int laser_hip_bias_grad_last_kernel(void);
 
 /* ---- Sine and cosine (f32): lsin and lcos, defined bit by bit ------------------------------------------------------------
  * The reference's forEach material uses exactly these two (`o = x + y - sin z` in benchmarks/loop_iteration/iter_bench.nim,

@@ -4,12 +4,13 @@
 //   relu      y = x > 0 ? x : +0 (NaN and -0 give +0)      dx = y > 0 ? dy : +0
 //   tanh      y = ltanh(x)                                  t = y * y;  u = 1 - t;  dx = dy * u
 //   sigmoid   y = lsigmoid(x)                               u = 1 - y;  v = y * u;  dx = dy * v
-// ActOp<ACT> (one input) and ActGradOp<ACT> (dy and y) are the rules; the kernels, the grid and the vector choice are
+// ActOp<ACT> (one input) and ActGradOp<ACT> (dy and y; act_grad_core.h's lh_act_grad) are the rules; the kernels, the grid and the vector choice are
 // pointwise.h's.  No table in LDS: the 512 bytes of 2^(j/64) stay in four cache lines.
 #include <hip/hip_runtime.h>
 
 #include "../../include/laser_hip.h"
 #include "act_core.h"
+#include "act_grad_core.h"
 #include "common.h"
 #include "pointwise.h"
 
@@ -31,18 +32,7 @@ struct ActOp : PointwiseOp<1, 1> {
 template <int ACT>
 struct ActGradOp : PointwiseOp<2, 1> {
   __device__ __forceinline__ void apply(const float (&x)[2], float (&dx)[1]) const {
-    const float dy = x[0], y = x[1];
-    if (ACT == LASER_HIP_ACT_RELU) dx[0] = y > 0.0f ? dy : 0.0f;
-    if (ACT == LASER_HIP_ACT_TANH) {
-      const float t = y * y;
-      const float u = 1.0f - t;
-      dx[0] = dy * u;
-    }
-    if (ACT == LASER_HIP_ACT_SIGMOID) {
-      const float u = 1.0f - y;
-      const float v = y * u;
-      dx[0] = dy * v;
-    }
+    dx[0] = lh_act_grad<ACT>(x[0], x[1]);
   }
 };
 

@@ -27,6 +27,7 @@
 #include "random_plan.h"
 #include "sampler_plan.h"
 #include "scan_plan.h"
+#include "bias_grad_plan.h"
 #include "softmax_axis_plan.h"
 #include "softmax_rows_plan.h"
 
@@ -1488,6 +1489,39 @@ int laser_hip_act_grad_f32_dev(int act, float *dx, const int64_t *dxs, const flo
   if (total == 0) return LASER_HIP_OK;
   if (!dx || !dy || !y) return fail(LASER_HIP_E_INVALID, "act_grad: null buffer");
   HIP_TRY(launch_act_grad_f32(act, dx, dxs, dy, dys, y, ys, shape, rank, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+// ---- dense-layer backward: dz = dy * f'(y) and the bias gradient in one pass (act_grad_core.h, dense_grad.hip, bias_grad_plan.h) ---
+int laser_hip_bias_grad_f32_dev(float *db, int64_t db_stride, float *dz, int64_t dz_row_stride, const float *dy, int64_t dy_row_stride,
+                                const float *y, int64_t y_row_stride, int64_t rows, int64_t n, int act, void *stream) {
+  if (rows < 0 || n < 0 || rows > LASER_HIP_BIAS_GRAD_MAX_ROWS)
+    return fail(LASER_HIP_E_INVALID, "bias_grad: rows %lld, n %lld (0 <= rows <= 2^26, n >= 0)", (long long)rows, (long long)n);
+  if (act != LASER_HIP_ACT_NONE && act != LASER_HIP_ACT_RELU && act != LASER_HIP_ACT_TANH && act != LASER_HIP_ACT_SIGMOID)
+    return fail(LASER_HIP_E_INVALID, "bias_grad: act %d is not LASER_HIP_ACT_NONE, _RELU, _TANH or _SIGMOID", act);
+  const bool has_y = act != LASER_HIP_ACT_NONE;
+  if (dy_row_stride < n || (dz && dz_row_stride < n) || (has_y && y_row_stride < n))
+    return fail(LASER_HIP_E_INVALID, "bias_grad: row strides %lld (dz) / %lld (dy) / %lld (y) below n %lld", (long long)dz_row_stride,
+                (long long)dy_row_stride, (long long)y_row_stride, (long long)n);
+  if (dz && ((dz == dy && dz_row_stride != dy_row_stride) || (has_y && dz == y && dz_row_stride != y_row_stride)))
+    return fail(LASER_HIP_E_INVALID, "bias_grad: dz in place over dy or y needs equal row strides");
+  long long plan[4];
+  if (lh_bias_grad_plan(rows, n, 0, 0, plan) != 0)
+    return fail(LASER_HIP_E_INVALID, "bias_grad: rows %lld x n %lld is past what the chunk partials can address", (long long)rows,
+                (long long)n);
+  // (what is never touched may be null: everything when n == 0, dy and y when rows == 0)
+  if (n > 0 && (!db || (rows > 0 && (!dy || (has_y && !y))))) return fail(LASER_HIP_E_INVALID, "bias_grad: null buffer");
+  if (int rc = ensure_init()) return rc;
+  if (n == 0) return LASER_HIP_OK;
+  HIP_TRY(launch_bias_grad_f32(db, db_stride, dz, dz_row_stride, dy, dy_row_stride, y, y_row_stride, rows, n, act, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_bias_grad_last_kernel(void) { return g_last_bias_grad_kernel; }
+int laser_hip_bias_grad_plan(int64_t rows, int64_t n, int vec, int cus, int64_t *out4) {
+  if (!out4) return fail(LASER_HIP_E_INVALID, "bias_grad_plan: null out4");
+  long long p[4];
+  if (lh_bias_grad_plan(rows, n, vec, cus, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "bias_grad_plan: rows %lld, n %lld outside what bias_grad takes", (long long)rows, (long long)n);
+  for (int i = 0; i < 4; i++) out4[i] = p[i];
   return LASER_HIP_OK;
 }
 // ---- lsin, lcos and both at once (sincos_core.h, sincos.hip) ---------------------------------------------------------------------

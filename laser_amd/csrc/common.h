@@ -252,6 +252,11 @@ hipError_t launch_act_f32(int act, float *dst, const int64_t *dstrides, const fl
                           int rank, hipStream_t s);
 hipError_t launch_act_grad_f32(int act, float *dx, const int64_t *dxstrides, const float *dy, const int64_t *dystrides, const float *y,
                                const int64_t *ystrides, const int64_t *shape, int rank, hipStream_t s);
+// the backward pass of a dense layer's activation and bias (dense_grad.hip; act_grad_core.h is the rule, bias_grad_plan.h the
+// launch plan): dz = the gradient rule of (dy, y), or dy for LASER_HIP_ACT_NONE, stored unless dz is null, and db = its column sums
+hipError_t launch_bias_grad_f32(float *db, int64_t db_stride, float *dz, int64_t dz_row_stride, const float *dy, int64_t dy_row_stride,
+                                const float *y, int64_t y_row_stride, int64_t rows, int64_t n, int act, hipStream_t s);
+extern std::atomic<int> g_last_bias_grad_kernel;
 // lsin, lcos and both from one reduction over strided views (sincos.hip; sincos_core.h is the definition)
 hipError_t launch_sin_f32(float *dst, const int64_t *dstrides, const float *src, const int64_t *sstrides, const int64_t *shape, int rank,
                           hipStream_t s);

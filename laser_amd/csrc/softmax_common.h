@@ -1,5 +1,5 @@
 // laser_amd/csrc/softmax_common.h -- what the row kernels (log_softmax.hip), the column-strip kernels
-// (softmax_axis.hip) and the elementwise template (pointwise.h: the vector types, the workgroup cap, the table copy) share:
+// (softmax_axis.hip, dense_grad.hip) and the elementwise template (pointwise.h: the vector types, the workgroup cap, the table copy) share:
 // the 16-byte vector types, the table copy into LDS, the bounded 4-element loads and stores, the order-free maximum and the
 // folds of reduce_core.h's order over the 256 lanes of a workgroup.  Device code only; every function is inlined.
 #ifndef LASER_HIP_SOFTMAX_COMMON_H
@@ -90,6 +90,62 @@ __device__ __forceinline__ float block_sum(const float (&acc)[4], float *red) {
   }
   __syncthreads();
   return red[256];
+}
+
+// ---- the column-strip folds (softmax_axis.hip, dense_grad.hip): a lane owns 4 adjacent columns, CW / 4 lanes span a strip
+// row, and row lane rl = tid / (CW / 4) holds the leaves a = q * 4 RL + 4 rl + p of each of its columns
+// the order's fold over the row lanes: lane tid merges lane tid + h, h = 128, 64, .., LPR; the CW column results go to
+// out[0 .. CW) (LDS), visible to every lane on return.  red4 holds 256 vectors.
+template <int CW>
+__device__ __forceinline__ void col_fold(const float (&v)[4], F4 *red4, float *out) {
+#pragma clang fp contract(off)
+  constexpr int LPR = CW / 4;
+  const int t = threadIdx.x;
+  F4 f;
+#pragma unroll
+  for (int j = 0; j < 4; j++) f.v[j] = v[j];
+  __syncthreads();  // the last readers of red4 and of out are done
+  red4[t] = f;
+  __syncthreads();
+  if (t < 64) {
+    const F4 a = red4[t], b = red4[t + 128], c = red4[t + 64], d = red4[t + 192];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      float s = (a.v[j] + b.v[j]) + (c.v[j] + d.v[j]);
+#pragma unroll
+      for (int h = 32; h >= LPR; h /= 2) s = s + __shfl_down(s, h);
+      if (t < LPR) out[t * 4 + j] = s;
+    }
+  }
+  __syncthreads();
+}
+
+// the leaves of one lane folded inside the lane: bits 1 and 0 of the leaf index (p), then the top bits (q).  The lane holds
+// the first QU of its Q blocks of 4 leaves; the others took no element and are the order's init, +0
+template <int Q, int QU>
+__device__ __forceinline__ void lane_fold(const float (&e)[QU][4][4], float (&v)[4]) {
+#pragma clang fp contract(off)
+  float u[Q][4];
+#pragma unroll
+  for (int q = 0; q < Q; q++) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) u[q][j] = 0.0f;
+  }
+#pragma unroll
+  for (int q = 0; q < QU; q++) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) u[q][j] = (e[q][0][j] + e[q][2][j]) + (e[q][1][j] + e[q][3][j]);
+  }
+#pragma unroll
+  for (int h = Q / 2; h >= 1; h /= 2) {
+#pragma unroll
+    for (int q = 0; q < h; q++) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) u[q][j] = u[q][j] + u[q + h][j];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; j++) v[j] = u[0][j];
 }
 
 }  // namespace

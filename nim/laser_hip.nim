@@ -712,6 +712,28 @@ proc activationGrad*(kind: Activation, dx, dy, y: DevicePtr[float32], len: Natur
   var n = int64(len)
   check laser_hip_act_grad_f32_dev(cint(ord(kind)), cast[ptr float32](dx), stride.addr, cast[ptr float32](dy), stride.addr, cast[ptr float32](y), stride.addr, n.addr, 1, stream)
 
+# ---- dense-layer backward (include/laser_hip.h "Dense-layer backward"): dZ = dY * f'(Y) and the bias gradient in one pass --
+# dz by activationGrad's rule (actNone: dz = dy, y may be nil), db[j] = reduce_sum of column j of dz; row-major (rows, n)
+# device matrices with unit column stride, row strides in elements
+proc laser_hip_bias_grad_f32_dev*(db: ptr float32, dbStride: int64, dz: ptr float32, dzRowStride: int64, dy: ptr float32, dyRowStride: int64, y: ptr float32, yRowStride: int64, rows: int64, n: int64, act: cint, stream: pointer): cint {.lh, importc: "laser_hip_bias_grad_f32_dev".}
+proc laser_hip_bias_grad_plan*(rows: int64, n: int64, vec: cint, cus: cint, out4: ptr int64): cint {.lh, importc: "laser_hip_bias_grad_plan".}
+proc laser_hip_bias_grad_last_kernel*(): cint {.lh, importc: "laser_hip_bias_grad_last_kernel".}
+
+proc biasGrad*(kind: Activation, db: DevicePtr[float32], dbStride: int, dz: DevicePtr[float32], dzRowStride: int, dy: DevicePtr[float32], dyRowStride: int, y: DevicePtr[float32], yRowStride: int, rows, n: Natural, stream: pointer = nil) =
+  ## dz[r, j] = the gradient of `kind` from dy[r, j] and the forward OUTPUT y[r, j] (activationGrad's bits) and
+  ## db[j * dbStride] = the sum of dz[0 ..< rows, j] in the order of reduce_sum over that column; dz may be nil (only db),
+  ## dy or y (equal row strides); rows <= 2^26
+  check laser_hip_bias_grad_f32_dev(cast[ptr float32](db), int64(dbStride), cast[ptr float32](dz), int64(dzRowStride), cast[ptr float32](dy), int64(dyRowStride), cast[ptr float32](y), int64(yRowStride), int64(rows), int64(n), cint(ord(kind)), stream)
+
+proc linearBackward*(kind: Activation, dx, dw, db, dz: DevicePtr[float32], x, w, dy, y: DevicePtr[float32], M, K, N: Natural, stream: pointer = nil) =
+  ## the gradients of the layer Y = kind(X W + b) with row-major X (M, K), W (K, N), dY and Y (M, N): one biasGrad call writes
+  ## dz (M, N; may be dy) and db (N), then dw (K, N) = X^T dZ and dx (M, K) = dZ W^T on gemm_strided, the transposes as
+  ## strides; dx may be nil (the first layer of a network)
+  biasGrad(kind, db, 1, dz, N, dy, N, y, N, M, N, stream)
+  gemm_strided(K, N, M, 1'f32, x, 1, K, dz, N, 1, 0'f32, dw, N, 1, stream)
+  if not pointer(dx).isNil:
+    gemm_strided(M, K, N, 1'f32, dz, N, 1, w, 1, N, 0'f32, dx, K, 1, stream)
+
 # ---- sine and cosine (include/laser_hip.h "Sine and cosine"): lsin and lcos of sincos_core.h -----------------------------
 # faithful for every finite float32, lsin odd and lcos even bit for bit, lsin(x) = x for tiny x, NaN for NaN and +-Inf
 proc laser_hip_sin_f32(dst: ptr float32, src: ptr float32, len: int64): cint {.lh, importc: "laser_hip_sin_f32".}
