@@ -741,6 +741,66 @@ inline LinearGrads linear_backward(const Tensor<float> &x, const Tensor<float> &
   return g;
 }
 
+// ---- layer normalization (include/laser_hip.h "Layer normalization") over device Tensors ---------------------------------------
+//   auto f = laser::layer_norm(x, &gamma, &beta, 1e-5f);                           f.y, f.mean, f.rstd  (asynchronous on `stream`)
+//   auto g = laser::layer_norm_backward(dy, x, f.mean, f.rstd, &gamma);            g.dx, g.dgamma, g.dbeta
+// 2-D (rows, n) Tensors or views with unit column stride; gamma, beta, mean and rstd 1-D; gamma and beta may be null.
+struct LayerNormResult {
+  Tensor<float> y, mean, rstd;  // mean and rstd are empty (no storage) when they were not asked for
+};
+struct LayerNormGrads {
+  Tensor<float> dx, dgamma, dbeta;  // empty (no storage) when not asked for
+};
+namespace detail {
+inline int64_t norm_vec(const char *what, const Tensor<float> &t, int64_t count) {
+  if (t.rank() != 1 || t.shape[0] != count) throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": a 1-D tensor of the right length is needed").c_str());
+  return count > 1 ? t.strides[0] : 1;
+}
+}  // namespace detail
+// y into `y` (which may be x); mean and rstd may be null (inference)
+inline void layer_norm(Tensor<float> &y, Tensor<float> *mean, Tensor<float> *rstd, const Tensor<float> &x, const Tensor<float> *gamma,
+                       const Tensor<float> *beta, float eps = 1e-5f, void *stream = nullptr) {
+  const int64_t xs = detail::grad_rows("layer_norm", x, x), rows = x.shape[0], n = x.shape[1];
+  check(laser_hip_layer_norm_f32_dev(y.unsafe_raw_data(), detail::grad_rows("layer_norm", y, x), mean ? mean->unsafe_raw_data() : nullptr,
+                                     mean ? detail::norm_vec("layer_norm", *mean, rows) : 1, rstd ? rstd->unsafe_raw_data() : nullptr,
+                                     rstd ? detail::norm_vec("layer_norm", *rstd, rows) : 1, x.unsafe_raw_data(), xs,
+                                     gamma ? gamma->unsafe_raw_data() : nullptr, gamma ? detail::norm_vec("layer_norm", *gamma, n) : 1,
+                                     beta ? beta->unsafe_raw_data() : nullptr, beta ? detail::norm_vec("layer_norm", *beta, n) : 1, rows, n,
+                                     eps, stream));
+}
+inline LayerNormResult layer_norm(const Tensor<float> &x, const Tensor<float> *gamma, const Tensor<float> *beta, float eps = 1e-5f,
+                                  bool stats = true, void *stream = nullptr) {
+  detail::grad_rows("layer_norm", x, x);
+  LayerNormResult f;
+  f.y = newTensor<float>({x.shape[0], x.shape[1]});
+  if (stats) {
+    f.mean = newTensor<float>({x.shape[0]});
+    f.rstd = newTensor<float>({x.shape[0]});
+  }
+  layer_norm(f.y, stats ? &f.mean : nullptr, stats ? &f.rstd : nullptr, x, gamma, beta, eps, stream);
+  return f;
+}
+// dx = ((g - rsum(g) / n) - xhat * (rsum(g * xhat) / n)) * rstd with g = dy * gamma, dbeta = the column sums of dy (bias_grad's
+// bits) and dgamma those of dy * xhat; what is not asked for stays empty
+inline LayerNormGrads layer_norm_backward(const Tensor<float> &dy, const Tensor<float> &x, const Tensor<float> &mean,
+                                          const Tensor<float> &rstd, const Tensor<float> *gamma, bool need_dx = true,
+                                          bool need_params = true, void *stream = nullptr) {
+  const int64_t dys = detail::grad_rows("layer_norm_backward", dy, dy), rows = dy.shape[0], n = dy.shape[1];
+  LayerNormGrads g;
+  if (need_dx) g.dx = newTensor<float>({rows, n});
+  if (need_params) {
+    g.dgamma = newTensor<float>({n});
+    g.dbeta = newTensor<float>({n});
+  }
+  check(laser_hip_layer_norm_grad_f32_dev(need_dx ? g.dx.unsafe_raw_data() : nullptr, n, need_params ? g.dgamma.unsafe_raw_data() : nullptr, 1,
+                                          need_params ? g.dbeta.unsafe_raw_data() : nullptr, 1, dy.unsafe_raw_data(), dys,
+                                          x.unsafe_raw_data(), detail::grad_rows("layer_norm_backward", x, dy), mean.unsafe_raw_data(),
+                                          detail::norm_vec("layer_norm_backward", mean, rows), rstd.unsafe_raw_data(),
+                                          detail::norm_vec("layer_norm_backward", rstd, rows), gamma ? gamma->unsafe_raw_data() : nullptr,
+                                          gamma ? detail::norm_vec("layer_norm_backward", *gamma, n) : 1, rows, n, stream));
+  return g;
+}
+
 // ---- sine and cosine (include/laser_hip.h "Sine and cosine") over device Tensors -----------------------------------------------
 //   laser::sin(y, x);  laser::cos(y, x);  laser::sincos(s, c, x);   y = laser::sin(x);              (asynchronous on `stream`)
 // lsin and lcos of sincos_core.h: faithful for every finite float32, lsin odd and lcos even bit for bit, NaN for NaN and +-Inf.

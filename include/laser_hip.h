@@ -836,7 +836,8 @@ int laser_hip_act_grad_f32_dev(int act, float *d_dx, const int64_t *dx_strides, 
  *   laser_hip_plan_f32: the plan does not depend on it.  n = 0: {code, 0, 0, 0}.  The logic is
  *   laser_amd/csrc/bias_grad_plan.h, which has no HIP dependency.
  * Not built: float64; f' fused into the GEMM's loader; sums along other axes or of other types, mean, argmin and argmax;
- *   convolution backward; optimizers (forEach writes w -= lr * dw); weight layouts other than matmul's.
+ *   convolution backward; optimizers (forEach writes w -= lr * dw); weight layouts other than matmul's; batch and RMS
+ *   normalization (layer normalization is the next section).
  * No gfx950 device: LASER_HIP_E_NODEVICE. */
 #define LASER_HIP_BIAS_GRAD_MAX_ROWS (1ll << 26)
 int laser_hip_bias_grad_f32_dev(float *d_db, int64_t db_stride, float *d_dz, int64_t dz_row_stride, const float *d_dy,
@@ -844,6 +845,82 @@ int laser_hip_bias_grad_f32_dev(float *d_db, int64_t db_stride, float *d_dz, int
                                 void *stream);
 int laser_hip_bias_grad_plan(int64_t rows, int64_t n, int vec, int cus, int64_t *out4);
 int laser_hip_bias_grad_last_kernel(void);
+
+/* ---- Layer normalization (f32): forward and backward over the rows of a matrix, defined bit by bit --------------------------
+ * The layer between two dense layers: every row of x is shifted to mean 0, scaled to variance 1, then scaled by gamma and
+ * shifted by beta.  Every operation below is ONE float32 operation rounded on its own (+ - x, a correctly rounded division
+ * and a correctly rounded square root), never fused, and every sum is a sum of "Reductions": no polynomial, no table.
+ * Row r of x is the n contiguous floats at d_x + r * x_row_stride; y, dy and dx are addressed the same way (ELEMENT strides,
+ * each >= n); mean[r] is d_mean[r * mean_stride], gamma[j] is d_gamma[j * gamma_stride], and so on.
+ * Definitions, for a row x[0..n):  nf = (float)n;  rsum(.) = the sum of the row as a 1-D array of n float32 in the order of
+ *   "Reductions" (E = 4, init +0; elements at or past n are skipped): what reduce_sum gives for it.
+ * laser_hip_layer_norm_f32_dev, the forward pass:
+ *     mean = rsum(x) / nf
+ *     d[j] = x[j] - mean
+ *     var  = rsum(d[j] * d[j]) / nf
+ *     rstd = 1 / sqrt(var + eps)
+ *     xhat[j] = d[j] * rstd
+ *     y[j] = xhat[j] * gamma[j] + beta[j]          two roundings; d_gamma NULL: no multiply; d_beta NULL: no add
+ *   d_mean and d_rstd receive the row's statistics for the backward pass; either may be NULL (inference).  d_y may equal d_x
+ *   when the row strides are equal; no other overlap is allowed.
+ * laser_hip_layer_norm_grad_f32_dev, the backward pass, from dy, x, the saved mean and rstd, and gamma:
+ *     xhat[j] = (x[j] - mean) * rstd               the forward's bits
+ *     g[j] = dy[j] * gamma[j]                      d_gamma NULL: g = dy
+ *     a = rsum(g) / nf
+ *     b = rsum(g[j] * xhat[j]) / nf
+ *     dx[j] = ((g[j] - a) - xhat[j] * b) * rstd
+ *     dbeta[j]  = the sum over the rows of dy[r, j]
+ *     dgamma[j] = the sum over the rows of dy[r, j] * xhat[r, j]
+ *   The two column sums run in the order "Dense-layer backward" documents for db (chunks of 8192 rows, row k of a chunk to
+ *   leaf k mod 1024, and so on): dbeta has exactly the bits of laser_hip_bias_grad_f32_dev's db for dy with LASER_HIP_ACT_NONE,
+ *   and dgamma[j] those of reduce_sum of column j of the matrix dy * xhat.  rows = 0 gives dgamma = dbeta = +0.
+ *   Each of d_dx, d_dgamma and d_dbeta may be NULL (not wanted), but not all three; what is asked for has the same bits
+ *   whatever else is asked for.  d_dx may equal d_dy or d_x when the row strides are equal; no other overlap is allowed.
+ * Consequences: a row's y, mean, rstd and dx depend on that row's values, n and eps alone, and a column's dgamma and dbeta
+ *   on that column's values (with the rows' mean and rstd) and `rows` alone: never on the grid, the stream, the base
+ *   alignment or the strides.  A NaN or an Inf in one row touches no other row's y, mean, rstd or dx; in dy it does touch the
+ *   columns of dgamma and dbeta it sits in, and only those (in x it reaches every column of dgamma, through its row's xhat).  A sum starts at +0 and adds its first element, so a row of -0 has
+ *   mean +0 and xhat -0.  n = 1 gives mean = x, var = +0 and y = (0 * rstd) * gamma + beta.  eps = 0 is allowed and follows
+ *   IEEE: a constant row gives var = +0, rstd = +Inf and y = 0 * Inf = NaN.
+ * Valid: rows >= 0, 1 <= n <= LASER_HIP_LAYER_NORM_MAX_N, eps >= 0 (not NaN), any base alignment; with d_dgamma or d_dbeta
+ *   also rows <= LASER_HIP_LAYER_NORM_MAX_ROWS (the chunk partials of a column fit one chunk).  Anything else -- a row stride
+ *   below n, a stride below 1 of a statistic or parameter that is written, a NULL d_y, d_x, d_dy, d_mean or d_rstd where it is
+ *   required, in-place operands with unequal row strides, no gradient asked for -- gives LASER_HIP_E_INVALID before a device
+ *   is looked for.  (With rows = 0 nothing but dgamma and dbeta is touched and the other pointers may be NULL.)
+ *   Asynchronous on `stream`.
+ * Kernels (laser_amd/csrc/layer_norm.hip).  Forward and dx, three lane mappings chosen by n alone, as the row softmax has
+ *   them: n <= 1024 one wave per row and four rows per workgroup, n <= 8192 one workgroup per row with the row in registers,
+ *   longer rows one workgroup streaming the row's chunks (x is read once per pass: three passes forward, two backward); at
+ *   most 2048 workgroups, which stride over the rows.  Each has a 16-byte-vector instance (every row operand, gamma and beta
+ *   16-byte aligned, row strides multiples of 4, gamma and beta with unit stride) and a single-element one: same bits.
+ *   dgamma and dbeta: a workgroup owns a (chunk of 8192 rows, strip of 8 columns) unit and produces both sums from one
+ *   read of dy and x; rows <= 8192 is one launch, longer columns write chunk partials to stream-ordered scratch, which the
+ *   bias gradient's launch folds ("the partials are one more such array").  No atomics, no workgroup waits on another.
+ * laser_hip_layer_norm_plan: what the calls above would launch, without a device.  what: 0 = forward, 1 = dx, 2 = dgamma and
+ *   dbeta together.  out4 = {kernel code, workgroups of the first launch, launches, scratch bytes}.  Codes for 0 and 1:
+ *   0 / 1 / 2 = wave / workgroup / long-row mapping, + 4 for the single-element instance (vec = 0); workgroups =
+ *   min(2048, ceil(rows / 4)) for code 0 and min(2048, rows) otherwise; one launch (none for rows = 0).  For 2: code 0 = vector,
+ *   1 = single elements; workgroups = min(2048, chunks * strips); rows <= 8192: one launch; longer: three (one fold per sum)
+ *   and 2 * chunks * n * 4 scratch bytes (one sum asked for alone: one launch and one matrix fewer).  The logic is
+ *   laser_amd/csrc/layer_norm_plan.h, which has no HIP dependency.
+ * laser_hip_layer_norm_last_kernel(what): the plan's kernel code of the last launch of that kind in this process; -1 = none
+ *   yet or an unknown `what`.  (A function of its own: the option table is a recorded set.)
+ * Not built: float64; batch and RMS normalization; normalization along an axis other than the last; the normalization fused
+ *   into a GEMM prologue or epilogue; one very long row split over several workgroups (64 rows keep 64 compute units busy).
+ * No gfx950 device: LASER_HIP_E_NODEVICE. */
+#define LASER_HIP_LAYER_NORM_MAX_N (1ll << 26)
+#define LASER_HIP_LAYER_NORM_MAX_ROWS (1ll << 26)
+int laser_hip_layer_norm_f32_dev(float *d_y, int64_t y_row_stride, float *d_mean, int64_t mean_stride, float *d_rstd,
+                                 int64_t rstd_stride, const float *d_x, int64_t x_row_stride, const float *d_gamma,
+                                 int64_t gamma_stride, const float *d_beta, int64_t beta_stride, int64_t rows, int64_t n, float eps,
+                                 void *stream);
+int laser_hip_layer_norm_grad_f32_dev(float *d_dx, int64_t dx_row_stride, float *d_dgamma, int64_t dgamma_stride, float *d_dbeta,
+                                      int64_t dbeta_stride, const float *d_dy, int64_t dy_row_stride, const float *d_x,
+                                      int64_t x_row_stride, const float *d_mean, int64_t mean_stride, const float *d_rstd,
+                                      int64_t rstd_stride, const float *d_gamma, int64_t gamma_stride, int64_t rows, int64_t n,
+                                      void *stream);
+int laser_hip_layer_norm_plan(int64_t rows, int64_t n, int vec, int what, int64_t *out);
+int laser_hip_layer_norm_last_kernel(int what);
 
 /* ---- Sine and cosine (f32): lsin and lcos, defined bit by bit ------------------------------------------------------------
  * The reference's forEach material uses exactly these two (`o = x + y - sin z` in benchmarks/loop_iteration/iter_bench.nim,

@@ -28,6 +28,7 @@
 #include "sampler_plan.h"
 #include "scan_plan.h"
 #include "bias_grad_plan.h"
+#include "layer_norm_plan.h"
 #include "softmax_axis_plan.h"
 #include "softmax_rows_plan.h"
 
@@ -1524,6 +1525,62 @@ int laser_hip_bias_grad_plan(int64_t rows, int64_t n, int vec, int cus, int64_t 
   for (int i = 0; i < 4; i++) out4[i] = p[i];
   return LASER_HIP_OK;
 }
+// ---- layer normalization forward and backward (layer_norm.hip, layer_norm_plan.h) -------------------------------------------------
+int laser_hip_layer_norm_f32_dev(float *y, int64_t y_row_stride, float *mean, int64_t mean_stride, float *rstd, int64_t rstd_stride,
+                                 const float *x, int64_t x_row_stride, const float *gamma, int64_t gamma_stride, const float *beta,
+                                 int64_t beta_stride, int64_t rows, int64_t n, float eps, void *stream) {
+  if (rows < 0 || n < 1 || n > LASER_HIP_LAYER_NORM_MAX_N)
+    return fail(LASER_HIP_E_INVALID, "layer_norm: rows %lld, n %lld (rows >= 0, 1 <= n <= 2^26)", (long long)rows, (long long)n);
+  if (!(eps >= 0.0f)) return fail(LASER_HIP_E_INVALID, "layer_norm: eps %g (eps >= 0 is needed)", (double)eps);
+  if (y_row_stride < n || x_row_stride < n)
+    return fail(LASER_HIP_E_INVALID, "layer_norm: row strides %lld (y) / %lld (x) below n %lld", (long long)y_row_stride,
+                (long long)x_row_stride, (long long)n);
+  if ((mean && mean_stride < 1) || (rstd && rstd_stride < 1))
+    return fail(LASER_HIP_E_INVALID, "layer_norm: strides %lld (mean) / %lld (rstd) below 1", (long long)mean_stride, (long long)rstd_stride);
+  if (y && y == x && y_row_stride != x_row_stride) return fail(LASER_HIP_E_INVALID, "layer_norm: y in place over x needs equal row strides");
+  if (rows > 0 && (!y || !x)) return fail(LASER_HIP_E_INVALID, "layer_norm: null buffer");
+  if (int rc = ensure_init()) return rc;
+  HIP_TRY(launch_layer_norm_f32(y, y_row_stride, mean, mean_stride, rstd, rstd_stride, x, x_row_stride, gamma, gamma_stride, beta,
+                                beta_stride, rows, n, eps, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_layer_norm_grad_f32_dev(float *dx, int64_t dx_row_stride, float *dgamma, int64_t dgamma_stride, float *dbeta,
+                                      int64_t dbeta_stride, const float *dy, int64_t dy_row_stride, const float *x, int64_t x_row_stride,
+                                      const float *mean, int64_t mean_stride, const float *rstd, int64_t rstd_stride, const float *gamma,
+                                      int64_t gamma_stride, int64_t rows, int64_t n, void *stream) {
+  if (rows < 0 || n < 1 || n > LASER_HIP_LAYER_NORM_MAX_N)
+    return fail(LASER_HIP_E_INVALID, "layer_norm_grad: rows %lld, n %lld (rows >= 0, 1 <= n <= 2^26)", (long long)rows, (long long)n);
+  if (!dx && !dgamma && !dbeta) return fail(LASER_HIP_E_INVALID, "layer_norm_grad: none of dx, dgamma and dbeta is asked for");
+  if ((dgamma || dbeta) && rows > LASER_HIP_LAYER_NORM_MAX_ROWS)
+    return fail(LASER_HIP_E_INVALID, "layer_norm_grad: rows %lld with a parameter gradient (rows <= 2^26)", (long long)rows);
+  if (dy_row_stride < n || x_row_stride < n || (dx && dx_row_stride < n))
+    return fail(LASER_HIP_E_INVALID, "layer_norm_grad: row strides %lld (dx) / %lld (dy) / %lld (x) below n %lld", (long long)dx_row_stride,
+                (long long)dy_row_stride, (long long)x_row_stride, (long long)n);
+  if ((dgamma && dgamma_stride < 1) || (dbeta && dbeta_stride < 1))
+    return fail(LASER_HIP_E_INVALID, "layer_norm_grad: strides %lld (dgamma) / %lld (dbeta) below 1", (long long)dgamma_stride,
+                (long long)dbeta_stride);
+  if (dx && ((dx == dy && dx_row_stride != dy_row_stride) || (dx == x && dx_row_stride != x_row_stride)))
+    return fail(LASER_HIP_E_INVALID, "layer_norm_grad: dx in place over dy or x needs equal row strides");
+  if (rows > 0 && (!dy || !x || !mean || !rstd)) return fail(LASER_HIP_E_INVALID, "layer_norm_grad: null buffer");
+  if (int rc = ensure_init()) return rc;
+  // the column sums first: they read dy and x as they came, and dx may overwrite either
+  HIP_TRY(launch_layer_norm_param_grads_f32(dgamma, dgamma_stride, dbeta, dbeta_stride, dy, dy_row_stride, x, x_row_stride, mean,
+                                            mean_stride, rstd, rstd_stride, rows, n, (hipStream_t)stream));
+  if (dx)
+    HIP_TRY(launch_layer_norm_dx_f32(dx, dx_row_stride, dy, dy_row_stride, x, x_row_stride, mean, mean_stride, rstd, rstd_stride, gamma,
+                                     gamma_stride, rows, n, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_layer_norm_plan(int64_t rows, int64_t n, int vec, int what, int64_t *out) {
+  if (!out) return fail(LASER_HIP_E_INVALID, "layer_norm_plan: null out");
+  long long p[4];
+  if (lh_layer_norm_plan(rows, n, vec, what, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "layer_norm_plan: rows %lld, n %lld, what %d outside what layer_norm takes", (long long)rows,
+                (long long)n, what);
+  for (int i = 0; i < 4; i++) out[i] = p[i];
+  return LASER_HIP_OK;
+}
+int laser_hip_layer_norm_last_kernel(int what) { return what >= 0 && what < 3 ? (int)g_last_layer_norm_kernel[what] : -1; }
 // ---- lsin, lcos and both at once (sincos_core.h, sincos.hip) ---------------------------------------------------------------------
 int laser_hip_sin_f32_dev(float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
                           void *stream) {

@@ -257,6 +257,20 @@ hipError_t launch_act_grad_f32(int act, float *dx, const int64_t *dxstrides, con
 hipError_t launch_bias_grad_f32(float *db, int64_t db_stride, float *dz, int64_t dz_row_stride, const float *dy, int64_t dy_row_stride,
                                 const float *y, int64_t y_row_stride, int64_t rows, int64_t n, int act, hipStream_t s);
 extern std::atomic<int> g_last_bias_grad_kernel;
+// layer normalization over the rows of a matrix (layer_norm.hip; layer_norm_plan.h is the launch plan): the forward pass
+// (mean, rstd, gamma and beta may each be null), dx from the saved statistics, and the column sums dgamma and dbeta (either
+// may be null).  g_last_layer_norm_kernel[what]: the plan's kernel code of the last launch of each
+hipError_t launch_layer_norm_f32(float *y, int64_t y_row_stride, float *mean, int64_t mean_stride, float *rstd, int64_t rstd_stride,
+                                 const float *x, int64_t x_row_stride, const float *gamma, int64_t gamma_stride, const float *beta,
+                                 int64_t beta_stride, int64_t rows, int64_t n, float eps, hipStream_t s);
+hipError_t launch_layer_norm_dx_f32(float *dx, int64_t dx_row_stride, const float *dy, int64_t dy_row_stride, const float *x,
+                                    int64_t x_row_stride, const float *mean, int64_t mean_stride, const float *rstd, int64_t rstd_stride,
+                                    const float *gamma, int64_t gamma_stride, int64_t rows, int64_t n, hipStream_t s);
+hipError_t launch_layer_norm_param_grads_f32(float *dgamma, int64_t dgamma_stride, float *dbeta, int64_t dbeta_stride, const float *dy,
+                                             int64_t dy_row_stride, const float *x, int64_t x_row_stride, const float *mean,
+                                             int64_t mean_stride, const float *rstd, int64_t rstd_stride, int64_t rows, int64_t n,
+                                             hipStream_t s);
+extern std::atomic<int> g_last_layer_norm_kernel[3];
 // lsin, lcos and both from one reduction over strided views (sincos.hip; sincos_core.h is the definition)
 hipError_t launch_sin_f32(float *dst, const int64_t *dstrides, const float *src, const int64_t *sstrides, const int64_t *shape, int rank,
                           hipStream_t s);

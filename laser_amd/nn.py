@@ -6,6 +6,11 @@
     laser_amd.linear_backward(x, w, dy, y=None, activation=None, need_dx=True) -> (dx, dw, db)
         one bias_grad call, then dw = matmul(x.T, dz) and dx = matmul(dz, w.T) on the strided GEMM
 
+and layer normalization over the rows of a matrix, forward and backward (include/laser_hip.h "Layer normalization"):
+
+    laser_amd.layer_norm(x, gamma=None, beta=None, eps=1e-5, out=None, stats=True) -> (y, mean, rstd)
+    laser_amd.layer_norm_backward(dy, x, mean, rstd, gamma=None, need_dx=True, need_params=True) -> (dx, dgamma, dbeta)
+
 With matmul(..., bias=, activation=) as the forward layer, softmax_cross_entropy(grad=True) as the loss and forEach for
 `w -= lr * dw`, a multi-layer perceptron trains without leaving the device, every bit of every step defined by the headers.
 Operands are laser_amd.Tensors or torch CUDA tensors; calls are asynchronous on the current torch stream.
@@ -19,7 +24,7 @@ from .primitives import ACTIVATIONS, matmul
 from .simd_math import _f32
 from .tensor import _stream, newTensor
 
-__all__ = ["bias_grad", "linear_backward"]
+__all__ = ["bias_grad", "linear_backward", "layer_norm", "layer_norm_backward"]
 
 
 def _act(activation):
@@ -79,3 +84,116 @@ def linear_backward(x, w, dy, y=None, activation=None, need_dx=True):
     dw = matmul(x.T, dz)
     dx = matmul(dz, w.T) if need_dx else None
     return dx, dw, db
+
+
+# ---- layer normalization ------------------------------------------------------------------------------------------------------
+LAYER_NORM_MAX_N = 1 << 26
+
+
+def _ln_rows(fn, name, obj, shape=None):
+    """(view, rows, n, row stride) of a row operand: a 2-D tensor or view whose columns have unit stride, or a C-contiguous
+    tensor of higher rank, taken as (prod(leading), n)"""
+    v = _f32(name, obj)
+    if v.rank < 2:
+        raise ValueError(f"{fn}: {name} has rank {v.rank} (rows of a 2-D tensor or view, or a contiguous tensor of higher rank)")
+    if shape is not None and v.shape != shape:
+        raise ValueError(f"{fn}: {name} has shape {v.shape}, {shape} is needed")
+    n = v.shape[-1]
+    if n < 1 or n > LAYER_NORM_MAX_N:
+        raise ValueError(f"{fn}: {name} has rows of {n} elements (1 <= n <= 2^26)")
+    if v.rank == 2:
+        rows = v.shape[0]
+        if n > 1 and v.strides[1] != 1:
+            raise ValueError(f"{fn}: {name} has column stride {v.strides[1]} (1 is needed: transposed views are not taken)")
+        return v, rows, n, (v.strides[0] if rows > 1 else n)  # (the stride of a lone row is never applied)
+    rows, acc = 1, 1
+    for e, st in zip(reversed(v.shape), reversed(v.strides)):
+        if e > 1 and st != acc:
+            raise ValueError(f"{fn}: {name} of rank {v.rank} has strides {v.strides} (C-contiguous is needed above rank 2)")
+        acc *= e
+    for e in v.shape[:-1]:
+        rows *= e
+    return v, rows, n, n
+
+
+def _ln_vector(fn, name, obj, shape):
+    """(view, stride) of `count` elements, one per row or per column: a 1-D tensor or view of any stride, or a C-contiguous
+    tensor of the shape given"""
+    v = _f32(name, obj)
+    count = 1
+    for e in shape:
+        count *= e
+    if v.rank == 1 and v.shape == (count,):
+        return v, (v.strides[0] if count > 1 else 1)
+    acc = 1
+    for e, st in zip(reversed(v.shape), reversed(v.strides)):
+        if e > 1 and st != acc:
+            break
+        acc *= e
+    else:
+        if v.shape == tuple(shape):
+            return v, 1
+    raise ValueError(f"{fn}: {name} has shape {v.shape}, strides {v.strides} (({count},) or contiguous {tuple(shape)} is needed)")
+
+
+def _ptr(v):
+    return C.c_void_p(v.ptr) if v is not None and v.ptr else None
+
+
+def layer_norm(x, gamma=None, beta=None, eps=1e-5, out=None, stats=True):
+    """Every row of `x` normalized to mean 0 and variance 1, then scaled by gamma and shifted by beta, each float32 operation
+    rounded on its own and every sum in reduce_sum's order: mean = rsum(x) / n, d = x - mean, var = rsum(d * d) / n,
+    rstd = 1 / sqrt(var + eps), y = (d * rstd) * gamma + beta (no multiply without gamma, no add without beta).  `x` is a 2-D
+    (rows, n) device tensor or view with unit column stride, or a contiguous tensor of higher rank taken as
+    (prod(leading), n); `gamma` and `beta` are 1-D of n elements; `out` takes y and may be `x`.  Returns (y, mean, rstd): the
+    statistics the backward pass needs, fresh Tensors of x's leading shape, or None, None with stats=False (inference).
+    eps = 0 is allowed and follows IEEE (a constant row gives NaN)."""
+    eps = float(eps)
+    if not eps >= 0.0:
+        raise ValueError(f"layer_norm: eps = {eps!r} (eps >= 0 is needed)")
+    vx, rows, n, xs = _ln_rows("layer_norm", "x", x)
+    vg, gs = _ln_vector("layer_norm", "gamma", gamma, (n,)) if gamma is not None else (None, 1)
+    vb, bs = _ln_vector("layer_norm", "beta", beta, (n,)) if beta is not None else (None, 1)
+    if out is None:
+        out = newTensor(np.float32, *vx.shape)
+    vy, _, _, ys = _ln_rows("layer_norm", "out", out, vx.shape)
+    mean = newTensor(np.float32, *vx.shape[:-1]) if stats else None
+    rstd = newTensor(np.float32, *vx.shape[:-1]) if stats else None
+    vm = _f32("mean", mean) if stats else None
+    vr = _f32("rstd", rstd) if stats else None
+    _lib.check(_lib.lib().laser_hip_layer_norm_f32_dev(_ptr(vy), ys, _ptr(vm), 1, _ptr(vr), 1, _ptr(vx), xs, _ptr(vg), gs, _ptr(vb), bs,
+                                                       rows, n, eps, _stream()))
+    return out, mean, rstd
+
+
+def layer_norm_backward(dy, x, mean, rstd, gamma=None, need_dx=True, need_params=True):
+    """The gradients of layer_norm from the incoming gradient `dy`, the forward INPUT `x`, the saved `mean` and `rstd` and
+    `gamma`: with xhat = (x - mean) * rstd and g = dy * gamma (dy without gamma), dx = ((g - rsum(g) / n) - xhat *
+    (rsum(g * xhat) / n)) * rstd, dbeta[j] = reduce_sum(dy[:, j]) -- the bits of bias_grad(dy)[0] -- and dgamma[j] =
+    reduce_sum((dy * xhat)[:, j]).  need_dx: True for a fresh Tensor, False for none, or the destination, which may be `dy` or
+    `x`; need_params: True for both parameter gradients, False for none, "gamma" or "beta" for one alone (rows <= 2^26).
+    What is asked for has the same bits whatever else is asked for.  Returns (dx, dgamma, dbeta), None where not asked for."""
+    fn = "layer_norm_backward"
+    if need_params not in (True, False, "gamma", "beta"):
+        raise ValueError(f'{fn}: need_params = {need_params!r} (True, False, "gamma" or "beta")')
+    vdy, rows, n, dys = _ln_rows(fn, "dy", dy)
+    vx, _, _, xs = _ln_rows(fn, "x", x, vdy.shape)
+    vm, ms = _ln_vector(fn, "mean", mean, vdy.shape[:-1])
+    vr, rs = _ln_vector(fn, "rstd", rstd, vdy.shape[:-1])
+    vg, gs = _ln_vector(fn, "gamma", gamma, (n,)) if gamma is not None else (None, 1)
+    if need_dx is False:
+        dx, vdx, dxs = None, None, 0
+    else:
+        dx = newTensor(np.float32, *vdy.shape) if need_dx is True else need_dx
+        vdx, _, _, dxs = _ln_rows(fn, "dx", dx, vdy.shape)
+    dgamma = newTensor(np.float32, n) if need_params in (True, "gamma") else None
+    dbeta = newTensor(np.float32, n) if need_params in (True, "beta") else None
+    if dx is None and dgamma is None and dbeta is None:
+        raise ValueError(f"{fn}: nothing is asked for (need_dx and need_params are both False)")
+    vdg = _f32("dgamma", dgamma) if dgamma is not None else None
+    vdb = _f32("dbeta", dbeta) if dbeta is not None else None
+    if rows == 0 and vdg is None and vdb is None:
+        return dx, dgamma, dbeta  # (no rows, no column sums: nothing to compute, and an empty dx has no address to pass)
+    _lib.check(_lib.lib().laser_hip_layer_norm_grad_f32_dev(_ptr(vdx), dxs, _ptr(vdg), 1, _ptr(vdb), 1, _ptr(vdy), dys, _ptr(vx), xs,
+                                                            _ptr(vm), ms, _ptr(vr), rs, _ptr(vg), gs, rows, n, _stream()))
+    return dx, dgamma, dbeta

@@ -734,6 +734,24 @@ proc linearBackward*(kind: Activation, dx, dw, db, dz: DevicePtr[float32], x, w,
   if not pointer(dx).isNil:
     gemm_strided(M, K, N, 1'f32, dz, N, 1, w, 1, N, 0'f32, dx, K, 1, stream)
 
+# ---- layer normalization (include/laser_hip.h "Layer normalization"): forward and backward over the rows of a matrix -------
+# every float32 operation rounded on its own, every sum in reduce_sum's order; row-major (rows, n) device matrices with unit
+# column stride, strides in elements; gamma, beta, mean and rstd may be nil where the header says so
+proc laser_hip_layer_norm_f32_dev*(y: ptr float32, yRowStride: int64, mean: ptr float32, meanStride: int64, rstd: ptr float32, rstdStride: int64, x: ptr float32, xRowStride: int64, gamma: ptr float32, gammaStride: int64, beta: ptr float32, betaStride: int64, rows: int64, n: int64, eps: float32, stream: pointer): cint {.lh, importc: "laser_hip_layer_norm_f32_dev".}
+proc laser_hip_layer_norm_grad_f32_dev*(dx: ptr float32, dxRowStride: int64, dgamma: ptr float32, dgammaStride: int64, dbeta: ptr float32, dbetaStride: int64, dy: ptr float32, dyRowStride: int64, x: ptr float32, xRowStride: int64, mean: ptr float32, meanStride: int64, rstd: ptr float32, rstdStride: int64, gamma: ptr float32, gammaStride: int64, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_layer_norm_grad_f32_dev".}
+proc laser_hip_layer_norm_plan*(rows: int64, n: int64, vec: cint, what: cint, outp: ptr int64): cint {.lh, importc: "laser_hip_layer_norm_plan".}
+proc laser_hip_layer_norm_last_kernel*(what: cint): cint {.lh, importc: "laser_hip_layer_norm_last_kernel".}
+
+proc layerNorm*(y, mean, rstd: DevicePtr[float32], x, gamma, beta: DevicePtr[float32], rows, n: Natural, eps: float32 = 1e-5'f32, stream: pointer = nil) =
+  ## y[r, j] = ((x[r, j] - mean[r]) * rstd[r]) * gamma[j] + beta[j] with mean = rsum(x) / n and rstd = 1 / sqrt(var + eps) of
+  ## row r; contiguous rows; mean and rstd (the statistics layerNormBackward needs), gamma and beta may be nil; y may be x
+  check laser_hip_layer_norm_f32_dev(cast[ptr float32](y), int64(n), cast[ptr float32](mean), 1, cast[ptr float32](rstd), 1, cast[ptr float32](x), int64(n), cast[ptr float32](gamma), 1, cast[ptr float32](beta), 1, int64(rows), int64(n), eps, stream)
+
+proc layerNormBackward*(dx, dgamma, dbeta: DevicePtr[float32], dy, x, mean, rstd, gamma: DevicePtr[float32], rows, n: Natural, stream: pointer = nil) =
+  ## dx (rows, n), dgamma (n) and dbeta (n) from dy, the forward input x and the saved mean and rstd; each of the three may be
+  ## nil (not wanted) but not all; gamma may be nil; dx may be dy or x; rows <= 2^26 with a parameter gradient
+  check laser_hip_layer_norm_grad_f32_dev(cast[ptr float32](dx), int64(n), cast[ptr float32](dgamma), 1, cast[ptr float32](dbeta), 1, cast[ptr float32](dy), int64(n), cast[ptr float32](x), int64(n), cast[ptr float32](mean), 1, cast[ptr float32](rstd), 1, cast[ptr float32](gamma), 1, int64(rows), int64(n), stream)
+
 # ---- sine and cosine (include/laser_hip.h "Sine and cosine"): lsin and lcos of sincos_core.h -----------------------------
 # faithful for every finite float32, lsin odd and lcos even bit for bit, lsin(x) = x for tiny x, NaN for NaN and +-Inf
 proc laser_hip_sin_f32(dst: ptr float32, src: ptr float32, len: int64): cint {.lh, importc: "laser_hip_sin_f32".}
