@@ -801,6 +801,65 @@ inline LayerNormGrads layer_norm_backward(const Tensor<float> &dy, const Tensor<
   return g;
 }
 
+// ---- embedding (include/laser_hip.h "Embedding") over device Tensors -----------------------------------------------------------
+//   auto y = laser::embedding(w, idx);                                             y[t, :] = w[idx[t], :]  (asynchronous on `stream`)
+//   auto g = laser::embedding_group(idx, vocab);                                   g.order, g.starts
+//   auto dw = laser::embedding_backward(dy, idx, vocab, &g);                       dw[v, :] = reduce_sum over the tokens of id v
+// w and dw are 2-D (vocab, dim), y and dy 2-D (tokens, dim), Tensors or views with unit column stride; idx is 1-D int32 with
+// unit stride.  An id of -1 gives a row of +0 and no gradient, any other id outside [0, vocab) a row of NaN and no gradient.
+struct EmbeddingGroup {
+  Tensor<int32_t> order, starts;  // id v owns order[starts[v] .. starts[v + 1])
+};
+namespace detail {
+inline int64_t embedding_ids(const char *what, const Tensor<int32_t> &idx) {
+  if (idx.rank() != 1 || (idx.shape[0] > 1 && idx.strides[0] != 1))
+    throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": idx must be a 1-D int32 tensor with unit stride").c_str());
+  return idx.shape[0];
+}
+}  // namespace detail
+inline void embedding(Tensor<float> &y, const Tensor<float> &w, const Tensor<int32_t> &idx, void *stream = nullptr) {
+  const int64_t ws = detail::grad_rows("embedding", w, w), tokens = detail::embedding_ids("embedding", idx);
+  if (y.rank() != 2 || y.shape[0] != tokens || y.shape[1] != w.shape[1]) throw Error(LASER_HIP_E_INVALID, "embedding: y must be (tokens, dim)");
+  check(laser_hip_embedding_f32_dev(y.unsafe_raw_data(), detail::grad_rows("embedding", y, y), w.unsafe_raw_data(), ws, idx.unsafe_raw_data(),
+                                    tokens, w.shape[0], w.shape[1], stream));
+}
+inline Tensor<float> embedding(const Tensor<float> &w, const Tensor<int32_t> &idx, void *stream = nullptr) {
+  detail::grad_rows("embedding", w, w);
+  Tensor<float> y = newTensor<float>({detail::embedding_ids("embedding", idx), w.shape[1]});
+  embedding(y, w, idx, stream);
+  return y;
+}
+inline EmbeddingGroup embedding_group(const Tensor<int32_t> &idx, int64_t vocab, void *stream = nullptr) {
+  const int64_t tokens = detail::embedding_ids("embedding_group", idx);
+  if (vocab < 0 || vocab > LASER_HIP_EMBEDDING_MAX_VOCAB) throw Error(LASER_HIP_E_INVALID, "embedding_group: 0 <= vocab <= 2^30 is needed");
+  EmbeddingGroup g;
+  g.order = newTensor<int32_t>({tokens});
+  g.starts = newTensor<int32_t>({vocab + 1});
+  check(laser_hip_embedding_group_i32_dev(g.order.unsafe_raw_data(), g.starts.unsafe_raw_data(), idx.unsafe_raw_data(), tokens, vocab, stream));
+  return g;
+}
+// dw into `dw` (vocab, dim); group null: the call groups by itself
+inline void embedding_backward(Tensor<float> &dw, const Tensor<float> &dy, const Tensor<int32_t> &idx, const EmbeddingGroup *group = nullptr,
+                               void *stream = nullptr) {
+  const int64_t dys = detail::grad_rows("embedding_backward", dy, dy), tokens = detail::embedding_ids("embedding_backward", idx);
+  const int64_t dws = detail::grad_rows("embedding_backward", dw, dw), vocab = dw.shape[0];
+  if (dy.shape[0] != tokens || dw.shape[1] != dy.shape[1])
+    throw Error(LASER_HIP_E_INVALID, "embedding_backward: dy (tokens, dim) and dw (vocab, dim) are needed");
+  if (group && (detail::embedding_ids("embedding_backward", group->order) != tokens ||
+                detail::embedding_ids("embedding_backward", group->starts) != vocab + 1))
+    throw Error(LASER_HIP_E_INVALID, "embedding_backward: the group is not embedding_group's for these ids and this vocab");
+  check(laser_hip_embedding_grad_f32_dev(dw.unsafe_raw_data(), dws, dy.unsafe_raw_data(), dys, idx.unsafe_raw_data(),
+                                         group ? group->order.unsafe_raw_data() : nullptr, group ? group->starts.unsafe_raw_data() : nullptr,
+                                         tokens, vocab, dy.shape[1], stream));
+}
+inline Tensor<float> embedding_backward(const Tensor<float> &dy, const Tensor<int32_t> &idx, int64_t vocab, const EmbeddingGroup *group = nullptr,
+                                        void *stream = nullptr) {
+  if (dy.rank() != 2 || vocab < 0) throw Error(LASER_HIP_E_INVALID, "embedding_backward: dy (tokens, dim) and vocab >= 0 are needed");
+  Tensor<float> dw = newTensor<float>({vocab, dy.shape[1]});
+  embedding_backward(dw, dy, idx, group, stream);
+  return dw;
+}
+
 // ---- sine and cosine (include/laser_hip.h "Sine and cosine") over device Tensors -----------------------------------------------
 //   laser::sin(y, x);  laser::cos(y, x);  laser::sincos(s, c, x);   y = laser::sin(x);              (asynchronous on `stream`)
 // lsin and lcos of sincos_core.h: faithful for every finite float32, lsin odd and lcos even bit for bit, NaN for NaN and +-Inf.

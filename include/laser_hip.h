@@ -922,6 +922,79 @@ int laser_hip_layer_norm_grad_f32_dev(float *d_dx, int64_t dx_row_stride, float 
 int laser_hip_layer_norm_plan(int64_t rows, int64_t n, int vec, int what, int64_t *out);
 int laser_hip_layer_norm_last_kernel(int what);
 
+/* ---- Embedding (f32): row gather by int32 ids and a deterministic gradient ------------------------------------------------------
+ * The first layer of a model that starts from token ids: the ids that "F+tree weighted sampler" and the inverse-CDF sampler
+ * return, and that the cross-entropy takes as labels, select rows of a weight table.  The gradient adds the rows of dY that
+ * hit the same id; here it does so in the one documented order of "Reductions", so a scatter keeps the project's claim that a
+ * column's bits depend on its values and the row count alone.
+ * Operands.  W is (vocab, dim) float32: row v is the dim contiguous floats at d_w + v * w_row_stride (ELEMENT strides, each
+ *   >= dim).  idx is `tokens` contiguous int32.  Y and dY are (tokens, dim) and dW is (vocab, dim), addressed like W.
+ * laser_hip_embedding_f32_dev, the forward pass: Y[t, :] is a bit copy of W[idx[t], :] -- NaN payloads and -0 are preserved,
+ *   no arithmetic is done.  idx[t] == -1 (the samplers' "no draw", the cross-entropy's "ignore") gives a row of +0; any other
+ *   id outside [0, vocab) gives a row of quiet NaN (0x7fc00000), so a wrong id never passes silently.  Y may not overlap W.
+ * laser_hip_embedding_group_i32_dev(d_order, d_starts, d_idx, tokens, vocab, stream), the grouping: order is `tokens` int32
+ *   and starts is vocab + 1 int32.  order holds the positions t of the tokens with 0 <= idx[t] < vocab sorted by
+ *   (idx[t], t) ascending, and after them the positions of all other tokens (-1 and out of range alike) in ascending t.
+ *   starts[v] = the number of tokens with a valid id below v: starts[0] = 0, starts[vocab] = the number of valid tokens, and
+ *   id v owns order[starts[v] .. starts[v + 1]).  This is the stable counting sort of the positions by id; its output is
+ *   unique, so it is the same on every grid, stream and run.
+ * laser_hip_embedding_grad_f32_dev, the backward pass.  d_order and d_starts are either both NULL or both the output of the
+ *   grouping call for the same idx and vocab; when NULL the call groups by itself in stream-ordered scratch (the pre-grouped
+ *   form exists so that one id vector feeding several tables is grouped once).  With c = starts[v + 1] - starts[v] and
+ *   a[k] = dY[order[starts[v] + k], j], k = 0 .. c - 1:  dW[v, j] = the sum of the 1-D array a in the order of "Reductions"
+ *   (E = 4, init +0) -- exactly the tree "Dense-layer backward" documents for db, with k in place of the row index: chunks
+ *   of 8192 elements, element k of a chunk to leaf k mod 1024, the fold stated there, chunk partials folded by the same rule.
+ *   The call writes every element of dW: an id that never occurs gets +0, and a single occurrence gives 0 + dY, so -0
+ *   becomes +0.  Tokens whose id is outside [0, vocab), -1 included, contribute nothing: the forward pass has already put NaN
+ *   (or, for -1, the agreed zeros) into that token's row of Y, so the error is visible where it is made and the table's
+ *   gradient stays usable.  dW may not overlap dY, idx, order or starts.
+ * Consequences.  With vocab = 1 and every id 0, dW[0, :] has the bits of laser_hip_bias_grad_f32_dev's db for dY with
+ *   LASER_HIP_ACT_NONE.  dW[v, j] depends on the sequence dY[t, j] over the tokens of id v, in token order, and on nothing
+ *   else: not on other tokens, vocab, dim, the neighbouring columns, the strides, the base alignment, the grid or the stream.
+ *   A NaN or an Inf in dY[t, j] reaches dW[idx[t], j] and no other element (NaN positions are defined, NaN payloads are not).
+ * Valid: 0 <= tokens <= LASER_HIP_EMBEDDING_MAX_TOKENS (positions fit int32 and the chunk partials of one id fit one chunk:
+ *   two levels at most), 0 <= vocab <= LASER_HIP_EMBEDDING_MAX_VOCAB, dim >= 0, any base alignment.  Anything else -- a row
+ *   stride below dim, a NULL buffer that would be touched, exactly one of d_order / d_starts NULL -- gives
+ *   LASER_HIP_E_INVALID before any pointer is touched or a device is looked for.  A buffer that is never touched may be NULL
+ *   (Y and W when tokens or dim is 0, W also when vocab is 0, idx and order when tokens is 0, dW and dY when vocab or dim is
+ *   0, dY when tokens is 0).  All calls are asynchronous on `stream`.
+ * Kernels (laser_amd/csrc/embedding.hip).  Gather: a lane loads its row's id once and walks the row in 16-byte vectors
+ *   (bases 16-byte aligned, row strides multiples of 4) or single elements: same bits.  Grouping: a stable least-significant-
+ *   digit radix sort of the positions by key (the id, or vocab for every invalid id), 8 bits a pass and only as many passes
+ *   as the bit length of vocab needs (vocab <= 255: one; <= 65535: two; < 2^24: three; else four).  A pass is per-wave-tile
+ *   digit histograms, the int32 row cumsum of "Row cumsum" over the (digit, tile) table, and a scatter whose rank among equal
+ *   digits is a per-digit LDS counter plus wave ballots counted below the lane; starts is scan_core.h's lower-bound descent
+ *   over the sorted keys.  Integer adds into counters only; nothing claims a slot atomically.  Sums: ids of at most 32
+ *   occurrences (none included) are evaluated by one lane per four columns in registers -- every leaf is +0 + x, so no partial
+ *   is ever -0, adding a +0 partner is exact, and the tree restricted to the occupied leaves has the same bits; longer
+ *   segments take the workgroup form of the bias gradient, (8192 gathered rows, 16 columns) per chunk, the chunk partials
+ *   folded by the same workgroup.  Two launches whatever the ids are.  No floating-point atomics, no workgroup waits on
+ *   another.
+ * laser_hip_embedding_plan(tokens, vocab, dim, vec, cus, out8): what the calls launch, without a device: out8 = {sort passes,
+ *   sort positions of one wave's tile, workgroups of a pass, kernel code of the sums (0 = 16-byte vectors when vec is 1, 1 =
+ *   single elements), launches of the grouping (3 per pass + 1; tokens = 0: 1), launches of the gradient given a group (2; 0
+ *   when vocab or dim is 0), scratch bytes of the grouping, scratch bytes of the gradient that groups by itself}.  cus is
+ *   taken for symmetry with laser_hip_plan_f32: the plan does not depend on it.  The logic is
+ *   laser_amd/csrc/embedding_plan.h, which has no HIP dependency.
+ * laser_hip_embedding_last_kernel(what): what the last call of this process launched: 0 = the gather's kernel code (0 vector,
+ *   1 single elements), 1 = the sort passes of the last grouping, 2 = the sums' kernel code, 3 = the workgroups of a pass
+ *   of the last grouping; -1 = none yet or an unknown `what`.  (A function of its own: the option table is a recorded set.)
+ * Not built: int64 ids; float64; accumulation into an existing dW; a sparse (rows, values) gradient; scale_grad_by_freq and
+ *   max_norm; a padding id other than -1; a public general-purpose sort; a fused optimizer step (forEach writes
+ *   w -= lr * dw).
+ * No gfx950 device: LASER_HIP_E_NODEVICE. */
+#define LASER_HIP_EMBEDDING_MAX_TOKENS (1ll << 26)
+#define LASER_HIP_EMBEDDING_MAX_VOCAB (1ll << 30)
+int laser_hip_embedding_f32_dev(float *d_y, int64_t y_row_stride, const float *d_w, int64_t w_row_stride, const int32_t *d_idx,
+                                int64_t tokens, int64_t vocab, int64_t dim, void *stream);
+int laser_hip_embedding_group_i32_dev(int32_t *d_order, int32_t *d_starts, const int32_t *d_idx, int64_t tokens, int64_t vocab,
+                                      void *stream);
+int laser_hip_embedding_grad_f32_dev(float *d_dw, int64_t dw_row_stride, const float *d_dy, int64_t dy_row_stride,
+                                     const int32_t *d_idx, const int32_t *d_order, const int32_t *d_starts, int64_t tokens,
+                                     int64_t vocab, int64_t dim, void *stream);
+int laser_hip_embedding_plan(int64_t tokens, int64_t vocab, int64_t dim, int vec, int cus, int64_t *out8);
+int laser_hip_embedding_last_kernel(int what);
+
 /* ---- Sine and cosine (f32): lsin and lcos, defined bit by bit ------------------------------------------------------------
  * The reference's forEach material uses exactly these two (`o = x + y - sin z` in benchmarks/loop_iteration/iter_bench.nim,
  * `sin(s) + cos(s)` in examples/ex02 and ex03); through the device library's sinf their bits are nobody's.  lsin and lcos are

@@ -150,6 +150,11 @@ def lib():
     L.laser_hip_layer_norm_grad_f32_dev.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, vp]
     L.laser_hip_layer_norm_plan.argtypes = [i64, i64, ci, ci, pi]
     L.laser_hip_layer_norm_last_kernel.argtypes = [ci]
+    L.laser_hip_embedding_f32_dev.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, vp]
+    L.laser_hip_embedding_group_i32_dev.argtypes = [vp, vp, vp, i64, i64, vp]
+    L.laser_hip_embedding_grad_f32_dev.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, i64, i64, vp]
+    L.laser_hip_embedding_plan.argtypes = [i64, i64, i64, ci, ci, pi]
+    L.laser_hip_embedding_last_kernel.argtypes = [ci]
     for fn in ("sin", "cos"):
         getattr(L, f"laser_hip_{fn}_f32_dev").argtypes = [vp, pi, vp, pi, pi, ci, vp]
         getattr(L, f"laser_hip_{fn}_f32").argtypes = [vp, vp, i64]
@@ -220,6 +225,8 @@ def declared_symbols():
              "laser_hip_bias_grad_f32_dev", "laser_hip_bias_grad_plan", "laser_hip_bias_grad_last_kernel",
              "laser_hip_layer_norm_f32_dev", "laser_hip_layer_norm_grad_f32_dev", "laser_hip_layer_norm_plan",
              "laser_hip_layer_norm_last_kernel",
+             "laser_hip_embedding_f32_dev", "laser_hip_embedding_group_i32_dev", "laser_hip_embedding_grad_f32_dev",
+             "laser_hip_embedding_plan", "laser_hip_embedding_last_kernel",
              "laser_hip_sin_f32_dev", "laser_hip_cos_f32_dev", "laser_hip_sincos_f32_dev", "laser_hip_sin_f32", "laser_hip_cos_f32",
              "laser_hip_sampler_tree_elems", "laser_hip_sampler_plan", "laser_hip_sampler_build_f32_dev",
              "laser_hip_sampler_sample_f32_dev", "laser_hip_sampler_sample_remove_f32_dev", "laser_hip_sampler_update_f32_dev",

@@ -28,6 +28,7 @@
 #include "sampler_plan.h"
 #include "scan_plan.h"
 #include "bias_grad_plan.h"
+#include "embedding_plan.h"
 #include "layer_norm_plan.h"
 #include "softmax_axis_plan.h"
 #include "softmax_rows_plan.h"
@@ -1581,6 +1582,59 @@ int laser_hip_layer_norm_plan(int64_t rows, int64_t n, int vec, int what, int64_
   return LASER_HIP_OK;
 }
 int laser_hip_layer_norm_last_kernel(int what) { return what >= 0 && what < 3 ? (int)g_last_layer_norm_kernel[what] : -1; }
+// ---- the embedding layer: row gather, stable grouping by id, deterministic gradient (embedding.hip, embedding_plan.h) ------------
+namespace {
+int embedding_sizes(const char *who, int64_t tokens, int64_t vocab, int64_t dim) {
+  if (tokens < 0 || tokens > LASER_HIP_EMBEDDING_MAX_TOKENS || vocab < 0 || vocab > LASER_HIP_EMBEDDING_MAX_VOCAB || dim < 0)
+    return fail(LASER_HIP_E_INVALID, "%s: tokens %lld, vocab %lld, dim %lld (0 <= tokens <= 2^26, 0 <= vocab <= 2^30, dim >= 0)", who,
+                (long long)tokens, (long long)vocab, (long long)dim);
+  return LASER_HIP_OK;
+}
+}  // namespace
+int laser_hip_embedding_f32_dev(float *y, int64_t y_row_stride, const float *w, int64_t w_row_stride, const int32_t *idx, int64_t tokens,
+                                int64_t vocab, int64_t dim, void *stream) {
+  if (int rc = embedding_sizes("embedding", tokens, vocab, dim)) return rc;
+  if (y_row_stride < dim || w_row_stride < dim)
+    return fail(LASER_HIP_E_INVALID, "embedding: row strides %lld (y) / %lld (w) below dim %lld", (long long)y_row_stride,
+                (long long)w_row_stride, (long long)dim);
+  // (what is never touched may be null: idx without tokens, y and w without tokens or columns, w without a vocabulary)
+  if (tokens > 0 && (!idx || (dim > 0 && (!y || (vocab > 0 && !w))))) return fail(LASER_HIP_E_INVALID, "embedding: null buffer");
+  if (int rc = ensure_init()) return rc;
+  HIP_TRY(launch_embedding_f32(y, y_row_stride, w, w_row_stride, idx, tokens, vocab, dim, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_embedding_group_i32_dev(int32_t *order, int32_t *starts, const int32_t *idx, int64_t tokens, int64_t vocab, void *stream) {
+  if (int rc = embedding_sizes("embedding_group", tokens, vocab, 0)) return rc;
+  if (!starts || (tokens > 0 && (!order || !idx))) return fail(LASER_HIP_E_INVALID, "embedding_group: null buffer");
+  if (int rc = ensure_init()) return rc;
+  HIP_TRY(launch_embedding_group_i32(order, starts, idx, tokens, vocab, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_embedding_grad_f32_dev(float *dw, int64_t dw_row_stride, const float *dy, int64_t dy_row_stride, const int32_t *idx,
+                                     const int32_t *order, const int32_t *starts, int64_t tokens, int64_t vocab, int64_t dim,
+                                     void *stream) {
+  if (int rc = embedding_sizes("embedding_grad", tokens, vocab, dim)) return rc;
+  if (dw_row_stride < dim || dy_row_stride < dim)
+    return fail(LASER_HIP_E_INVALID, "embedding_grad: row strides %lld (dw) / %lld (dy) below dim %lld", (long long)dw_row_stride,
+                (long long)dy_row_stride, (long long)dim);
+  if ((order == nullptr) != (starts == nullptr))
+    return fail(LASER_HIP_E_INVALID, "embedding_grad: d_order and d_starts are given together or not at all");
+  // (dW has no element without a vocabulary or columns: nothing is touched then; dy, idx and order only with tokens)
+  if (vocab > 0 && dim > 0 && (!dw || (tokens > 0 && (!dy || !idx)))) return fail(LASER_HIP_E_INVALID, "embedding_grad: null buffer");
+  if (int rc = ensure_init()) return rc;
+  HIP_TRY(launch_embedding_grad_f32(dw, dw_row_stride, dy, dy_row_stride, idx, order, starts, tokens, vocab, dim, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_embedding_plan(int64_t tokens, int64_t vocab, int64_t dim, int vec, int cus, int64_t *out8) {
+  if (!out8) return fail(LASER_HIP_E_INVALID, "embedding_plan: null out8");
+  long long p[8];
+  if (lh_embedding_plan(tokens, vocab, dim, vec, cus, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "embedding_plan: tokens %lld, vocab %lld, dim %lld outside what embedding takes", (long long)tokens,
+                (long long)vocab, (long long)dim);
+  for (int i = 0; i < 8; i++) out8[i] = p[i];
+  return LASER_HIP_OK;
+}
+int laser_hip_embedding_last_kernel(int what) { return what >= 0 && what < 4 ? (int)g_last_embedding_kernel[what] : -1; }
 // ---- lsin, lcos and both at once (sincos_core.h, sincos.hip) ---------------------------------------------------------------------
 int laser_hip_sin_f32_dev(float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
                           void *stream) {

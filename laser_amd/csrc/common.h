@@ -271,6 +271,16 @@ hipError_t launch_layer_norm_param_grads_f32(float *dgamma, int64_t dgamma_strid
                                              int64_t mean_stride, const float *rstd, int64_t rstd_stride, int64_t rows, int64_t n,
                                              hipStream_t s);
 extern std::atomic<int> g_last_layer_norm_kernel[3];
+// the embedding layer (embedding.hip; embedding_plan.h is the launch plan): the row gather, the stable grouping of the token
+// positions by id, and the gradient (order and starts both null: grouped here, in stream-ordered scratch).
+// g_last_embedding_kernel[what]: laser_hip_embedding_last_kernel's answers
+hipError_t launch_embedding_f32(float *y, int64_t y_row_stride, const float *w, int64_t w_row_stride, const int32_t *idx, int64_t tokens,
+                                int64_t vocab, int64_t dim, hipStream_t s);
+hipError_t launch_embedding_group_i32(int32_t *order, int32_t *starts, const int32_t *idx, int64_t tokens, int64_t vocab, hipStream_t s);
+hipError_t launch_embedding_grad_f32(float *dw, int64_t dw_row_stride, const float *dy, int64_t dy_row_stride, const int32_t *idx,
+                                     const int32_t *order, const int32_t *starts, int64_t tokens, int64_t vocab, int64_t dim,
+                                     hipStream_t s);
+extern std::atomic<int> g_last_embedding_kernel[4];
 // lsin, lcos and both from one reduction over strided views (sincos.hip; sincos_core.h is the definition)
 hipError_t launch_sin_f32(float *dst, const int64_t *dstrides, const float *src, const int64_t *sstrides, const int64_t *shape, int rank,
                           hipStream_t s);

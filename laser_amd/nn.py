@@ -11,6 +11,12 @@ and layer normalization over the rows of a matrix, forward and backward (include
     laser_amd.layer_norm(x, gamma=None, beta=None, eps=1e-5, out=None, stats=True) -> (y, mean, rstd)
     laser_amd.layer_norm_backward(dy, x, mean, rstd, gamma=None, need_dx=True, need_params=True) -> (dx, dgamma, dbeta)
 
+and the embedding layer, a row gather by int32 ids with a deterministic gradient (include/laser_hip.h "Embedding"):
+
+    laser_amd.embedding(w, idx, out=None) -> y                                   y[..., :] = w[idx[...], :], a bit copy
+    laser_amd.embedding_group(idx, vocab) -> (order, starts)                     the stable grouping of the positions by id
+    laser_amd.embedding_backward(dy, idx, vocab, out=None, group=None) -> dw     dw[v, :] = reduce_sum over the tokens of id v
+
 With matmul(..., bias=, activation=) as the forward layer, softmax_cross_entropy(grad=True) as the loss and forEach for
 `w -= lr * dw`, a multi-layer perceptron trains without leaving the device, every bit of every step defined by the headers.
 Operands are laser_amd.Tensors or torch CUDA tensors; calls are asynchronous on the current torch stream.
@@ -21,10 +27,11 @@ import numpy as np
 
 from . import _lib
 from .primitives import ACTIVATIONS, matmul
+from .foreach import _View
 from .simd_math import _f32
 from .tensor import _stream, newTensor
 
-__all__ = ["bias_grad", "linear_backward", "layer_norm", "layer_norm_backward"]
+__all__ = ["bias_grad", "linear_backward", "layer_norm", "layer_norm_backward", "embedding", "embedding_group", "embedding_backward"]
 
 
 def _act(activation):
@@ -197,3 +204,116 @@ def layer_norm_backward(dy, x, mean, rstd, gamma=None, need_dx=True, need_params
     _lib.check(_lib.lib().laser_hip_layer_norm_grad_f32_dev(_ptr(vdx), dxs, _ptr(vdg), 1, _ptr(vdb), 1, _ptr(vdy), dys, _ptr(vx), xs,
                                                             _ptr(vm), ms, _ptr(vr), rs, _ptr(vg), gs, rows, n, _stream()))
     return dx, dgamma, dbeta
+
+
+# ---- embedding ----------------------------------------------------------------------------------------------------------------
+EMBEDDING_MAX_TOKENS = 1 << 26
+EMBEDDING_MAX_VOCAB = 1 << 30
+
+
+def _emb_ids(fn, name, obj, count=None):
+    """the view of a contiguous int32 operand of any shape (`count`: the number of elements it must have)"""
+    v = _View(name, obj)
+    if v.dtype == np.int64:
+        raise ValueError(f"{fn}: {name} is int64; convert it to int32 (int64 ids are not built: the samplers return int32)")
+    if v.dtype != np.int32:
+        raise TypeError(f"{fn}: {name} has element type {v.dtype} (int32 only)")
+    acc = 1
+    for e, st in zip(reversed(v.shape), reversed(v.strides)):
+        if e > 1 and st != acc:
+            raise ValueError(f"{fn}: {name} has shape {v.shape}, strides {v.strides} (contiguous is needed)")
+        acc *= e
+    if count is not None and acc != count:
+        raise ValueError(f"{fn}: {name} has {acc} elements, {count} are needed")
+    return v, acc
+
+
+def _emb_rows(fn, name, obj, lead, dim):
+    """(view, row stride) of a (tokens, dim) operand: contiguous of shape lead + (dim,), or a 2-D (tokens, dim) view with unit
+    column stride"""
+    tokens = 1
+    for e in lead:
+        tokens *= e
+    v, rows, n, stride = _ln_rows(fn, name, obj)
+    if v.shape != tuple(lead) + (dim,) and v.shape != (tokens, dim):
+        raise ValueError(f"{fn}: {name} has shape {v.shape}, {tuple(lead) + (dim,)} or {(tokens, dim)} is needed")
+    return v, stride
+
+
+def _emb_vocab(fn, vocab):
+    vocab = int(vocab)
+    if vocab < 0 or vocab > EMBEDDING_MAX_VOCAB:
+        raise ValueError(f"{fn}: vocab = {vocab} (0 <= vocab <= 2^30)")
+    return vocab
+
+
+def embedding(w, idx, out=None):
+    """y[..., :] = w[idx[...], :], a bit copy (NaN payloads and -0 survive).  `w` is a 2-D (vocab, dim) device tensor or view
+    with unit column stride; `idx` is a contiguous int32 tensor of any shape -- what the samplers return and the cross-entropy
+    takes.  An id of -1 gives a row of +0, any other id outside [0, vocab) a row of NaN.  `out`: the destination, contiguous
+    of shape idx.shape + (dim,) or a 2-D (tokens, dim) view (None: a fresh Tensor); it may not overlap `w`."""
+    fn = "embedding"
+    vw, vocab, dim, ws = _ln_rows(fn, "w", w)
+    if vw.rank != 2:
+        raise ValueError(f"{fn}: w has rank {vw.rank} (a 2-D (vocab, dim) tensor or view is needed)")
+    vi, tokens = _emb_ids(fn, "idx", idx)
+    if tokens > EMBEDDING_MAX_TOKENS or vocab > EMBEDDING_MAX_VOCAB:
+        raise ValueError(f"{fn}: {tokens} tokens, vocab {vocab} (tokens <= 2^26, vocab <= 2^30)")
+    if out is None:
+        out = newTensor(np.float32, *(vi.shape + (dim,)))
+    vy, ys = _emb_rows(fn, "out", out, vi.shape, dim)
+    if tokens:
+        _lib.check(_lib.lib().laser_hip_embedding_f32_dev(_ptr(vy), ys, _ptr(vw), ws, _ptr(vi), tokens, vocab, dim, _stream()))
+    return out
+
+
+def embedding_group(idx, vocab):
+    """The stable grouping of the token positions by id: (order, starts), int32 Tensors of idx.size and vocab + 1 elements.
+    `order` holds the positions of the tokens with 0 <= id < vocab sorted by (id, position), then all other positions in
+    ascending order; id v owns order[starts[v] : starts[v + 1]].  Pass the pair as embedding_backward(group=) when one id
+    vector feeds several tables."""
+    fn = "embedding_group"
+    vocab = _emb_vocab(fn, vocab)
+    vi, tokens = _emb_ids(fn, "idx", idx)
+    if tokens > EMBEDDING_MAX_TOKENS:
+        raise ValueError(f"{fn}: {tokens} tokens (tokens <= 2^26)")
+    order, starts = newTensor(np.int32, tokens), newTensor(np.int32, vocab + 1)
+    _lib.check(_lib.lib().laser_hip_embedding_group_i32_dev(_ptr(_View("order", order)), _ptr(_View("starts", starts)), _ptr(vi), tokens,
+                                                            vocab, _stream()))
+    return order, starts
+
+
+def embedding_backward(dy, idx, vocab, out=None, group=None):
+    """The gradient of embedding's table: dw[v, j] = the sum of dy[t, j] over the tokens t of id v, in token order, in the
+    order of reduce_sum applied to that sequence alone -- the same bits on every run, grid and stream; with vocab = 1 and
+    every id 0 they are bias_grad(dy)[0]'s.  Every element of dw is written (+0 for an id that never occurs); tokens whose id
+    is outside [0, vocab), -1 included, contribute nothing.  `dy` is contiguous of shape idx.shape + (dim,) or a 2-D
+    (tokens, dim) view with unit column stride; `out`: a 2-D (vocab, dim) tensor or view (None: fresh); `group`: the pair
+    embedding_group(idx, vocab) returned (None: grouped here)."""
+    fn = "embedding_backward"
+    vocab = _emb_vocab(fn, vocab)
+    vi, tokens = _emb_ids(fn, "idx", idx)
+    if tokens > EMBEDDING_MAX_TOKENS:
+        raise ValueError(f"{fn}: {tokens} tokens (tokens <= 2^26)")
+    vdy = _f32("dy", dy)
+    if vdy.rank < 2:
+        raise ValueError(f"{fn}: dy has rank {vdy.rank} (idx.shape + (dim,) or (tokens, dim) is needed)")
+    dim = vdy.shape[-1]
+    vdy, dys = _emb_rows(fn, "dy", dy, vi.shape, dim)
+    if out is None:
+        out = newTensor(np.float32, vocab, dim)
+    vdw, rows, n, dws = _ln_rows(fn, "out", out)
+    if vdw.shape != (vocab, dim):
+        raise ValueError(f"{fn}: out has shape {vdw.shape}, {(vocab, dim)} is needed")
+    vo = vs = None
+    if group is not None:
+        try:
+            order, starts = group
+        except (TypeError, ValueError):
+            raise ValueError(f"{fn}: group is the pair (order, starts) of embedding_group")
+        vo, _ = _emb_ids(fn, "group[0] (order)", order, tokens)
+        vs, _ = _emb_ids(fn, "group[1] (starts)", starts, vocab + 1)
+    if vocab:
+        _lib.check(_lib.lib().laser_hip_embedding_grad_f32_dev(_ptr(vdw), dws, _ptr(vdy), dys, _ptr(vi), _ptr(vo), _ptr(vs), tokens, vocab,
+                                                               dim, _stream()))
+    return out

@@ -752,6 +752,28 @@ proc layerNormBackward*(dx, dgamma, dbeta: DevicePtr[float32], dy, x, mean, rstd
   ## nil (not wanted) but not all; gamma may be nil; dx may be dy or x; rows <= 2^26 with a parameter gradient
   check laser_hip_layer_norm_grad_f32_dev(cast[ptr float32](dx), int64(n), cast[ptr float32](dgamma), 1, cast[ptr float32](dbeta), 1, cast[ptr float32](dy), int64(n), cast[ptr float32](x), int64(n), cast[ptr float32](mean), 1, cast[ptr float32](rstd), 1, cast[ptr float32](gamma), 1, int64(rows), int64(n), stream)
 
+# ---- embedding (include/laser_hip.h "Embedding"): row gather by int32 ids, stable grouping, deterministic gradient --------
+# row-major device matrices with unit column stride, contiguous rows; ids are int32 (-1: a row of +0 and no gradient; any
+# other id outside [0, vocab): a row of NaN and no gradient)
+proc laser_hip_embedding_f32_dev*(y: ptr float32, yRowStride: int64, w: ptr float32, wRowStride: int64, idx: ptr int32, tokens: int64, vocab: int64, dim: int64, stream: pointer): cint {.lh, importc: "laser_hip_embedding_f32_dev".}
+proc laser_hip_embedding_group_i32_dev*(order: ptr int32, starts: ptr int32, idx: ptr int32, tokens: int64, vocab: int64, stream: pointer): cint {.lh, importc: "laser_hip_embedding_group_i32_dev".}
+proc laser_hip_embedding_grad_f32_dev*(dw: ptr float32, dwRowStride: int64, dy: ptr float32, dyRowStride: int64, idx: ptr int32, order: ptr int32, starts: ptr int32, tokens: int64, vocab: int64, dim: int64, stream: pointer): cint {.lh, importc: "laser_hip_embedding_grad_f32_dev".}
+proc laser_hip_embedding_plan*(tokens: int64, vocab: int64, dim: int64, vec: cint, cus: cint, out8: ptr int64): cint {.lh, importc: "laser_hip_embedding_plan".}
+proc laser_hip_embedding_last_kernel*(what: cint): cint {.lh, importc: "laser_hip_embedding_last_kernel".}
+
+proc embedding*(y: DevicePtr[float32], w: DevicePtr[float32], idx: DevicePtr[int32], tokens, vocab, dim: Natural, stream: pointer = nil) =
+  ## y[t, :] = w[idx[t], :], a bit copy; y is (tokens, dim), w is (vocab, dim)
+  check laser_hip_embedding_f32_dev(cast[ptr float32](y), int64(dim), cast[ptr float32](w), int64(dim), cast[ptr int32](idx), int64(tokens), int64(vocab), int64(dim), stream)
+
+proc embeddingGroup*(order, starts: DevicePtr[int32], idx: DevicePtr[int32], tokens, vocab: Natural, stream: pointer = nil) =
+  ## the stable grouping of the positions by id: order (tokens) and starts (vocab + 1); id v owns order[starts[v] ..< starts[v + 1]]
+  check laser_hip_embedding_group_i32_dev(cast[ptr int32](order), cast[ptr int32](starts), cast[ptr int32](idx), int64(tokens), int64(vocab), stream)
+
+proc embeddingBackward*(dw: DevicePtr[float32], dy: DevicePtr[float32], idx: DevicePtr[int32], order, starts: DevicePtr[int32], tokens, vocab, dim: Natural, stream: pointer = nil) =
+  ## dw[v, :] = the sum of dy[t, :] over the tokens of id v in reduce_sum's order; order and starts are embeddingGroup's, or
+  ## both nil (the call groups by itself)
+  check laser_hip_embedding_grad_f32_dev(cast[ptr float32](dw), int64(dim), cast[ptr float32](dy), int64(dim), cast[ptr int32](idx), cast[ptr int32](order), cast[ptr int32](starts), int64(tokens), int64(vocab), int64(dim), stream)
+
 # ---- sine and cosine (include/laser_hip.h "Sine and cosine"): lsin and lcos of sincos_core.h -----------------------------
 # faithful for every finite float32, lsin odd and lcos even bit for bit, lsin(x) = x for tiny x, NaN for NaN and +-Inf
 proc laser_hip_sin_f32(dst: ptr float32, src: ptr float32, len: int64): cint {.lh, importc: "laser_hip_sin_f32".}
