@@ -24,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = [None, "relu", "tanh", "sigmoid"]
 ROWS = [0, 1, 3, 4, 5, 1023, 1024, 1025, 8191, 8192, 8193, 16389, 40961]     # leaf, chunk and partial boundaries; 2, 3, 6 chunks
 COLS = [1, 3, 4, 15, 16, 17, 37]                                             # strip and vector edges
+# (at most 6 chunks x 3 strips here; more units than the cap of 2048 workgroups are in test_gpu_grid_stride.py)
 SENTINEL = np.float32(-12345.0)
 EPS = 2.0 ** -23
 

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = np.float32(-12345.0)
-MAXT, MAXD = 8200, 37
+MAXT, MAXD = 8200, 37                    # (rows wider than 1024, sort tiles above 512, 4 passes, capped grids: test_gpu_grid_stride.py)
 INVALID = (-1, -2, 2 ** 31 - 1)          # and `vocab` itself, which depends on the case
 
 

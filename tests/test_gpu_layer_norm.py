@@ -22,6 +22,7 @@ NS = [1, 3, 4, 5, 255, 256, 257, 1023, 1024, 1025, 4099, 8191, 8192, 8193, 16389
 ROWS = [0, 1, 3, 4, 5, 9]                                                            # the four-rows-per-workgroup edge
 PROWS = [0, 1, 5, 1023, 1025, 8191, 8192, 8193, 16389]                               # leaf, chunk and partial boundaries
 PCOLS = [1, 3, 4, 15, 16, 17, 37]                                                    # strip and vector edges
+# (no shape here reaches the cap of 2048 workgroups: rows and units past it are in test_gpu_grid_stride.py)
 SENTINEL = np.float32(-12345.0)
 EPS = 1e-5
 FWD, DX, PARAMS = 0, 1, 2

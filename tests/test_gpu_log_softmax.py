@@ -17,7 +17,7 @@ from tests import log_model as G
 pytestmark = pytest.mark.gpu
 
 NS = [1, 3, 4, 5, 255, 256, 257, 1023, 1024, 1025, 8191, 8192, 8193, 16385]
-ROWS = [1, 3, 4, 5, 9]
+ROWS = [1, 3, 4, 5, 9]      # (past the cap of 2048 workgroups: the two cases below; the long-row kernel's: test_gpu_grid_stride.py)
 SENTINEL = np.float32(-12345.0)
 
 

@@ -25,6 +25,7 @@ KINDS = 6                                          # uniform, 60 % zeros, x 1e30
 # the issue's list, plus the bound of the LDS kernel (512 leaves) +- 1 and the segment size / hand-over (1024, 2048 leaves) +- 1
 N_GRID = [1, 2, 3, 4, 5, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096, 4097, 8193, 50000,
           65537]
+# (at most 67 rows here; more rows, segments and draws than the cap of 16384 workgroups holds are in test_gpu_grid_stride.py)
 
 
 def L():

@@ -45,6 +45,7 @@ T = plan_constant("LH_SCAN_LANES") * R             # the tile of the long-row ke
 SWITCHES = [plan_constant("LH_SCAN_WAVE") * R]     # the last n of every variant but the last one
 N_GRID = sorted({1, 2, R - 1, R, R + 1, 2 * R + 1, T - 1, T, T + 1, 2 * T - 1, 2 * T + 1, 50000, 65537} |
                 {n + d for n in SWITCHES for d in (-1, 0, 1)})
+# (at most 67 rows and 64 draws a row here; more rows, values and draws than the capped grids hold are in test_gpu_grid_stride.py)
 
 
 def test_the_grid_covers_the_kernels_bounds():

@@ -48,6 +48,7 @@ def setup_module(_):
 
 
 N_GRID = [1, 2, 3, 4, 5, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4096, 8191, 8192, 8193, 16389]
+# (at most 3 x 5 strips here; more strips than the cap of 2048 workgroups are in test_gpu_grid_stride.py)
 
 _pools = {}
 
