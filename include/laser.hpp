@@ -860,6 +860,69 @@ inline Tensor<float> embedding_backward(const Tensor<float> &dy, const Tensor<in
   return dw;
 }
 
+// ---- optimizer steps (include/laser_hip.h "Optimizer steps") over lists of device Tensors ------------------------------------------
+//   laser::sgd_step({&w1, &b1}, {&dw1, &db1}, &momentum, lr, mu);                 every tensor of the list, one call, in place
+//   laser::adam_step(params, grads, m, v, step, lr);                             step counts from 1; m and v start as zeros
+//   auto n = laser::grad_norm(grads, 1.0f);  laser::sgd_step(params, grads, nullptr, lr, 0, 0, false, 1, &n.clip);
+// Every float32 operation is rounded on its own (laser_amd/csrc/optim_core.h); the clip factor never leaves the device.
+// Tensors are float32 and C-contiguous, of any shape; the lists of one call have equal lengths and element counts.
+typedef std::vector<Tensor<float> *> TensorList;
+struct GradNorm {
+  Tensor<float> norm, clip;  // one element each, on the device
+};
+namespace detail {
+// the device pointers of a list (nullptr for an empty tensor); `lens` is filled by the first list and checked by the others
+inline std::vector<float *> optim_list(const char *what, const TensorList &list, std::vector<int64_t> &lens, bool first) {
+  if (!first && list.size() != lens.size()) throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": lists of unequal length").c_str());
+  if (first) lens.assign(list.size(), 0);
+  std::vector<float *> p(list.size(), nullptr);
+  for (size_t k = 0; k < list.size(); k++) {
+    if (!list[k] || !list[k]->is_C_contiguous())
+      throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": a tensor of a list is null or not C-contiguous").c_str());
+    const int64_t n = list[k]->size();
+    if (first) lens[k] = n;
+    if (n != lens[k]) throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": tensors of unequal size at one list position").c_str());
+    p[k] = n ? list[k]->unsafe_raw_data() : nullptr;
+  }
+  return p;
+}
+}  // namespace detail
+inline float adam_bias_correction(float beta, int64_t step) {
+  float out = 0.0f;
+  check(laser_hip_adam_bias_correction(beta, step, &out));
+  return out;
+}
+inline void sgd_step(const TensorList &params, const TensorList &grads, const TensorList *momentum, float lr, float mu = 0.0f,
+                     float wd = 0.0f, bool nesterov = false, float gscale = 1.0f, const Tensor<float> *clip = nullptr,
+                     void *stream = nullptr) {
+  std::vector<int64_t> lens;
+  const std::vector<float *> w = detail::optim_list("sgd_step", params, lens, true), g = detail::optim_list("sgd_step", grads, lens, false);
+  std::vector<float *> m;
+  if (momentum) m = detail::optim_list("sgd_step", *momentum, lens, false);
+  if (clip && clip->size() != 1) throw Error(LASER_HIP_E_INVALID, "sgd_step: clip is one device float");
+  check(laser_hip_sgd_step_f32_dev(w.data(), g.data(), momentum ? m.data() : nullptr, lens.data(), (int)lens.size(), lr, mu, wd,
+                                   nesterov ? 1 : 0, gscale, clip ? clip->unsafe_raw_data() : nullptr, stream));
+}
+inline void adam_step(const TensorList &params, const TensorList &grads, const TensorList &m, const TensorList &v, int64_t step, float lr,
+                      float b1 = 0.9f, float b2 = 0.999f, float eps = 1e-8f, float wd = 0.0f, bool decoupled = false, float gscale = 1.0f,
+                      const Tensor<float> *clip = nullptr, void *stream = nullptr) {
+  std::vector<int64_t> lens;
+  const std::vector<float *> w = detail::optim_list("adam_step", params, lens, true), g = detail::optim_list("adam_step", grads, lens, false),
+                             pm = detail::optim_list("adam_step", m, lens, false), pv = detail::optim_list("adam_step", v, lens, false);
+  if (clip && clip->size() != 1) throw Error(LASER_HIP_E_INVALID, "adam_step: clip is one device float");
+  check(laser_hip_adam_step_f32_dev(w.data(), g.data(), pm.data(), pv.data(), lens.data(), (int)lens.size(), lr, b1, b2, eps, wd,
+                                    decoupled ? 1 : 0, adam_bias_correction(b1, step), adam_bias_correction(b2, step), gscale,
+                                    clip ? clip->unsafe_raw_data() : nullptr, stream));
+}
+inline GradNorm grad_norm(const TensorList &grads, float max_norm, void *stream = nullptr) {
+  std::vector<int64_t> lens;
+  const std::vector<float *> g = detail::optim_list("grad_norm", grads, lens, true);
+  GradNorm r{newTensor<float>({1}), newTensor<float>({1})};
+  check(laser_hip_grad_norm_f32_dev(r.norm.unsafe_raw_data(), r.clip.unsafe_raw_data(), g.data(), lens.data(), (int)lens.size(), max_norm,
+                                    stream));
+  return r;
+}
+
 // ---- sine and cosine (include/laser_hip.h "Sine and cosine") over device Tensors -----------------------------------------------
 //   laser::sin(y, x);  laser::cos(y, x);  laser::sincos(s, c, x);   y = laser::sin(x);              (asynchronous on `stream`)
 // lsin and lcos of sincos_core.h: faithful for every finite float32, lsin odd and lcos even bit for bit, NaN for NaN and +-Inf.

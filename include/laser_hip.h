@@ -995,6 +995,80 @@ int laser_hip_embedding_grad_f32_dev(float *d_dw, int64_t dw_row_stride, const f
 int laser_hip_embedding_plan(int64_t tokens, int64_t vocab, int64_t dim, int vec, int cus, int64_t *out8);
 int laser_hip_embedding_last_kernel(int what);
 
+/* ---- Optimizer steps (f32): multi-tensor SGD and Adam and the global gradient norm, defined bit by bit ----------------------------
+ * The last link of a training step: one call updates a whole LIST of parameter tensors, and the clip factor of the global
+ * gradient norm is computed, kept and used on the device.  Every + - x / sqrt below is ONE correctly rounded float32
+ * operation, never fused; the arithmetic is defined once, in laser_amd/csrc/optim_core.h.
+ * Lists: d_w, d_g, d_m, d_v are HOST arrays of `count` DEVICE pointers; tensor k is lens[k] contiguous floats at any base
+ * alignment.  A tensor of length 0 is skipped and its pointers may be NULL.  Operands of one call may not overlap (not
+ * detected).  For element i of tensor k, with w, g, m, v the loaded values:
+ *     g1 = g * gscale                        (gscale == 1.0f: the same bits)
+ *     g2 = g1 * c,  c = *d_clip              (d_clip NULL: no operation; c is one device float, read by the kernel)
+ * laser_hip_sgd_step_f32_dev(lr, mu, wd, nesterov):
+ *     g3 = g2 + wd * w                       two roundings; wd == 0: no operation, g3 = g2
+ *     with a momentum list:  m' = mu * m + g3  (two roundings);  d = nesterov ? g3 + mu * m' : m'
+ *     without (d_m NULL):    d = g3          (mu != 0 or nesterov without a list: LASER_HIP_E_INVALID)
+ *     w' = w - lr * d                        two roundings
+ * laser_hip_adam_step_f32_dev(lr, b1, b2, eps, wd, decoupled, bc1, bc2):
+ *     g3 = (!decoupled && wd != 0) ? g2 + wd * w : g2
+ *     m' = b1 * m + omb1 * g3                three roundings; omb1 = 1.0f - b1 in float32, on the host, once
+ *     v' = b2 * v + (omb2 * g3) * g3         four roundings; omb2 = 1.0f - b2 likewise
+ *     mh = m' / bc1;  vh = v' / bc2;  den = sqrt(vh) + eps;  u = mh / den
+ *     w1 = (decoupled && wd != 0) ? w - lrwd * w : w          lrwd = lr * wd in float32, on the host, once
+ *     w' = w1 - lr * u
+ *   m and v start as zeros supplied by the caller; there is no "first step" case.  Hyper-parameters are not validated: NaN,
+ *   Inf and eps = 0 follow IEEE (v = g = 0 with eps = 0 gives 0 / 0 = NaN).  bc1 and bc2 are plain floats:
+ * laser_hip_adam_bias_correction(beta, step, out), host only, no device needed: for step >= 1 (else LASER_HIP_E_INVALID), in
+ *   double, p = beta^step by square-and-multiply from the low bit (r = 1, b = beta; while step: if step & 1: r *= b; b *= b;
+ *   step >>= 1), then *out = (float)(1.0 - p), the product and the difference rounded separately.  Every mirror calls it, so
+ *   bc1 = 1 - b1^t and bc2 = 1 - b2^t are the same bits in every language.
+ * laser_hip_grad_norm_f32_dev(d_norm, d_clip, d_g, lens, count, max_norm):
+ *     s_k   = rsum(g_k[i] * g_k[i])          the product rounded to float32, summed in the order of "Reductions" (E = 4,
+ *                                            init +0): the bits reduce_sum gives for the array g_k * g_k (+0 for length 0)
+ *     total = ((+0 + s_0) + s_1) + ...       left to right in list order
+ *     norm  = sqrt(total)
+ *     clip  = norm > max_norm ? max_norm / norm : 1.0f        (a NaN norm gives 1: the NaN is already in g and travels on)
+ *   d_norm and d_clip are one device float each; either may be NULL, not both.  count = 0 gives norm = +0 and clip = 1.
+ *   Valid max_norm: >= 0 and not NaN; +Inf is allowed (clip = 1 unless the norm is NaN).
+ * Consequences: an element's w', m', v' depend on that element's four values and the scalars alone: never on the grid, the
+ *   stream, the base alignment, the tensor's position in the list or how the list is cut into calls and launches.  SGD with
+ *   mu = 0, wd = 0, gscale = 1, no momentum list and no clip has exactly the bits of forEach("w -= lr * g").  A NaN in one
+ *   element of g reaches no other element, except through c.  s_k depends on tensor k alone; total depends on the list order.
+ * Valid: 0 <= count <= LASER_HIP_OPTIM_MAX_COUNT, 0 <= lens[k] <= LASER_HIP_OPTIM_MAX_LEN (a tensor's chunk partials fit one
+ *   chunk of the order).  A negative length, a limit exceeded, a NULL list or NULL lens with count > 0, a NULL entry with
+ *   lens[k] > 0 give LASER_HIP_E_INVALID before a device is looked for.  Asynchronous on `stream`: no host synchronisation,
+ *   no copy of a table to the device, no allocation but grad_norm's stream-ordered scratch, so a call can be captured in a
+ *   graph.  The host lists are read before the call returns.
+ * Kernels (laser_amd/csrc/optim.hip).  A step launch serves up to 64 tensors: their table (base pointers, lengths, running
+ *   chunk counts) travels BY VALUE in the kernel arguments; a longer list is cut into consecutive launches.  Work is cut into
+ *   chunks of 4096 elements; min(2048, chunks) workgroups stride over the chunks of all tensors of the launch and find a
+ *   chunk's tensor from the prefix with a wave-uniform index.  Per tensor the 16-byte-vector instance runs when all its bases
+ *   are 16-byte aligned (the last len % 4 elements singly), else the single-element one: same bits.  Every input of a step is
+ *   loaded before any store.  grad_norm: per group of 192 tensors one launch with a workgroup per (tensor, 8192-element
+ *   reduction chunk) and one with a workgroup per tensor that folds its partials; then one lane does the list sum, the
+ *   square root and the clip.  No atomics, no workgroup waits on another.
+ * laser_hip_optim_plan(what, lens, count, out4): what the calls would launch, without a device.  what: 0 = SGD, 1 = Adam,
+ *   2 = grad_norm.  out4 = {launches, workgroups of the first launch, chunks in all, scratch bytes}.  Steps: one launch per
+ *   group of 64 consecutive tensors, ceil(count / 64) (a group of empty tensors launches nothing); chunks = the sum of
+ *   ceil(len / 4096); no scratch.  grad_norm: 2 * ceil(count / 192) + 1 launches -- three up to 192 tensors, one for an empty
+ *   list; chunks = the sum of max(1, ceil(len / 8192)); scratch = 4 bytes per chunk and per tensor, each array rounded up to
+ *   16.  The logic is laser_amd/csrc/optim_plan.h, which has no HIP dependency.
+ * Not built: float64 and mixed precision; AMSGrad, RMSprop and LAMB; strided or non-contiguous parameters; a learning rate
+ *   read from the device; per-tensor norms returned to the caller; loss scaling with overflow skip; the update fused into
+ *   dW's GEMM epilogue.
+ * No gfx950 device: LASER_HIP_E_NODEVICE (the bias correction and the plan need none). */
+#define LASER_HIP_OPTIM_MAX_LEN (1ll << 26)
+#define LASER_HIP_OPTIM_MAX_COUNT 65536
+int laser_hip_sgd_step_f32_dev(float *const *d_w, const float *const *d_g, float *const *d_m, const int64_t *lens, int count, float lr,
+                               float mu, float wd, int nesterov, float gscale, const float *d_clip, void *stream);
+int laser_hip_adam_step_f32_dev(float *const *d_w, const float *const *d_g, float *const *d_m, float *const *d_v, const int64_t *lens,
+                                int count, float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2,
+                                float gscale, const float *d_clip, void *stream);
+int laser_hip_grad_norm_f32_dev(float *d_norm, float *d_clip, const float *const *d_g, const int64_t *lens, int count, float max_norm,
+                                void *stream);
+int laser_hip_adam_bias_correction(float beta, int64_t step, float *out);
+int laser_hip_optim_plan(int what, const int64_t *lens, int count, int64_t *out4);
+
 /* ---- Sine and cosine (f32): lsin and lcos, defined bit by bit ------------------------------------------------------------
  * The reference's forEach material uses exactly these two (`o = x + y - sin z` in benchmarks/loop_iteration/iter_bench.nim,
  * `sin(s) + cos(s)` in examples/ex02 and ex03); through the device library's sinf their bits are nobody's.  lsin and lcos are

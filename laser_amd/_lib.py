@@ -155,6 +155,12 @@ def lib():
     L.laser_hip_embedding_grad_f32_dev.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, i64, i64, vp]
     L.laser_hip_embedding_plan.argtypes = [i64, i64, i64, ci, ci, pi]
     L.laser_hip_embedding_last_kernel.argtypes = [ci]
+    pvp, cf = C.POINTER(vp), C.c_float
+    L.laser_hip_sgd_step_f32_dev.argtypes = [pvp, pvp, pvp, pi, ci, cf, cf, cf, ci, cf, vp, vp]
+    L.laser_hip_adam_step_f32_dev.argtypes = [pvp, pvp, pvp, pvp, pi, ci, cf, cf, cf, cf, cf, ci, cf, cf, cf, vp, vp]
+    L.laser_hip_grad_norm_f32_dev.argtypes = [vp, vp, pvp, pi, ci, cf, vp]
+    L.laser_hip_adam_bias_correction.argtypes = [cf, i64, C.POINTER(cf)]
+    L.laser_hip_optim_plan.argtypes = [ci, pi, ci, pi]
     for fn in ("sin", "cos"):
         getattr(L, f"laser_hip_{fn}_f32_dev").argtypes = [vp, pi, vp, pi, pi, ci, vp]
         getattr(L, f"laser_hip_{fn}_f32").argtypes = [vp, vp, i64]
@@ -227,6 +233,8 @@ def declared_symbols():
              "laser_hip_layer_norm_last_kernel",
              "laser_hip_embedding_f32_dev", "laser_hip_embedding_group_i32_dev", "laser_hip_embedding_grad_f32_dev",
              "laser_hip_embedding_plan", "laser_hip_embedding_last_kernel",
+             "laser_hip_sgd_step_f32_dev", "laser_hip_adam_step_f32_dev", "laser_hip_grad_norm_f32_dev",
+             "laser_hip_adam_bias_correction", "laser_hip_optim_plan",
              "laser_hip_sin_f32_dev", "laser_hip_cos_f32_dev", "laser_hip_sincos_f32_dev", "laser_hip_sin_f32", "laser_hip_cos_f32",
              "laser_hip_sampler_tree_elems", "laser_hip_sampler_plan", "laser_hip_sampler_build_f32_dev",
              "laser_hip_sampler_sample_f32_dev", "laser_hip_sampler_sample_remove_f32_dev", "laser_hip_sampler_update_f32_dev",

@@ -29,6 +29,7 @@
 #include "scan_plan.h"
 #include "bias_grad_plan.h"
 #include "embedding_plan.h"
+#include "optim_plan.h"
 #include "layer_norm_plan.h"
 #include "softmax_axis_plan.h"
 #include "softmax_rows_plan.h"
@@ -1635,6 +1636,69 @@ int laser_hip_embedding_plan(int64_t tokens, int64_t vocab, int64_t dim, int vec
   return LASER_HIP_OK;
 }
 int laser_hip_embedding_last_kernel(int what) { return what >= 0 && what < 4 ? (int)g_last_embedding_kernel[what] : -1; }
+// ---- optimizer steps over a list of tensors and the global gradient norm (optim_core.h, optim.hip, optim_plan.h) ---------------
+// the list of a step or of the norm: judged before a device is looked for
+static int optim_list(const char *fn, const int64_t *lens, int count, const void *const *const *lists, const char *const *names, int nlists) {
+  if (count < 0 || count > LASER_HIP_OPTIM_MAX_COUNT) return fail(LASER_HIP_E_INVALID, "%s: count %d (0 <= count <= 65536)", fn, count);
+  if (count == 0) return LASER_HIP_OK;
+  if (!lens) return fail(LASER_HIP_E_INVALID, "%s: null lens", fn);
+  for (int a = 0; a < nlists; a++)
+    if (!lists[a]) return fail(LASER_HIP_E_INVALID, "%s: null list %s", fn, names[a]);
+  for (int k = 0; k < count; k++) {
+    if (lens[k] < 0 || lens[k] > LASER_HIP_OPTIM_MAX_LEN)
+      return fail(LASER_HIP_E_INVALID, "%s: lens[%d] = %lld (0 <= len <= 2^26)", fn, k, (long long)lens[k]);
+    for (int a = 0; a < nlists && lens[k] > 0; a++)
+      if (!lists[a][k]) return fail(LASER_HIP_E_INVALID, "%s: %s[%d] is null with lens[%d] = %lld", fn, names[a], k, k, (long long)lens[k]);
+  }
+  return LASER_HIP_OK;
+}
+int laser_hip_sgd_step_f32_dev(float *const *d_w, const float *const *d_g, float *const *d_m, const int64_t *lens, int count, float lr,
+                               float mu, float wd, int nesterov, float gscale, const float *d_clip, void *stream) {
+  if (!d_m && (mu != 0.0f || nesterov))
+    return fail(LASER_HIP_E_INVALID, "sgd_step: mu %g, nesterov %d without a momentum list", (double)mu, nesterov);
+  const void *const *lists[3] = {(const void *const *)d_w, (const void *const *)d_g, (const void *const *)d_m};
+  const char *names[3] = {"d_w", "d_g", "d_m"};
+  if (int rc = optim_list("sgd_step", lens, count, lists, names, d_m ? 3 : 2)) return rc;
+  if (int rc = ensure_init()) return rc;
+  HIP_TRY(launch_sgd_step_f32(d_w, d_g, d_m, lens, count, lr, mu, wd, nesterov, gscale, d_clip, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_adam_step_f32_dev(float *const *d_w, const float *const *d_g, float *const *d_m, float *const *d_v, const int64_t *lens,
+                                int count, float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2,
+                                float gscale, const float *d_clip, void *stream) {
+  const void *const *lists[4] = {(const void *const *)d_w, (const void *const *)d_g, (const void *const *)d_m, (const void *const *)d_v};
+  const char *names[4] = {"d_w", "d_g", "d_m", "d_v"};
+  if (int rc = optim_list("adam_step", lens, count, lists, names, 4)) return rc;
+  if (int rc = ensure_init()) return rc;
+  HIP_TRY(launch_adam_step_f32(d_w, d_g, d_m, d_v, lens, count, lr, b1, b2, eps, wd, decoupled, bc1, bc2, gscale, d_clip,
+                               (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_grad_norm_f32_dev(float *d_norm, float *d_clip, const float *const *d_g, const int64_t *lens, int count, float max_norm,
+                                void *stream) {
+  if (!d_norm && !d_clip) return fail(LASER_HIP_E_INVALID, "grad_norm: neither d_norm nor d_clip is asked for");
+  if (!(max_norm >= 0.0f)) return fail(LASER_HIP_E_INVALID, "grad_norm: max_norm %g (max_norm >= 0 is needed; +Inf is allowed)", (double)max_norm);
+  const void *const *lists[1] = {(const void *const *)d_g};
+  const char *names[1] = {"d_g"};
+  if (int rc = optim_list("grad_norm", lens, count, lists, names, 1)) return rc;
+  if (int rc = ensure_init()) return rc;
+  HIP_TRY(launch_grad_norm_f32(d_norm, d_clip, d_g, lens, count, max_norm, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_adam_bias_correction(float beta, int64_t step, float *out) {
+  if (!out) return fail(LASER_HIP_E_INVALID, "adam_bias_correction: null out");
+  if (step < 1) return fail(LASER_HIP_E_INVALID, "adam_bias_correction: step %lld (step >= 1 is needed)", (long long)step);
+  *out = optim_bias_correction(beta, step);
+  return LASER_HIP_OK;
+}
+int laser_hip_optim_plan(int what, const int64_t *lens, int count, int64_t *out4) {
+  if (!out4) return fail(LASER_HIP_E_INVALID, "optim_plan: null out4");
+  long long p[4];
+  if (lh_optim_plan(what, lens, count, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "optim_plan: what %d, count %d or a length outside what the optimizer steps take", what, count);
+  for (int i = 0; i < 4; i++) out4[i] = p[i];
+  return LASER_HIP_OK;
+}
 // ---- lsin, lcos and both at once (sincos_core.h, sincos.hip) ---------------------------------------------------------------------
 int laser_hip_sin_f32_dev(float *dst, const int64_t *ds, const float *src, const int64_t *ss, const int64_t *shape, int rank,
                           void *stream) {

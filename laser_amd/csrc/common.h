@@ -281,6 +281,17 @@ hipError_t launch_embedding_grad_f32(float *dw, int64_t dw_row_stride, const flo
                                      const int32_t *order, const int32_t *starts, int64_t tokens, int64_t vocab, int64_t dim,
                                      hipStream_t s);
 extern std::atomic<int> g_last_embedding_kernel[4];
+// the optimizer steps over a list of tensors and the global gradient norm (optim.hip; optim_core.h is the arithmetic,
+// optim_plan.h the launch plan): the pointer lists are host arrays of device pointers, m may be null for SGD, d_clip may be null
+hipError_t launch_sgd_step_f32(float *const *w, const float *const *g, float *const *m, const int64_t *lens, int count, float lr, float mu,
+                               float wd, int nesterov, float gscale, const float *d_clip, hipStream_t s);
+hipError_t launch_adam_step_f32(float *const *w, const float *const *g, float *const *m, float *const *v, const int64_t *lens, int count,
+                                float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2, float gscale,
+                                const float *d_clip, hipStream_t s);
+hipError_t launch_grad_norm_f32(float *d_norm, float *d_clip, const float *const *g, const int64_t *lens, int count, float max_norm,
+                                hipStream_t s);
+// 1 - beta^step of optim_core.h (host only; it lives in optim.hip, which is compiled with contraction off)
+float optim_bias_correction(float beta, int64_t step);
 // lsin, lcos and both from one reduction over strided views (sincos.hip; sincos_core.h is the definition)
 hipError_t launch_sin_f32(float *dst, const int64_t *dstrides, const float *src, const int64_t *sstrides, const int64_t *shape, int rank,
                           hipStream_t s);

@@ -17,8 +17,9 @@ and the embedding layer, a row gather by int32 ids with a deterministic gradient
     laser_amd.embedding_group(idx, vocab) -> (order, starts)                     the stable grouping of the positions by id
     laser_amd.embedding_backward(dy, idx, vocab, out=None, group=None) -> dw     dw[v, :] = reduce_sum over the tokens of id v
 
-With matmul(..., bias=, activation=) as the forward layer, softmax_cross_entropy(grad=True) as the loss and forEach for
-`w -= lr * dw`, a multi-layer perceptron trains without leaving the device, every bit of every step defined by the headers.
+With matmul(..., bias=, activation=) as the forward layer, softmax_cross_entropy(grad=True) as the loss and sgd_step or
+adam_step (laser_amd/optim.py) for the update of every parameter in one launch, a multi-layer perceptron trains without
+leaving the device, every bit of every step defined by the headers.
 Operands are laser_amd.Tensors or torch CUDA tensors; calls are asynchronous on the current torch stream.
 """
 import ctypes as C

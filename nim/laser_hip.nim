@@ -774,6 +774,38 @@ proc embeddingBackward*(dw: DevicePtr[float32], dy: DevicePtr[float32], idx: Dev
   ## both nil (the call groups by itself)
   check laser_hip_embedding_grad_f32_dev(cast[ptr float32](dw), int64(dim), cast[ptr float32](dy), int64(dim), cast[ptr int32](idx), cast[ptr int32](order), cast[ptr int32](starts), int64(tokens), int64(vocab), int64(dim), stream)
 
+# ---- optimizer steps (include/laser_hip.h "Optimizer steps"): multi-tensor SGD and Adam, the global gradient norm -----------
+# the lists are host arrays of device pointers, tensor k is lens[k] contiguous floats; every float32 operation is rounded on
+# its own (laser_amd/csrc/optim_core.h); the clip factor of gradNorm is read by the step kernels on the device
+proc laser_hip_sgd_step_f32_dev*(w: ptr ptr float32, g: ptr ptr float32, m: ptr ptr float32, lens: ptr int64, count: cint, lr: float32, mu: float32, wd: float32, nesterov: cint, gscale: float32, clip: ptr float32, stream: pointer): cint {.lh, importc: "laser_hip_sgd_step_f32_dev".}
+proc laser_hip_adam_step_f32_dev*(w: ptr ptr float32, g: ptr ptr float32, m: ptr ptr float32, v: ptr ptr float32, lens: ptr int64, count: cint, lr: float32, b1: float32, b2: float32, eps: float32, wd: float32, decoupled: cint, bc1: float32, bc2: float32, gscale: float32, clip: ptr float32, stream: pointer): cint {.lh, importc: "laser_hip_adam_step_f32_dev".}
+proc laser_hip_grad_norm_f32_dev*(norm: ptr float32, clip: ptr float32, g: ptr ptr float32, lens: ptr int64, count: cint, maxNorm: float32, stream: pointer): cint {.lh, importc: "laser_hip_grad_norm_f32_dev".}
+proc laser_hip_adam_bias_correction*(beta: float32, step: int64, outp: ptr float32): cint {.lh, importc: "laser_hip_adam_bias_correction".}
+proc laser_hip_optim_plan*(what: cint, lens: ptr int64, count: cint, outp: ptr int64): cint {.lh, importc: "laser_hip_optim_plan".}
+
+proc optimList(list: openArray[DevicePtr[float32]]): ptr ptr float32 =
+  if list.len == 0: nil else: cast[ptr ptr float32](unsafeAddr list[0])
+
+proc adamBiasCorrection*(beta: float32, step: int64): float32 =
+  ## 1 - beta^step (step >= 1) as the float32 every mirror uses: no device needed
+  check laser_hip_adam_bias_correction(beta, step, addr result)
+
+proc sgdStep*(w, g: openArray[DevicePtr[float32]], m: openArray[DevicePtr[float32]], lens: openArray[int64], lr: float32, mu: float32 = 0, wd: float32 = 0, nesterov = false, gscale: float32 = 1, clip: DevicePtr[float32] = DevicePtr[float32](nil), stream: pointer = nil) =
+  ## one SGD step on every tensor of the list, in place; m empty: no momentum (mu = 0 and no nesterov); clip: gradNorm's factor or nil
+  doAssert w.len == lens.len and g.len == lens.len and (m.len == 0 or m.len == lens.len)
+  check laser_hip_sgd_step_f32_dev(optimList(w), optimList(g), optimList(m), (if lens.len == 0: nil else: unsafeAddr lens[0]), cint(lens.len), lr, mu, wd, cint(ord(nesterov)), gscale, cast[ptr float32](clip), stream)
+
+proc adamStep*(w, g, m, v: openArray[DevicePtr[float32]], lens: openArray[int64], step: int64, lr: float32, b1: float32 = 0.9, b2: float32 = 0.999, eps: float32 = 1e-8, wd: float32 = 0, decoupled = false, gscale: float32 = 1, clip: DevicePtr[float32] = DevicePtr[float32](nil), stream: pointer = nil) =
+  ## one Adam step (step counts from 1; m and v start as zeros) on every tensor of the list, in place; decoupled: AdamW's decay
+  doAssert w.len == lens.len and g.len == lens.len and m.len == lens.len and v.len == lens.len
+  check laser_hip_adam_step_f32_dev(optimList(w), optimList(g), optimList(m), optimList(v), (if lens.len == 0: nil else: unsafeAddr lens[0]), cint(lens.len), lr, b1, b2, eps, wd, cint(ord(decoupled)), adamBiasCorrection(b1, step), adamBiasCorrection(b2, step), gscale, cast[ptr float32](clip), stream)
+
+proc gradNorm*(norm, clip: DevicePtr[float32], g: openArray[DevicePtr[float32]], lens: openArray[int64], maxNorm: float32 = Inf, stream: pointer = nil) =
+  ## norm = sqrt of the sum over the list of reduce_sum(g * g), clip = maxNorm / norm when norm > maxNorm, else 1: one device
+  ## float each; either may be nil, not both
+  doAssert g.len == lens.len
+  check laser_hip_grad_norm_f32_dev(cast[ptr float32](norm), cast[ptr float32](clip), optimList(g), (if lens.len == 0: nil else: unsafeAddr lens[0]), cint(lens.len), maxNorm, stream)
+
 # ---- sine and cosine (include/laser_hip.h "Sine and cosine"): lsin and lcos of sincos_core.h -----------------------------
 # faithful for every finite float32, lsin odd and lcos even bit for bit, lsin(x) = x for tiny x, NaN for NaN and +-Inf
 proc laser_hip_sin_f32(dst: ptr float32, src: ptr float32, len: int64): cint {.lh, importc: "laser_hip_sin_f32".}
