@@ -4,6 +4,7 @@
 // Header-only; link with -llaser_hip.  No compute happens on the host.
 #pragma once
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <initializer_list>
@@ -798,6 +799,125 @@ inline LayerNormGrads layer_norm_backward(const Tensor<float> &dy, const Tensor<
                                           detail::norm_vec("layer_norm_backward", mean, rows), rstd.unsafe_raw_data(),
                                           detail::norm_vec("layer_norm_backward", rstd, rows), gamma ? gamma->unsafe_raw_data() : nullptr,
                                           gamma ? detail::norm_vec("layer_norm_backward", *gamma, n) : 1, rows, n, stream));
+  return g;
+}
+
+// ---- the softmax gradient and attention (include/laser_hip.h "Softmax gradient", "Attention") over device Tensors ----------------
+//   auto dx = laser::softmax_backward(dy, y);                                      dx = y * (dy - reduce_sum(dy * y)) per row
+//   auto f = laser::attention(q, k, v, scale, causal, /*probs*/ false, /*stats*/ false);    f.out (f.probs, f.row_max, f.row_sum)
+//   auto g = laser::attention_backward(dout, q, k, v, scale, causal);              g.dq, g.dk, g.dv
+// softmax_backward: 2-D (rows, n) Tensors or views with unit column stride; dx may be dy or y.  attention: q (B, H, Tq, d) or
+// (BH, Tq, d), k (.., Tk, d), v (.., Tk, dv), Tensors or views of any outer strides with unit feature stride; scale < 0 or NaN
+// is taken as given, laser::attention_default_scale(d) is float(1 / sqrt(double(d))).
+inline void softmax_backward(Tensor<float> &dx, const Tensor<float> &dy, const Tensor<float> &y, void *stream = nullptr) {
+  const int64_t dys = detail::grad_rows("softmax_backward", dy, dy), rows = dy.shape[0], n = dy.shape[1];
+  check(laser_hip_softmax_grad_rows_f32_dev(dx.unsafe_raw_data(), detail::grad_rows("softmax_backward", dx, dy), dy.unsafe_raw_data(), dys,
+                                            y.unsafe_raw_data(), detail::grad_rows("softmax_backward", y, dy), rows, n, stream));
+}
+inline Tensor<float> softmax_backward(const Tensor<float> &dy, const Tensor<float> &y, void *stream = nullptr) {
+  Tensor<float> dx = exp_result_like(dy);
+  softmax_backward(dx, dy, y, stream);
+  return dx;
+}
+struct AttentionResult {
+  Tensor<float> out, probs, row_max, row_sum;  // empty (no storage) when not asked for
+};
+struct AttentionGrads {
+  Tensor<float> dq, dk, dv;  // empty (no storage) when not asked for
+};
+inline float attention_default_scale(int64_t d) { return (float)(1.0 / std::sqrt((double)d)); }
+namespace detail {
+struct AttnView {
+  int64_t b, h, t, w, st[4];  // strides of batch, head, position, feature (1)
+};
+inline AttnView attn_view(const char *what, const Tensor<float> &x) {
+  const int r = x.rank();
+  if ((r != 3 && r != 4) || (x.shape[r - 1] > 1 && x.strides[r - 1] != 1))
+    throw Error(LASER_HIP_E_INVALID, (std::string(what) + ": 3-D (BH, T, d) or 4-D (B, H, T, d) operands with unit feature stride are needed").c_str());
+  AttnView v;
+  v.b = x.shape[0], v.h = r == 4 ? x.shape[1] : 1, v.t = x.shape[r - 2], v.w = x.shape[r - 1];
+  v.st[0] = x.strides[0], v.st[1] = r == 4 ? x.strides[1] : 0, v.st[2] = x.strides[r - 2], v.st[3] = 1;
+  return v;
+}
+inline Tensor<float> attn_new(const AttnView &like, bool four, int64_t t, int64_t w) {
+  return four ? newTensor<float>({like.b, like.h, t, w}) : newTensor<float>({like.b, t, w});
+}
+// C[b, h] = alpha * A[b, h] B[b, h] on gemm_strided_batched: strides {batch, head, row, column}; one launch per batch unless
+// the (batch, head) dims of all three collapse into one batch stride
+inline void attn_gemm(int64_t b, int64_t h, int64_t M, int64_t N, int64_t K, float alpha, const float *A, const int64_t *as, const float *B,
+                      const int64_t *bs, float *Cm, const int64_t *cs, void *stream) {
+  if (b * h == 0 || M == 0 || N == 0) return;
+  const bool one = h == 1 || b == 1 || (as[0] == as[1] * h && bs[0] == bs[1] * h && cs[0] == cs[1] * h);
+  const int pick = h == 1 ? 0 : 1;
+  for (int64_t i = 0; i < (one ? 1 : b); i++)
+    check(laser_hip_gemm_strided_batched_f32_dev(one ? b * h : h, M, N, K, alpha, A + i * as[0], as[2], as[3], as[pick], B + i * bs[0], bs[2],
+                                                 bs[3], bs[pick], 0.0f, Cm + i * cs[0], cs[2], cs[3], cs[pick], stream));
+}
+}  // namespace detail
+// the fused forward: out (unless need_out is false), P with probs, the row maxima and sums with stats
+inline AttentionResult attention(const Tensor<float> &q, const Tensor<float> &k, const Tensor<float> &v, float scale, bool causal = false,
+                                 bool probs = false, bool stats = false, bool need_out = true, void *stream = nullptr) {
+  const detail::AttnView vq = detail::attn_view("attention", q), vk = detail::attn_view("attention", k), vv = detail::attn_view("attention", v);
+  if (q.rank() != k.rank() || q.rank() != v.rank() || vk.b != vq.b || vk.h != vq.h || vv.b != vq.b || vv.h != vq.h || vk.w != vq.w || vv.t != vk.t)
+    throw Error(LASER_HIP_E_INVALID, "attention: q (.., Tq, d), k (.., Tk, d) and v (.., Tk, dv) with one leading shape are needed");
+  const bool four = q.rank() == 4;
+  AttentionResult f;
+  int64_t os[3] = {0, 0, 0}, ps[3] = {0, 0, 0};
+  if (need_out) {
+    f.out = detail::attn_new(vq, four, vq.t, vv.w);
+    os[0] = vq.h * vq.t * vv.w, os[1] = four ? vq.t * vv.w : 0, os[2] = vv.w;
+  }
+  if (probs) {
+    f.probs = detail::attn_new(vq, four, vq.t, vk.t);
+    ps[0] = vq.h * vq.t * vk.t, ps[1] = four ? vq.t * vk.t : 0, ps[2] = vk.t;
+  }
+  if (stats) {
+    f.row_max = four ? newTensor<float>({vq.b, vq.h, vq.t}) : newTensor<float>({vq.b, vq.t});
+    f.row_sum = four ? newTensor<float>({vq.b, vq.h, vq.t}) : newTensor<float>({vq.b, vq.t});
+  }
+  check(laser_hip_attention_f32_dev(need_out ? f.out.unsafe_raw_data() : nullptr, os, q.unsafe_raw_data(), vq.st, k.unsafe_raw_data(), vk.st,
+                                    v.unsafe_raw_data(), vv.st, probs ? f.probs.unsafe_raw_data() : nullptr, ps,
+                                    stats ? f.row_max.unsafe_raw_data() : nullptr, stats ? f.row_sum.unsafe_raw_data() : nullptr, vq.b, vq.h,
+                                    vq.t, vk.t, vq.w, vv.w, scale, causal ? 1 : 0, stream));
+  return f;
+}
+// the composed backward: P from the forward kernel, dV = P^T dO, dP = dO V^T, dS = softmax_backward(dP, P) in place,
+// dQ = scale * (dS K), dK = scale * (dS^T Q); needs B*H*Tq*Tk floats twice
+inline AttentionGrads attention_backward(const Tensor<float> &dout, const Tensor<float> &q, const Tensor<float> &k, const Tensor<float> &v,
+                                         float scale, bool causal = false, bool need_q = true, bool need_k = true, bool need_v = true,
+                                         void *stream = nullptr) {
+  if (!need_q && !need_k && !need_v) throw Error(LASER_HIP_E_INVALID, "attention_backward: nothing is asked for");
+  AttentionResult f = attention(q, k, v, scale, causal, true, false, false, stream);
+  const detail::AttnView vq = detail::attn_view("attention_backward", q), vk = detail::attn_view("attention_backward", k),
+                         vv = detail::attn_view("attention_backward", v), vo = detail::attn_view("attention_backward", dout);
+  if (dout.rank() != q.rank() || vo.b != vq.b || vo.h != vq.h || vo.t != vq.t || vo.w != vv.w)
+    throw Error(LASER_HIP_E_INVALID, "attention_backward: dout must have the shape of the forward output");
+  const bool four = q.rank() == 4;
+  const int64_t b = vq.b, h = vq.h, tq = vq.t, tk = vk.t, d = vq.w, dv = vv.w;
+  const int64_t ps[4] = {h * tq * tk, tq * tk, tk, 1}, pt[4] = {h * tq * tk, tq * tk, 1, tk};
+  const int64_t vt[4] = {vv.st[0], vv.st[1], 1, vv.st[2]};
+  AttentionGrads g;
+  if (need_v) {
+    g.dv = detail::attn_new(vq, four, tk, dv);
+    const int64_t cs[4] = {h * tk * dv, tk * dv, dv, 1};
+    detail::attn_gemm(b, h, tk, dv, tq, 1.0f, f.probs.unsafe_raw_data(), pt, dout.unsafe_raw_data(), vo.st, g.dv.unsafe_raw_data(), cs, stream);
+  }
+  if (need_q || need_k) {
+    Tensor<float> ds = detail::attn_new(vq, four, tq, tk);
+    detail::attn_gemm(b, h, tq, tk, dv, 1.0f, dout.unsafe_raw_data(), vo.st, v.unsafe_raw_data(), vt, ds.unsafe_raw_data(), ps, stream);
+    check(laser_hip_softmax_grad_rows_f32_dev(ds.unsafe_raw_data(), tk, ds.unsafe_raw_data(), tk, f.probs.unsafe_raw_data(), tk, b * h * tq, tk,
+                                              stream));
+    if (need_q) {
+      g.dq = detail::attn_new(vq, four, tq, d);
+      const int64_t cs[4] = {h * tq * d, tq * d, d, 1};
+      detail::attn_gemm(b, h, tq, d, tk, scale, ds.unsafe_raw_data(), ps, k.unsafe_raw_data(), vk.st, g.dq.unsafe_raw_data(), cs, stream);
+    }
+    if (need_k) {
+      g.dk = detail::attn_new(vq, four, tk, d);
+      const int64_t cs[4] = {h * tk * d, tk * d, d, 1};
+      detail::attn_gemm(b, h, tk, d, tq, scale, ds.unsafe_raw_data(), pt, q.unsafe_raw_data(), vq.st, g.dk.unsafe_raw_data(), cs, stream);
+    }
+  }
   return g;
 }
 

@@ -1069,6 +1069,80 @@ int laser_hip_grad_norm_f32_dev(float *d_norm, float *d_clip, const float *const
 int laser_hip_adam_bias_correction(float beta, int64_t step, float *out);
 int laser_hip_optim_plan(int what, const int64_t *lens, int count, int64_t *out4);
 
+/* ---- Softmax gradient (f32): the backward of the row softmax from its output, defined bit by bit ---------------------------------
+ * laser_hip_softmax_grad_rows_f32_dev: for each of `rows` rows, with y the softmax's OUTPUT row and dy the incoming gradient
+ *   (elements of a row contiguous, row strides in elements and >= n):
+ *   1. D = reduce_sum(dy (.) y): every product dy[j] * y[j] rounded to float32 on its own, the sum in the order of
+ *      "Reductions" applied to the row of products as a 1-D array of n float32 (E = 4, init +0).
+ *   2. dx[j] = y[j] * (dy[j] - D): a rounded subtraction, then a rounded multiplication; nothing is fused.
+ *   A row's result is a function of its values and n alone.  Valid: rows >= 0 (0: nothing happens), 1 <= n <= 2^26, any base
+ *   alignment; d_dx may be d_dy or d_y with equal row strides (any other overlap is not allowed); anything else
+ *   LASER_HIP_E_INVALID.  Asynchronous on `stream`.
+ * laser_hip_softmax_grad_plan: what the call would launch, without a device: out3 = {kernel code, workgroups, LDS bytes}.  The
+ *   lane mappings, their thresholds, the codes and the grid are those of laser_hip_softmax_rows_plan (0 = one wave per row,
+ *   n <= 1024; 1 = one workgroup per row, n <= 8192; 2 = long rows; + 4 for single-element accesses); only the LDS differs (no
+ *   table).  The logic is lh_softmax_grad_rows_plan in laser_amd/csrc/softmax_rows_plan.h.
+ * laser_hip_softmax_grad_last_kernel(): the plan's kernel code of the last launch in this process; -1 = none yet.
+ * No gfx950 device: LASER_HIP_E_NODEVICE. */
+int laser_hip_softmax_grad_rows_f32_dev(float *d_dx, int64_t dx_row_stride, const float *d_dy, int64_t dy_row_stride, const float *d_y,
+                                        int64_t y_row_stride, int64_t rows, int64_t n, void *stream);
+int laser_hip_softmax_grad_plan(int64_t rows, int64_t n, int vec, int64_t *out3);
+int laser_hip_softmax_grad_last_kernel(void);
+
+/* ---- Attention (f32): O = softmax(scale * Q K^T) V, fused, defined bit by bit ----------------------------------------------------
+ * Per (batch b, head h) slice: Q is (Tq, d), K is (Tk, d), V is (Tk, dv), O is (Tq, dv).  Element [b, h, t, c] of an operand is at
+ * ptr + b * strides[0] + h * strides[1] + t * strides[2] + c: ELEMENT strides {batch, head, position}, unit stride along the
+ * feature index -- so Q, K and V may be slices of one fused projection output (B, T, 3, H, d) with no copy.
+ * Limits: 1 <= d, dv <= LASER_HIP_ATTENTION_MAX_D; 1 <= Tk <= LASER_HIP_ATTENTION_MAX_KEYS; Tq >= 0; B * H >= 0 (0: nothing
+ * happens).  Anything past a limit is LASER_HIP_E_INVALID and the text says which limit.
+ * The rule:
+ *   1. Scores.  c[i,j] = the k-ascending fmaf chain over k = 0..d-1 of Q[i,k] * K[j,k], from +0: the GEMM's laser-order
+ *      contract for K <= 512 (one chain; an f32 MFMA is bitwise that chain, and gfx950 has no xf32 path).  s[i,j] =
+ *      scale * c[i,j], one rounded multiply, never fused into the chain.  (gemm_strided writes 0 + alpha*AB on full tiles and
+ *      alpha*AB on edge tiles, so a score matrix composed from it may differ from s in the sign of a zero.  That sign never
+ *      reaches P: lexp(+-0 - m) has the same bits.  Where products underflow so that a chain ends at -0, the sign of a zero
+ *      row_max is the chain's.)
+ *   2. Causal (causal != 0; needs Tq <= Tk, otherwise LASER_HIP_E_INVALID).  Row i sees keys [0, n_i), n_i = i + (Tk - Tq) + 1;
+ *      without causal n_i = Tk.  A masked score is never used: a NaN in a K row reaches only the rows that see that row.
+ *      There is no -Inf trick: lexp clamps at -88, so -Inf would not give 0.
+ *   3. Probabilities.  P[i, 0:n_i] is exactly laser_hip_softmax_rows_f32_dev applied to s[i, 0:n_i] as a 1-D array of n_i
+ *      elements: m_i = the maximum under reduce_max's rule, e = lexp(s - m_i), s_i = the sum of e in the order of "Reductions"
+ *      (E = 4, init +0), P = e / s_i correctly rounded.  P[i, j >= n_i] = +0.  The softmax's NaN rules carry over: a NaN or a
+ *      +Inf maximum in a row makes that row of P NaN, and hence that row of O.
+ *   4. Output.  O = P V in laser-order over ALL Tk keys, the masked ones included with their +0: S_p[i,c] = the fmaf chain
+ *      over j in [512 p, 512 (p + 1)) of P[i,j] * V[j,c], from +0, and O = ((S_0 + S_1) + S_2) + .., each addition rounded,
+ *      nothing fused (a single slice is S_0 itself).  That is gemm_strided(P, V) in laser-order mode.  So a NaN or an Inf in a
+ *      V row reaches every row of O (0 * NaN), as it does in the composition.
+ * Every row i of every slice depends on Q[i,:], K, V, scale, n_i and Tk alone: never on B, H, Tq, the strides, the base
+ * alignment, the grid, the stream or the kernel instance the plan picks.
+ * Outputs, each optional (NULL: not written), but at least one:
+ *   d_out            O, with its own strides
+ *   d_probs          P in full, (B, H, Tq, Tk) with its own strides {batch, head, row}, the masked +0 included
+ *   d_row_max/_sum   m_i and s_i, (B, H, Tq) contiguous
+ * With d_out NULL the P V sweep is skipped.  What is asked for has the same bits whatever else is asked for.  Outputs may not
+ * overlap inputs or each other.  Position strides must be >= the row length (d, dv or Tk) wherever there is more than one
+ * position; no stride may be negative.  Arguments are judged before any pointer is dereferenced.  Asynchronous on `stream`.
+ * laser_hip_attention_plan: what a call would launch, without a device: out5 = {BM (query rows of a workgroup), kernel code,
+ *   workgroups, LDS bytes, units}.  bh = B * H; vec = 1 when the bases of Q and K are 16-byte aligned and all their strides are
+ *   multiples of 4 elements (code 0, 16-byte loads), else code 1 (single-element loads): the same bits.  The units are the
+ *   bh * ceil(Tq / BM) query blocks; at most 1024 workgroups stride over them.  One kernel form, streaming: no resident form is
+ *   built.  The logic is laser_amd/csrc/attention_plan.h, which has no HIP dependency.
+ * laser_hip_attention_last_kernel(): the kernel code of the last launch in this process; -1 = none yet.
+ * The backward is a composition of defined steps, built in the mirrors (laser_amd.attention_backward, laser::attention_backward,
+ * attentionBackward): P from this entry point (d_probs, d_out NULL); dV = P^T dO; dP = dO V^T; dS = softmax_grad(dP, P) over the
+ * full Tk (masked positions give +-0); dQ = scale * (dS K); dK = scale * (dS^T Q) -- the four products on
+ * gemm_strided_batched in the current float mode, the transposes as strides, scale as the GEMM's alpha.
+ * Not built: float64 and 16-bit operands, a resident (scores in LDS) form, a fused backward, dropout, an additive mask or bias.
+ * No gfx950 device: LASER_HIP_E_NODEVICE. */
+#define LASER_HIP_ATTENTION_MAX_D 128
+#define LASER_HIP_ATTENTION_MAX_KEYS 65536
+int laser_hip_attention_f32_dev(float *d_out, const int64_t *out_strides, const float *d_q, const int64_t *q_strides, const float *d_k,
+                                const int64_t *k_strides, const float *d_v, const int64_t *v_strides, float *d_probs,
+                                const int64_t *probs_strides, float *d_row_max, float *d_row_sum, int64_t batch, int64_t heads,
+                                int64_t tq, int64_t tk, int64_t d, int64_t dv, float scale, int causal, void *stream);
+int laser_hip_attention_plan(int64_t bh, int64_t tq, int64_t tk, int64_t d, int64_t dv, int causal, int vec, int64_t *out5);
+int laser_hip_attention_last_kernel(void);
+
 /* ---- Sine and cosine (f32): lsin and lcos, defined bit by bit ------------------------------------------------------------
  * The reference's forEach material uses exactly these two (`o = x + y - sin z` in benchmarks/loop_iteration/iter_bench.nim,
  * `sin(s) + cos(s)` in examples/ex02 and ex03); through the device library's sinf their bits are nobody's.  lsin and lcos are

@@ -10,12 +10,13 @@ from . import tensor  # noqa: F401
 from . import sharded  # noqa: F401
 from .foreach import forEach  # noqa: F401
 from .reduce import reduce_sum, reduce_min, reduce_max, forEachReduce  # noqa: F401
-from .simd_math import exp, softmax, log, logsumexp, log_softmax, softmax_cross_entropy  # noqa: F401
+from .simd_math import exp, softmax, softmax_backward, log, logsumexp, log_softmax, softmax_cross_entropy  # noqa: F401
 from .simd_math import tanh, sigmoid, activation, activation_grad  # noqa: F401
 from .simd_math import sin, cos, sincos  # noqa: F401
 from .nn import bias_grad, linear_backward, layer_norm, layer_norm_backward  # noqa: F401
 from .optim import sgd_step, adam_step, grad_norm, adam_bias_correction, SGD, Adam  # noqa: F401
 from .nn import embedding, embedding_group, embedding_backward  # noqa: F401
+from .nn import attention, attention_backward  # noqa: F401
 from .sampling import Sampler, newSampler, multinomial  # noqa: F401
 from .random import Rng, randomTensor, randomNormalTensor  # noqa: F401
 from .scan import cumsum, searchsorted, cdfSample, cdfSampleAndRemove  # noqa: F401

@@ -150,6 +150,12 @@ def lib():
     L.laser_hip_layer_norm_grad_f32_dev.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, vp]
     L.laser_hip_layer_norm_plan.argtypes = [i64, i64, ci, ci, pi]
     L.laser_hip_layer_norm_last_kernel.argtypes = [ci]
+    L.laser_hip_softmax_grad_rows_f32_dev.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, vp]
+    L.laser_hip_softmax_grad_plan.argtypes = [i64, i64, ci, pi]
+    L.laser_hip_softmax_grad_last_kernel.argtypes = []
+    L.laser_hip_attention_f32_dev.argtypes = [vp, pi, vp, pi, vp, pi, vp, pi, vp, pi, vp, vp, i64, i64, i64, i64, i64, i64, C.c_float, ci, vp]
+    L.laser_hip_attention_plan.argtypes = [i64, i64, i64, i64, i64, ci, ci, pi]
+    L.laser_hip_attention_last_kernel.argtypes = []
     L.laser_hip_embedding_f32_dev.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, vp]
     L.laser_hip_embedding_group_i32_dev.argtypes = [vp, vp, vp, i64, i64, vp]
     L.laser_hip_embedding_grad_f32_dev.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, i64, i64, vp]
@@ -231,6 +237,8 @@ def declared_symbols():
              "laser_hip_bias_grad_f32_dev", "laser_hip_bias_grad_plan", "laser_hip_bias_grad_last_kernel",
              "laser_hip_layer_norm_f32_dev", "laser_hip_layer_norm_grad_f32_dev", "laser_hip_layer_norm_plan",
              "laser_hip_layer_norm_last_kernel",
+             "laser_hip_softmax_grad_rows_f32_dev", "laser_hip_softmax_grad_plan", "laser_hip_softmax_grad_last_kernel",
+             "laser_hip_attention_f32_dev", "laser_hip_attention_plan", "laser_hip_attention_last_kernel",
              "laser_hip_embedding_f32_dev", "laser_hip_embedding_group_i32_dev", "laser_hip_embedding_grad_f32_dev",
              "laser_hip_embedding_plan", "laser_hip_embedding_last_kernel",
              "laser_hip_sgd_step_f32_dev", "laser_hip_adam_step_f32_dev", "laser_hip_grad_norm_f32_dev",

@@ -31,6 +31,7 @@
 #include "embedding_plan.h"
 #include "optim_plan.h"
 #include "layer_norm_plan.h"
+#include "attention_plan.h"
 #include "softmax_axis_plan.h"
 #include "softmax_rows_plan.h"
 
@@ -1583,6 +1584,98 @@ int laser_hip_layer_norm_plan(int64_t rows, int64_t n, int vec, int what, int64_
   return LASER_HIP_OK;
 }
 int laser_hip_layer_norm_last_kernel(int what) { return what >= 0 && what < 3 ? (int)g_last_layer_norm_kernel[what] : -1; }
+// ---- the softmax gradient from the output (softmax_grad.hip; lh_softmax_grad_rows_plan in softmax_rows_plan.h) --------------------
+int laser_hip_softmax_grad_rows_f32_dev(float *dx, int64_t dx_row_stride, const float *dy, int64_t dy_row_stride, const float *y,
+                                        int64_t y_row_stride, int64_t rows, int64_t n, void *stream) {
+  if (n < 1 || n > LASER_HIP_SOFTMAX_MAX_N) return fail(LASER_HIP_E_INVALID, "softmax_grad: row length %lld outside 1..2^26", (long long)n);
+  if (rows < 0) return fail(LASER_HIP_E_INVALID, "softmax_grad: negative row count");
+  if (dx_row_stride < n || dy_row_stride < n || y_row_stride < n)
+    return fail(LASER_HIP_E_INVALID, "softmax_grad: row strides %lld (dx) / %lld (dy) / %lld (y) below the row length %lld",
+                (long long)dx_row_stride, (long long)dy_row_stride, (long long)y_row_stride, (long long)n);
+  if (dx && ((dx == dy && dx_row_stride != dy_row_stride) || (dx == y && dx_row_stride != y_row_stride)))
+    return fail(LASER_HIP_E_INVALID, "softmax_grad: dx in place over dy or y needs equal row strides");
+  if (rows > 0 && (!dx || !dy || !y)) return fail(LASER_HIP_E_INVALID, "softmax_grad: null buffer");
+  if (int rc = ensure_init()) return rc;
+  if (rows == 0) return LASER_HIP_OK;
+  HIP_TRY(launch_softmax_grad_rows_f32(dx, dx_row_stride, dy, dy_row_stride, y, y_row_stride, rows, n, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_softmax_grad_plan(int64_t rows, int64_t n, int vec, int64_t *out3) {
+  if (!out3) return fail(LASER_HIP_E_INVALID, "softmax_grad_plan: null out3");
+  long long p[3];
+  if (lh_softmax_grad_rows_plan(rows, n, vec, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "softmax_grad_plan: rows %lld, n %lld outside what softmax_grad takes", (long long)rows, (long long)n);
+  for (int i = 0; i < 3; i++) out3[i] = p[i];
+  return LASER_HIP_OK;
+}
+int laser_hip_softmax_grad_last_kernel(void) { return g_last_softmax_grad_kernel; }
+// ---- the fused attention forward (attention.hip, attention_plan.h) ----------------------------------------------------------------
+namespace {
+// the limits of "Attention", each with its own text
+int attention_sizes(const char *who, int64_t bh_b, int64_t bh_h, int64_t tq, int64_t tk, int64_t d, int64_t dv, int causal) {
+  if (bh_b < 0 || bh_h < 0) return fail(LASER_HIP_E_INVALID, "%s: batch %lld, heads %lld (both >= 0)", who, (long long)bh_b, (long long)bh_h);
+  if (tq < 0) return fail(LASER_HIP_E_INVALID, "%s: Tq %lld (Tq >= 0)", who, (long long)tq);
+  if (tk < 1 || tk > LASER_HIP_ATTENTION_MAX_KEYS)
+    return fail(LASER_HIP_E_INVALID, "%s: Tk %lld outside 1..LASER_HIP_ATTENTION_MAX_KEYS = %d", who, (long long)tk, LASER_HIP_ATTENTION_MAX_KEYS);
+  if (d < 1 || d > LASER_HIP_ATTENTION_MAX_D)
+    return fail(LASER_HIP_E_INVALID, "%s: d %lld outside 1..LASER_HIP_ATTENTION_MAX_D = %d", who, (long long)d, LASER_HIP_ATTENTION_MAX_D);
+  if (dv < 1 || dv > LASER_HIP_ATTENTION_MAX_D)
+    return fail(LASER_HIP_E_INVALID, "%s: dv %lld outside 1..LASER_HIP_ATTENTION_MAX_D = %d", who, (long long)dv, LASER_HIP_ATTENTION_MAX_D);
+  if (causal && tq > tk) return fail(LASER_HIP_E_INVALID, "%s: causal with Tq %lld > Tk %lld", who, (long long)tq, (long long)tk);
+  long long p[5];
+  if (bh_h != 0 && bh_b > (1ll << 40) / bh_h) return fail(LASER_HIP_E_INVALID, "%s: batch * heads past 2^40", who);
+  if (lh_attention_plan(bh_b * bh_h, tq, tk, d, dv, causal, 1, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "%s: batch * heads * ceil(Tq / %d) past 2^40 query blocks", who, LH_ATTENTION_BM);
+  return LASER_HIP_OK;
+}
+// strides {batch, head, position} of an operand of (B, H, T, width): none negative, rows apart by at least their length
+int attention_strides(const char *name, const int64_t *st, int64_t t, int64_t width) {
+  if (!st) return fail(LASER_HIP_E_INVALID, "attention: null strides of %s", name);
+  if (st[0] < 0 || st[1] < 0 || st[2] < 0 || (t > 1 && st[2] < width))
+    return fail(LASER_HIP_E_INVALID, "attention: strides {%lld, %lld, %lld} of %s (none negative, position stride >= %lld)", (long long)st[0],
+                (long long)st[1], (long long)st[2], name, (long long)width);
+  return LASER_HIP_OK;
+}
+}  // namespace
+int laser_hip_attention_f32_dev(float *d_out, const int64_t *out_strides, const float *d_q, const int64_t *q_strides, const float *d_k,
+                                const int64_t *k_strides, const float *d_v, const int64_t *v_strides, float *d_probs,
+                                const int64_t *probs_strides, float *d_row_max, float *d_row_sum, int64_t batch, int64_t heads,
+                                int64_t tq, int64_t tk, int64_t d, int64_t dv, float scale, int causal, void *stream) {
+  if (int rc = attention_sizes("attention", batch, heads, tq, tk, d, dv, causal)) return rc;
+  if (!d_out && !d_probs && !d_row_max && !d_row_sum)
+    return fail(LASER_HIP_E_INVALID, "attention: none of out, probs, row_max and row_sum is asked for");
+  if (int rc = attention_strides("q", q_strides, tq, d)) return rc;
+  if (int rc = attention_strides("k", k_strides, tk, d)) return rc;
+  if (int rc = attention_strides("v", v_strides, tk, dv)) return rc;
+  if (d_out)
+    if (int rc = attention_strides("out", out_strides, tq, dv)) return rc;
+  if (d_probs)
+    if (int rc = attention_strides("probs", probs_strides, tq, tk)) return rc;
+  const bool any = batch > 0 && heads > 0 && tq > 0;
+  if (any && (!d_q || !d_k || !d_v)) return fail(LASER_HIP_E_INVALID, "attention: null buffer");
+  const void *outs[4] = {d_out, d_probs, d_row_max, d_row_sum}, *ins[3] = {d_q, d_k, d_v};
+  for (int i = 0; i < 4; i++) {
+    for (int j = 0; j < 3; j++)
+      if (outs[i] && outs[i] == ins[j]) return fail(LASER_HIP_E_INVALID, "attention: an output may not overlap an input");
+    for (int j = 0; j < i; j++)
+      if (outs[i] && outs[i] == outs[j]) return fail(LASER_HIP_E_INVALID, "attention: the outputs may not overlap each other");
+  }
+  if (int rc = ensure_init()) return rc;
+  if (!any) return LASER_HIP_OK;
+  HIP_TRY(launch_attention_f32(d_out, out_strides, d_q, q_strides, d_k, k_strides, d_v, v_strides, d_probs, probs_strides, d_row_max,
+                               d_row_sum, batch, heads, tq, tk, d, dv, scale, causal, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_attention_plan(int64_t bh, int64_t tq, int64_t tk, int64_t d, int64_t dv, int causal, int vec, int64_t *out5) {
+  if (!out5) return fail(LASER_HIP_E_INVALID, "attention_plan: null out5");
+  long long p[5];
+  if (lh_attention_plan(bh, tq, tk, d, dv, causal, vec, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "attention_plan: bh %lld, Tq %lld, Tk %lld, d %lld, dv %lld, causal %d outside what attention takes",
+                (long long)bh, (long long)tq, (long long)tk, (long long)d, (long long)dv, causal);
+  for (int i = 0; i < 5; i++) out5[i] = p[i];
+  return LASER_HIP_OK;
+}
+int laser_hip_attention_last_kernel(void) { return g_last_attention_kernel; }
 // ---- the embedding layer: row gather, stable grouping by id, deterministic gradient (embedding.hip, embedding_plan.h) ------------
 namespace {
 int embedding_sizes(const char *who, int64_t tokens, int64_t vocab, int64_t dim) {

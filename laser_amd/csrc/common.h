@@ -271,6 +271,17 @@ hipError_t launch_layer_norm_param_grads_f32(float *dgamma, int64_t dgamma_strid
                                              int64_t mean_stride, const float *rstd, int64_t rstd_stride, int64_t rows, int64_t n,
                                              hipStream_t s);
 extern std::atomic<int> g_last_layer_norm_kernel[3];
+// the gradient of the row softmax from its output (softmax_grad.hip; lh_softmax_grad_rows_plan in softmax_rows_plan.h picks
+// the kernel), and the fused attention forward (attention.hip; attention_plan.h is the launch plan): strides are
+// {batch, head, position} in elements; o, probs, row_max and row_sum may each be null
+hipError_t launch_softmax_grad_rows_f32(float *dx, int64_t dx_row_stride, const float *dy, int64_t dy_row_stride, const float *y,
+                                        int64_t y_row_stride, int64_t rows, int64_t n, hipStream_t s);
+extern std::atomic<int> g_last_softmax_grad_kernel;
+hipError_t launch_attention_f32(float *o, const int64_t *os, const float *q, const int64_t *qs, const float *k, const int64_t *ks,
+                                const float *v, const int64_t *vs, float *probs, const int64_t *ps, float *row_max, float *row_sum,
+                                int64_t batch, int64_t heads, int64_t tq, int64_t tk, int64_t d, int64_t dv, float scale, int causal,
+                                hipStream_t s);
+extern std::atomic<int> g_last_attention_kernel;
 // the embedding layer (embedding.hip; embedding_plan.h is the launch plan): the row gather, the stable grouping of the token
 // positions by id, and the gradient (order and starts both null: grouped here, in stream-ordered scratch).
 // g_last_embedding_kernel[what]: laser_hip_embedding_last_kernel's answers

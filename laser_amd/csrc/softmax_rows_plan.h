@@ -32,4 +32,16 @@ static inline int lh_softmax_rows_plan(const long long rows, const long long n, 
   return 0;
 }
 
+// The softmax gradient's row kernels (softmax_grad.hip) take the same three lane mappings at the same thresholds, the same
+// codes and the same grid; they gather from no table, so only the LDS differs.  out3 and the return value as above.
+static inline int lh_softmax_grad_rows_plan(const long long rows, const long long n, const int vec, long long *out3) {
+  long long p[3];
+  if (lh_softmax_rows_plan(rows, n, vec, p) != 0) return -1;
+  const int k = (int)p[0] & 3;
+  out3[0] = p[0];
+  out3[1] = p[1];
+  out3[2] = (k >= 1 ? LH_SOFTMAX_ROWS_LDS_RED : 0) + (k == 2 ? LH_SOFTMAX_ROWS_LDS_PART : 0);
+  return 0;
+}
+
 #endif  // LASER_HIP_SOFTMAX_ROWS_PLAN_H

@@ -20,6 +20,12 @@ and the embedding layer, a row gather by int32 ids with a deterministic gradient
 With matmul(..., bias=, activation=) as the forward layer, softmax_cross_entropy(grad=True) as the loss and sgd_step or
 adam_step (laser_amd/optim.py) for the update of every parameter in one launch, a multi-layer perceptron trains without
 leaving the device, every bit of every step defined by the headers.
+
+and attention, the one layer of a transformer block the list above lacks (include/laser_hip.h "Attention"):
+
+    laser_amd.attention(q, k, v, scale=None, causal=False, out=None, probs=None, stats=False)    the fused forward
+    laser_amd.attention_backward(dout, q, k, v, scale=None, causal=False, need=("q", "k", "v")) -> (dq, dk, dv)
+
 Operands are laser_amd.Tensors or torch CUDA tensors; calls are asynchronous on the current torch stream.
 """
 import ctypes as C
@@ -32,7 +38,8 @@ from .foreach import _View
 from .simd_math import _f32
 from .tensor import _stream, newTensor
 
-__all__ = ["bias_grad", "linear_backward", "layer_norm", "layer_norm_backward", "embedding", "embedding_group", "embedding_backward"]
+__all__ = ["bias_grad", "linear_backward", "layer_norm", "layer_norm_backward", "embedding", "embedding_group", "embedding_backward",
+           "attention", "attention_backward"]
 
 
 def _act(activation):
@@ -318,3 +325,176 @@ def embedding_backward(dy, idx, vocab, out=None, group=None):
         _lib.check(_lib.lib().laser_hip_embedding_grad_f32_dev(_ptr(vdw), dws, _ptr(vdy), dys, _ptr(vi), _ptr(vo), _ptr(vs), tokens, vocab,
                                                                dim, _stream()))
     return out
+
+
+# ---- attention ----------------------------------------------------------------------------------------------------------------
+ATTENTION_MAX_D = 128
+ATTENTION_MAX_KEYS = 65536
+
+
+def _attn_view(fn, name, obj, width=None):
+    """(view, B, H, T, width, (batch, head, position strides)) of an attention operand: a 3-D (BH, T, width) or 4-D
+    (B, H, T, width) device tensor or view of any outer strides, the feature index unit-stride.  A 3-D operand is B = BH
+    batches of one head."""
+    v = _f32(name, obj)
+    if v.rank not in (3, 4):
+        raise ValueError(f"{fn}: {name} has rank {v.rank} (a 3-D (BH, T, d) or 4-D (B, H, T, d) tensor or view is needed)")
+    w = v.shape[-1]
+    if width is not None and w != width:
+        raise ValueError(f"{fn}: {name} has {w} features, {width} are needed")
+    if w > 1 and v.strides[-1] != 1:
+        raise ValueError(f"{fn}: {name} has feature stride {v.strides[-1]} (1 is needed)")
+    if any(s < 0 for s in v.strides[:-1]):
+        raise ValueError(f"{fn}: {name} has strides {v.strides} (negative strides are not taken)")
+    t = v.shape[-2]
+    if v.rank == 3:
+        b, h, st = v.shape[0], 1, (v.strides[0], 0, v.strides[1])
+    else:
+        b, h, st = v.shape[0], v.shape[1], (v.strides[0], v.strides[1], v.strides[2])
+    if t > 1 and st[2] < w:
+        raise ValueError(f"{fn}: {name} has position stride {st[2]} below its {w} features")
+    return v, b, h, t, w, st
+
+
+def _attn_scale(fn, scale, d):
+    """float32(1 / sqrt(float64(d))) by default"""
+    s = np.float32(1.0 / np.sqrt(np.float64(d))) if scale is None else np.float32(scale)
+    return float(s)
+
+
+def _i64x3(st):
+    return (C.c_int64 * 3)(*st)
+
+
+def attention(q, k, v, scale=None, causal=False, out=None, probs=None, stats=False):
+    """O = softmax(scale * Q K^T) V per (batch, head) slice in one fused kernel: the scores never reach global memory
+    (include/laser_hip.h "Attention" defines every bit: scores as k-ascending fmaf chains, the row softmax of
+    laser_amd.softmax on the visible scores, P V in laser-order).  `q` is (B, H, Tq, d) or (BH, Tq, d), `k` (.., Tk, d),
+    `v` (.., Tk, dv): device tensors or views of any outer strides with unit feature stride, so slices of one fused
+    projection output (B, T, 3, H, d) need no copy.  1 <= d, dv <= 128, 1 <= Tk <= 65536.  scale=None:
+    float32(1 / sqrt(d)).  causal: row i sees keys [0, i + (Tk - Tq) + 1); Tq <= Tk is needed.
+    out: None for a fresh Tensor of q's leading shape + (dv,), a destination, or False for no O (probs or stats must then
+    be asked for; the P V sweep is skipped).  probs: None / False for none, True for a fresh (.., Tq, Tk) Tensor, or a
+    destination; masked positions are written as +0.  stats=True: also the row maxima and row sums, fresh contiguous
+    Tensors of q's leading shape.  Returns O alone, or (O, probs, row_max, row_sum) when probs or stats is asked for (None
+    where not).  What is asked for has the same bits whatever else is asked for."""
+    fn = "attention"
+    vq, b, h, tq, d, qs = _attn_view(fn, "q", q)
+    vk, bk, hk, tk, _, ks = _attn_view(fn, "k", k, d)
+    vv, bv, hv, tkv, dv, vs = _attn_view(fn, "v", v)
+    if vk.rank != vq.rank or vv.rank != vq.rank or (bk, hk) != (b, h) or (bv, hv) != (b, h):
+        raise ValueError(f"{fn}: q, k and v have leading shapes {vq.shape[:-2]}, {vk.shape[:-2]} and {vv.shape[:-2]}")
+    if tkv != tk:
+        raise ValueError(f"{fn}: k has {tk} positions, v has {tkv}")
+    if not 1 <= d <= ATTENTION_MAX_D or not 1 <= dv <= ATTENTION_MAX_D:
+        raise ValueError(f"{fn}: d = {d}, dv = {dv} (1 .. {ATTENTION_MAX_D})")
+    if not 1 <= tk <= ATTENTION_MAX_KEYS:
+        raise ValueError(f"{fn}: Tk = {tk} (1 .. {ATTENTION_MAX_KEYS})")
+    if causal and tq > tk:
+        raise ValueError(f"{fn}: causal with Tq = {tq} > Tk = {tk}")
+    scale = _attn_scale(fn, scale, d)
+    lead = vq.shape[:-2]
+    want_probs = probs is not None and probs is not False
+    if out is False and not want_probs and not stats:
+        raise ValueError(f"{fn}: nothing is asked for (out=False needs probs or stats)")
+    # (what was passed in is checked before anything fresh is allocated)
+    if out is not None and out is not False:
+        vo, bo, ho, to, _, _ = _attn_view(fn, "out", out, dv)
+        if vo.rank != vq.rank or (bo, ho, to) != (b, h, tq):
+            raise ValueError(f"{fn}: out has shape {vo.shape}, {lead + (tq, dv)} is needed")
+    if want_probs and probs is not True:
+        vp, bp, hp, tp, _, _ = _attn_view(fn, "probs", probs, tk)
+        if vp.rank != vq.rank or (bp, hp, tp) != (b, h, tq):
+            raise ValueError(f"{fn}: probs has shape {vp.shape}, {lead + (tq, tk)} is needed")
+    vo, os_, vp, ps = None, (0, 0, 0), None, (0, 0, 0)
+    if out is False:
+        out = None
+    else:
+        if out is None:
+            out = newTensor(np.float32, *(lead + (tq, dv)))
+        vo, _, _, _, _, os_ = _attn_view(fn, "out", out, dv)
+    if want_probs:
+        if probs is True:
+            probs = newTensor(np.float32, *(lead + (tq, tk)))
+        vp, _, _, _, _, ps = _attn_view(fn, "probs", probs, tk)
+    else:
+        probs = None
+    rmax = newTensor(np.float32, *(lead + (tq,))) if stats else None
+    rsum = newTensor(np.float32, *(lead + (tq,))) if stats else None
+    vm = _f32("row_max", rmax) if stats else None
+    vs_ = _f32("row_sum", rsum) if stats else None
+    if b * h * tq > 0:
+        _lib.check(_lib.lib().laser_hip_attention_f32_dev(_ptr(vo), _i64x3(os_), _ptr(vq), _i64x3(qs), _ptr(vk), _i64x3(ks), _ptr(vv),
+                                                          _i64x3(vs), _ptr(vp), _i64x3(ps), _ptr(vm), _ptr(vs_), b, h, tq, tk, d, dv,
+                                                          scale, 1 if causal else 0, _stream()))
+    if want_probs or stats:
+        return out, probs, rmax, rsum
+    return out
+
+
+def _attn_gemm(b, h, m, n, kk, alpha, a_st, a_ptr, b_st, b_ptr, c_st, c_ptr):
+    """C[b, h] = alpha * A[b, h] B[b, h] for every slice on gemm_strided_batched in the current float mode: strides are
+    (batch, head, row, column) in elements.  One launch when the (batch, head) dims of all three collapse into one batch
+    stride, else one per batch."""
+    L = _lib.lib()
+
+    def one(batch, off, pick):
+        _lib.check(L.laser_hip_gemm_strided_batched_f32_dev(
+            batch, m, n, kk, C.c_float(alpha), C.c_void_p(a_ptr + 4 * off(a_st)), a_st[2], a_st[3], pick(a_st),
+            C.c_void_p(b_ptr + 4 * off(b_st)), b_st[2], b_st[3], pick(b_st), C.c_float(0.0),
+            C.c_void_p(c_ptr + 4 * off(c_st)), c_st[2], c_st[3], pick(c_st), _stream()))
+
+    if b * h == 0 or m == 0 or n == 0:
+        return
+    if h == 1 or b == 1 or all(st[0] == st[1] * h for st in (a_st, b_st, c_st)):
+        one(b * h, lambda st: 0, (lambda st: st[0]) if h == 1 else (lambda st: st[1]))
+    else:
+        for i in range(b):
+            one(h, lambda st, i=i: i * st[0], lambda st: st[1])
+
+
+def attention_backward(dout, q, k, v, scale=None, causal=False, need=("q", "k", "v")):
+    """The gradients of attention(q, k, v, scale, causal) from the incoming gradient `dout` (shape of O), as a composition
+    of steps that each have defined bits (include/laser_hip.h "Attention"): P from the fused forward kernel (probs only);
+    dV = P^T dO; dP = dO V^T; dS = softmax_backward(dP, P) over the full Tk (masked positions give +-0); dQ = scale * (dS K);
+    dK = scale * (dS^T Q).  The four products run on gemm_strided_batched in the current float mode, the transposes as
+    strides and `scale` as the GEMM's alpha; no operand is copied.  Memory: B*H*Tq*Tk floats twice (P, and dP / dS in
+    place), freed on return.  `need`: which of "q", "k", "v" to compute; what is asked for has the same bits whatever else
+    is asked for.  Returns (dq, dk, dv), fresh contiguous Tensors of the operands' shapes, None where not asked for."""
+    fn = "attention_backward"
+    need = (need,) if isinstance(need, str) else tuple(need)
+    if not need or any(x not in ("q", "k", "v") for x in need):
+        raise ValueError(f'{fn}: need = {need!r} (a non-empty subset of ("q", "k", "v"))')
+    vq, b, h, tq, d, qs = _attn_view(fn, "q", q)
+    vk, _, _, tk, _, ks = _attn_view(fn, "k", k, d)
+    vv, _, _, _, dv, vs = _attn_view(fn, "v", v)
+    vdo, bo, ho, to, _, dos = _attn_view(fn, "dout", dout, dv)
+    if vdo.rank != vq.rank or (bo, ho, to) != (b, h, tq):
+        raise ValueError(f"{fn}: dout has shape {vdo.shape}, {vq.shape[:-1] + (dv,)} is needed")
+    sc = _attn_scale(fn, scale, d)
+    lead = vq.shape[:-2]
+    probs = newTensor(np.float32, *(lead + (tq, tk)))
+    attention(q, k, v, scale=scale, causal=causal, out=False, probs=probs)       # (checks q, k and v against each other)
+    vp = _f32("probs", probs)
+    pst = (h * tq * tk, tq * tk, tk, 1)                                          # (batch, head, row, column)
+    four = lambda st: (st[0], st[1], st[2], 1)
+    tr = lambda st: (st[0], st[1], st[3], st[2])
+    dq = dk = dvv = None
+    if "v" in need:
+        dvv = newTensor(np.float32, *(lead + (tk, dv)))
+        _attn_gemm(b, h, tk, dv, tq, 1.0, tr(pst), vp.ptr, four(dos), vdo.ptr, (h * tk * dv, tk * dv, dv, 1),
+                   _f32("dv", dvv).ptr)
+    if "q" in need or "k" in need:
+        ds = newTensor(np.float32, *(lead + (tq, tk)))
+        vds = _f32("ds", ds)
+        _attn_gemm(b, h, tq, tk, dv, 1.0, four(dos), vdo.ptr, tr(four(vs)), vv.ptr, pst, vds.ptr)
+        from .simd_math import softmax_backward
+        if b * h * tq > 0:
+            softmax_backward(ds, probs, out=ds)
+        if "q" in need:
+            dq = newTensor(np.float32, *(lead + (tq, d)))
+            _attn_gemm(b, h, tq, d, tk, sc, pst, vds.ptr, four(ks), vk.ptr, (h * tq * d, tq * d, d, 1), _f32("dq", dq).ptr)
+        if "k" in need:
+            dk = newTensor(np.float32, *(lead + (tk, d)))
+            _attn_gemm(b, h, tk, d, tq, sc, tr(pst), vds.ptr, four(qs), vq.ptr, (h * tk * d, tk * d, d, 1), _f32("dk", dk).ptr)
+    return dq, dk, dvv

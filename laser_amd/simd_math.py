@@ -6,7 +6,8 @@ cosine (include/laser_hip.h "Sine and cosine"), float32:
     laser_amd.exp(t)        lexp of every element: the exported SIMD `exp*` of the reference, bit for bit
     laser_amd.softmax(t)    softmax over the rows of a 2-D tensor, summed in the fixed order of the reductions
     laser_amd.softmax(t, axis=k)   the same along any axis of a tensor of rank 1 .. 6: bit for bit what the row form gives the
-                            same values as rows (not built: float64, backward)
+                            same values as rows (not built: float64)
+    laser_amd.softmax_backward(dy, y)     the gradient from the softmax's OUTPUT: y * (dy - reduce_sum(dy * y)) per row
     laser_amd.log(t)        llog of every element: the bit-defined logarithm of laser_amd/csrc/log_core.h
     laser_amd.logsumexp(t)  one value per row of a 2-D tensor: max + llog(sum), max and sum exactly the softmax's
     laser_amd.log_softmax(t)       (x - max) - llog(sum) over the rows of a 2-D tensor
@@ -198,6 +199,46 @@ def softmax(t, out=None, axis=None):
     # a single row has no row stride to speak of
     ds, ss = (dst.strides[0], src.strides[0]) if rows > 1 else (n, n)
     _lib.check(_lib.lib().laser_hip_softmax_rows_f32_dev(C.c_void_p(dst.ptr), ds, C.c_void_p(src.ptr), ss, rows, n, _stream()))
+    return out
+
+
+def _grad_rows(name, v, shape=None):
+    """(rows, row stride, n) of a softmax_backward operand: the last axis unit-stride, the leading dims one stride"""
+    if v.rank < 2:
+        raise ValueError(f"softmax_backward: {name} has rank {v.rank} (rows: rank 2 or more is needed)")
+    if shape is not None and v.shape != shape:
+        raise ValueError(f"softmax_backward: {name} has shape {v.shape}, dy has {shape}")
+    n = v.shape[-1]
+    if n < 1:
+        raise ValueError("softmax_backward: empty rows")
+    if n != 1 and v.strides[-1] != 1:
+        raise ValueError(f"softmax_backward: {name} has last stride {v.strides[-1]} (the elements of a row must be contiguous)")
+    lead = _collapse(list(zip(v.shape[:-1], v.strides[:-1])))
+    if lead is None:
+        raise ValueError(f"softmax_backward: the leading dims of {name} (shape {v.shape}, strides {v.strides}) do not collapse "
+                         "into one row stride (make it contiguous)")
+    rows, stride = lead
+    return rows, (stride if rows > 1 and stride is not None else n), n
+
+
+def softmax_backward(dy, y, out=None):
+    """The gradient of softmax over the last axis from the incoming gradient `dy` and the softmax's OUTPUT `y`:
+    D = reduce_sum(dy * y) per row (every product rounded, the sum in the order of the reductions), then
+    dx = y * (dy - D), a rounded subtraction and a rounded multiplication -- a row's result depends on its values and length
+    alone.  `dy`, `y` and `out` are device tensors or views of one shape, rank 2 or more, the last axis contiguous and the
+    leading dims collapsing into one row stride; out=None: a fresh Tensor; `out` may be `dy` or `y`.  1 <= n <= 2^26."""
+    vdy = _f32("dy", dy)
+    rows, dys, n = _grad_rows("dy", vdy)
+    vy = _f32("y", y)
+    _, ys, _ = _grad_rows("y", vy, vdy.shape)
+    if out is None:
+        out = newTensor(np.float32, *vdy.shape)
+    vdx = _f32("out", out)
+    _, dxs, _ = _grad_rows("out", vdx, vdy.shape)
+    if rows == 0:
+        return out
+    _lib.check(_lib.lib().laser_hip_softmax_grad_rows_f32_dev(C.c_void_p(vdx.ptr), dxs, C.c_void_p(vdy.ptr), dys, C.c_void_p(vy.ptr), ys,
+                                                              rows, n, _stream()))
     return out
 
 

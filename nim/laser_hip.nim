@@ -752,6 +752,53 @@ proc layerNormBackward*(dx, dgamma, dbeta: DevicePtr[float32], dy, x, mean, rstd
   ## nil (not wanted) but not all; gamma may be nil; dx may be dy or x; rows <= 2^26 with a parameter gradient
   check laser_hip_layer_norm_grad_f32_dev(cast[ptr float32](dx), int64(n), cast[ptr float32](dgamma), 1, cast[ptr float32](dbeta), 1, cast[ptr float32](dy), int64(n), cast[ptr float32](x), int64(n), cast[ptr float32](mean), 1, cast[ptr float32](rstd), 1, cast[ptr float32](gamma), 1, int64(rows), int64(n), stream)
 
+# ---- the softmax gradient and attention (include/laser_hip.h "Softmax gradient", "Attention") -------------------------------
+# the gradient of the row softmax from its OUTPUT; the fused attention forward O = softmax(scale * Q K^T) V with the scores
+# never in global memory; and the backward composed from the forward's P, the softmax gradient and the batched GEMM
+proc laser_hip_softmax_grad_rows_f32_dev*(dx: ptr float32, dxRowStride: int64, dy: ptr float32, dyRowStride: int64, y: ptr float32, yRowStride: int64, rows: int64, n: int64, stream: pointer): cint {.lh, importc: "laser_hip_softmax_grad_rows_f32_dev".}
+proc laser_hip_softmax_grad_plan*(rows: int64, n: int64, vec: cint, out3: ptr int64): cint {.lh, importc: "laser_hip_softmax_grad_plan".}
+proc laser_hip_softmax_grad_last_kernel*(): cint {.lh, importc: "laser_hip_softmax_grad_last_kernel".}
+proc laser_hip_attention_f32_dev*(o: ptr float32, oStrides: ptr int64, q: ptr float32, qStrides: ptr int64, k: ptr float32, kStrides: ptr int64, v: ptr float32, vStrides: ptr int64, probs: ptr float32, probsStrides: ptr int64, rowMax: ptr float32, rowSum: ptr float32, batch: int64, heads: int64, tq: int64, tk: int64, d: int64, dv: int64, scale: float32, causal: cint, stream: pointer): cint {.lh, importc: "laser_hip_attention_f32_dev".}
+proc laser_hip_attention_plan*(bh: int64, tq: int64, tk: int64, d: int64, dv: int64, causal: cint, vec: cint, out5: ptr int64): cint {.lh, importc: "laser_hip_attention_plan".}
+proc laser_hip_attention_last_kernel*(): cint {.lh, importc: "laser_hip_attention_last_kernel".}
+proc laser_hip_gemm_strided_batched_f32_dev(batch, M, N, K: int, alpha: float32, A: pointer, rsA, csA, bsA: int, B: pointer, rsB, csB, bsB: int, beta: float32, C: pointer, rsC, csC, bsC: int, stream: pointer): cint {.lh, importc: "laser_hip_gemm_strided_batched_f32_dev".}
+
+proc softmaxBackward*(dx: DevicePtr[float32], dxRowStride: int, dy: DevicePtr[float32], dyRowStride: int, y: DevicePtr[float32], yRowStride: int, rows, n: Natural, stream: pointer = nil) =
+  ## dx[r, j] = y[r, j] * (dy[r, j] - D[r]) with D[r] = the sum of the rounded products dy[r, :] * y[r, :] in the order of
+  ## reduce_sum; y is the softmax's OUTPUT; dx may be dy or y (equal row strides); 1 <= n <= 2^26
+  check laser_hip_softmax_grad_rows_f32_dev(cast[ptr float32](dx), int64(dxRowStride), cast[ptr float32](dy), int64(dyRowStride), cast[ptr float32](y), int64(yRowStride), int64(rows), int64(n), stream)
+
+from std/math import sqrt
+proc attentionDefaultScale*(d: Natural): float32 = float32(1.0 / sqrt(float64(d)))
+
+proc attention*(o, probs, rowMax, rowSum: DevicePtr[float32], q, k, v: DevicePtr[float32], bh, tq, tk, d, dv: Natural, scale: float32, causal = false, stream: pointer = nil) =
+  ## contiguous row-major slices: q (bh, tq, d), k (bh, tk, d), v (bh, tk, dv) -> o (bh, tq, dv), probs (bh, tq, tk), rowMax and
+  ## rowSum (bh, tq); each output may be nil (not wanted) but not all; with o nil the P V sweep is skipped.  causal: row i sees
+  ## keys [0, i + (tk - tq) + 1), tq <= tk.  1 <= d, dv <= 128, 1 <= tk <= 65536.  Views of other strides (slices of a fused
+  ## (B, T, 3, H, d) projection) go through laser_hip_attention_f32_dev with their {batch, head, position} strides.
+  var os = [int64(tq * dv), 0'i64, int64(dv)]
+  var qs = [int64(tq * d), 0'i64, int64(d)]
+  var ks = [int64(tk * d), 0'i64, int64(d)]
+  var vs = [int64(tk * dv), 0'i64, int64(dv)]
+  var ps = [int64(tq * tk), 0'i64, int64(tk)]
+  check laser_hip_attention_f32_dev(cast[ptr float32](o), addr os[0], cast[ptr float32](q), addr qs[0], cast[ptr float32](k), addr ks[0], cast[ptr float32](v), addr vs[0], cast[ptr float32](probs), addr ps[0], cast[ptr float32](rowMax), cast[ptr float32](rowSum), int64(bh), 1, int64(tq), int64(tk), int64(d), int64(dv), scale, cint(ord(causal)), stream)
+
+proc attentionBackward*(dq, dk, dvOut: DevicePtr[float32], probs, ds: DevicePtr[float32], dout, q, k, v: DevicePtr[float32], bh, tq, tk, d, dv: Natural, scale: float32, causal = false, stream: pointer = nil) =
+  ## the gradients of `attention` for contiguous slices, as the header composes them: probs (bh, tq, tk) <- P from the forward
+  ## kernel; dvOut = P^T dO; ds (bh, tq, tk) <- dO V^T, then softmaxBackward in place; dq = scale * (dS K); dk = scale * (dS^T Q)
+  ## on gemm_strided_batched in the current float mode, the transposes as strides.  probs and ds are scratch of bh * tq * tk
+  ## floats each; dq, dk and dvOut may each be nil (not wanted)
+  attention(DevicePtr[float32](nil), probs, DevicePtr[float32](nil), DevicePtr[float32](nil), q, k, v, bh, tq, tk, d, dv, scale, causal, stream)
+  if not pointer(dvOut).isNil:
+    check laser_hip_gemm_strided_batched_f32_dev(bh, tk, dv, tq, 1'f32, pointer(probs), 1, tk, tq * tk, pointer(dout), dv, 1, tq * dv, 0'f32, pointer(dvOut), dv, 1, tk * dv, stream)
+  if pointer(dq).isNil and pointer(dk).isNil: return
+  check laser_hip_gemm_strided_batched_f32_dev(bh, tq, tk, dv, 1'f32, pointer(dout), dv, 1, tq * dv, pointer(v), 1, dv, tk * dv, 0'f32, pointer(ds), tk, 1, tq * tk, stream)
+  softmaxBackward(ds, tk, ds, tk, probs, tk, bh * tq, tk, stream)
+  if not pointer(dq).isNil:
+    check laser_hip_gemm_strided_batched_f32_dev(bh, tq, d, tk, scale, pointer(ds), tk, 1, tq * tk, pointer(k), d, 1, tk * d, 0'f32, pointer(dq), d, 1, tq * d, stream)
+  if not pointer(dk).isNil:
+    check laser_hip_gemm_strided_batched_f32_dev(bh, tk, d, tq, scale, pointer(ds), 1, tk, tq * tk, pointer(q), d, 1, tq * d, 0'f32, pointer(dk), d, 1, tk * d, stream)
+
 # ---- embedding (include/laser_hip.h "Embedding"): row gather by int32 ids, stable grouping, deterministic gradient --------
 # row-major device matrices with unit column stride, contiguous rows; ids are int32 (-1: a row of +0 and no gradient; any
 # other id outside [0, vocab): a row of NaN and no gradient)
