@@ -441,7 +441,12 @@ int laser_hip_storage_set_zero(void *d_buffer, int64_t bytes, void *stream);
  * download run on the NULL stream, which does NOT wait for non-blocking streams (PyTorch's side streams, any
  * hipStreamNonBlocking stream): a caller that computes on its own stream uses these so that the zero fill precedes
  * the first kernel on that stream, an upload follows the last reader and a download follows the producer.  Upload and
- * download are complete when the call returns. */
+ * download are complete when the call returns.  storage_alloc_stream and storage_set_zero never synchronise the host.
+ * A storage belongs to the stream it was allocated on (the NULL stream for the plain storage_alloc): storage_free
+ * records, on that stream, the point after which a cached block may be handed out again, and the next storage_alloc_stream
+ * of the block is ordered behind that point on the device (on the same stream by stream order alone).  A caller that
+ * also uses a storage on ANOTHER stream orders that use before the free itself (an event, or a host wait), as with any
+ * stream-ordered allocator. */
 int laser_hip_storage_alloc_stream(void **d_raw_buffer, int64_t bytes, void *stream);
 int laser_hip_storage_upload_stream(void *d_dst, const void *host_src, int64_t bytes, void *stream);
 int laser_hip_storage_download_stream(void *host_dst, const void *d_src, int64_t bytes, void *stream);

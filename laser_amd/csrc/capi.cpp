@@ -516,17 +516,29 @@ constexpr size_t kStorageCacheMax = (size_t)32 << 30;
 // live blocks: ptr -> key; free list keyed by the same key = rounded size | device ordinal << 56 (a block is only
 // ever handed back to a caller on the device it was allocated on)
 std::unordered_map<void *, size_t> g_live_storage;
-std::unordered_map<size_t, std::vector<void *>> g_free_storage;
+// A cached block remembers the stream it was allocated on and an event recorded on that stream when it was freed: whoever
+// takes the block next is ordered behind that event ON THE DEVICE (nothing, on the same stream), never by a host wait.
+// done == nullptr: the event could not be made or recorded -- the taker falls back to hipDeviceSynchronize.
+struct FreeBlock {
+  void *p;
+  hipStream_t owner;
+  hipEvent_t done;
+};
+std::unordered_map<void *, hipStream_t> g_storage_owner;
+std::unordered_map<size_t, std::vector<FreeBlock>> g_free_storage;
+inline void free_block_release(const FreeBlock &b) {
+  if (b.done) (void)hipEventDestroy(b.done);
+  (void)hipFree(b.p);
+  g_live_storage.erase(b.p);
+  g_storage_owner.erase(b.p);
+}
 inline size_t storage_key(size_t rounded, int dev) { return rounded | ((size_t)(dev & 0xff) << 56); }
 inline size_t storage_size(size_t key) { return key & (((size_t)1 << 56) - 1); }
 size_t g_free_storage_bytes = 0;
 void storage_trim() {
   std::lock_guard<std::mutex> lk(g_mu);
   for (auto &kv : g_free_storage)
-    for (void *p : kv.second) {
-      (void)hipFree(p);
-      g_live_storage.erase(p);
-    }
+    for (const FreeBlock &b : kv.second) free_block_release(b);
   g_free_storage.clear();
   g_free_storage_bytes = 0;
 }
@@ -710,10 +722,7 @@ int laser_hip_finalize(void) {
   panel_cache_clear_locked();
   if (g_ctx.device >= 0) (void)hipSetDevice(g_ctx.device);
   for (auto &kv : g_free_storage)
-    for (void *p : kv.second) {
-      (void)hipFree(p);
-      g_live_storage.erase(p);
-    }
+    for (const FreeBlock &b : kv.second) free_block_release(b);
   g_free_storage.clear();
   g_free_storage_bytes = 0;
   g_ctx.ready = false;
@@ -1050,8 +1059,8 @@ static int conv2d_api_dev(float *dout, const float *din, int64_t iN, int64_t iC,
                   dws, s, dbias, act);
   }
   if (own) {
-    const hipError_t e = hipFreeAsync(own, s);
-    if (rc == LASER_HIP_OK && e != hipSuccess) rc = fail(LASER_HIP_E_HIP, "hipFreeAsync: %s", hipGetErrorString(e));
+    const hipError_t e = scratch_free_async(own, s);
+    if (rc == LASER_HIP_OK && e != hipSuccess) rc = fail(LASER_HIP_E_HIP, "scratch_free_async: %s", hipGetErrorString(e));
   }
   return rc;
 }
@@ -1159,18 +1168,38 @@ static int storage_alloc(void **d, int64_t bytes, hipStream_t stream, bool order
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   const size_t key = storage_key(want, dev);
+  FreeBlock taken = {nullptr, nullptr, nullptr};
   {
     std::lock_guard<std::mutex> lk(g_mu);
     auto it = g_free_storage.find(key);
     if (it != g_free_storage.end() && !it->second.empty()) {
-      *d = it->second.back();
-      it->second.pop_back();
+      // the newest block this stream freed itself, if there is one (no wait at all), else the newest of the size
+      auto &list = it->second;
+      size_t pick = list.size() - 1;
+      for (size_t k = list.size(); ordered && k-- > 0;)
+        if (list[k].owner == stream && list[k].done) {
+          pick = k;
+          break;
+        }
+      taken = list[pick];
+      *d = taken.p;
+      list.erase(list.begin() + (ptrdiff_t)pick);
       g_free_storage_bytes -= want;
+      g_storage_owner[*d] = ordered ? stream : nullptr;
     }
   }
-  // a recycled block may still be read by work queued on any stream when its owner dropped it (hipFree would have
-  // waited for the device; the free list does not): wait here, where it is only paid on reuse
-  if (*d) HIP_TRY(hipDeviceSynchronize());
+  // A recycled block may still be read by work queued on its owner's stream when the owner dropped it (hipFree would have
+  // waited for the device; the free list does not).  The stream-ordered form stays asynchronous: the same stream needs
+  // nothing (its zero fill queues behind that work), another stream waits for the event of the free on the device.  The
+  // plain form waits for that event on the host, as it waits for its zero fill.
+  if (*d) {
+    hipError_t e = hipSuccess;
+    if (!taken.done) e = hipDeviceSynchronize();
+    else if (!ordered) e = hipEventSynchronize(taken.done);
+    else if (stream != taken.owner) e = hipStreamWaitEvent(stream, taken.done, 0);
+    if (taken.done) (void)hipEventDestroy(taken.done);
+    if (e != hipSuccess) return fail(LASER_HIP_E_HIP, "storage_alloc (reuse): %s", hipGetErrorString(e));
+  }
   if (!*d) {
     hipError_t e = hipMalloc(d, want);  // hipMalloc is 256-byte aligned >= LASER_MEM_ALIGN
     if (e != hipSuccess) {             // out of memory: give the cached blocks back and retry once
@@ -1180,6 +1209,7 @@ static int storage_alloc(void **d, int64_t bytes, hipStream_t stream, bool order
     if (e != hipSuccess) return fail(LASER_HIP_E_HIP, "hipMalloc(%zu): %s", want, hipGetErrorString(e));
     std::lock_guard<std::mutex> lk(g_mu);
     g_live_storage[*d] = key;
+    g_storage_owner[*d] = ordered ? stream : nullptr;
   }
   // zero fill (allocShared0): ordered on the caller's stream -- the stream the tensor's first kernel will run on --
   // or, for the plain entry point, completed before returning (PyTorch-style side streams are non-blocking: a fill
@@ -1199,11 +1229,22 @@ int laser_hip_storage_free(void *d) {
   if (it == g_live_storage.end()) return fail(LASER_HIP_E_INVALID, "storage_free: not a laser_hip storage");
   const size_t key = it->second, sz = storage_size(key);
   if (g_free_storage_bytes + sz <= kStorageCacheMax) {
-    g_free_storage[key].push_back(d);
+    FreeBlock b = {d, nullptr, nullptr};
+    auto ow = g_storage_owner.find(d);
+    if (ow != g_storage_owner.end()) b.owner = ow->second;
+    // everything queued so far on the owner's stream may still use the block
+    if (hipEventCreateWithFlags(&b.done, hipEventDisableTiming) != hipSuccess) b.done = nullptr;
+    if (b.done && hipEventRecord(b.done, b.owner) != hipSuccess) {
+      (void)hipEventDestroy(b.done);
+      b.done = nullptr;
+    }
+    if (!b.done) (void)hipGetLastError();
+    g_free_storage[key].push_back(b);
     g_free_storage_bytes += sz;
     return LASER_HIP_OK;
   }
   g_live_storage.erase(it);
+  g_storage_owner.erase(d);
   HIP_TRY(hipFree(d));
   return LASER_HIP_OK;
 }

@@ -3,8 +3,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <atomic>
 #include <functional>
+#include <map>
+#include <mutex>
+#include <unordered_map>
+#include <utility>
+#include <vector>
 
 #include "gemm_args.h"
 
@@ -15,13 +21,90 @@ namespace laser_hip {
 // synchronisation hands a pool's free memory back to the driver and the next call pays for mapping it again (a packed 4096^3 product
 // timed 4 calls per synchronise lost 60 us per call to that: profiles/r04/colmajor_a_probe_v1.jsonl against configs_v5.jsonl).  The
 // device's DEFAULT pool belongs to the host application and its other libraries: its threshold is never touched.
-// Freed with hipFreeAsync like any stream-ordered allocation.  A runtime that cannot make a pool: plain hipMallocAsync.
+// Given back with scratch_free_async (below).  A runtime that cannot make a pool: plain hipMallocAsync.
 struct ScratchPools {
   std::atomic<hipMemPool_t> pool[64] = {};
   std::atomic<unsigned long long> failed{0};     // one bit per device ordinal whose pool could not be made
 };
 inline ScratchPools g_scratch_pools;
+inline hipError_t scratch_pool_alloc(void **p, size_t bytes, hipStream_t s);
+
+// In front of the pool, a cache of idle blocks per (device, stream).  A block that scratch_free_async takes back is handed
+// out again ONLY on the stream it was freed on, so stream order alone separates its users: no event, no wait, no runtime call.
+// It is there because hipFreeAsync waits ON THE HOST when the block it frees was allocated from a free that has not completed
+// yet -- the second scratch-taking call queued on a stream that is still busy with (or blocked before) the first would stall
+// its caller until the stream drains, which `_dev` calls never do (seen: two reductions queued behind a blocked stream, the
+// second returned only when the stream ran; tests/test_gpu_stream_order.py).  A stream that is being captured bypasses the
+// cache: its allocations and frees become nodes of the graph, as before.  Idle blocks above kScratchIdleMax go back to the pool.
+struct ScratchCache {
+  struct Block {
+    void *p;
+    size_t bytes;
+  };
+  std::mutex mu;
+  std::map<std::pair<int, hipStream_t>, std::vector<Block>> idle;
+  std::unordered_map<void *, size_t> owned;     // every block handed out through the cache or idle in it -> its size
+  size_t idle_bytes = 0;
+};
+inline ScratchCache g_scratch_cache;
+constexpr size_t kScratchIdleMax = (size_t)4 << 30;
+inline bool scratch_capturing(hipStream_t s) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess) {
+    (void)hipGetLastError();
+    return true;      // (unknown: the conservative path)
+  }
+  return cap != hipStreamCaptureStatusNone;
+}
 inline hipError_t scratch_alloc_async(void **p, size_t bytes, hipStream_t s) {
+  if (scratch_capturing(s)) return scratch_pool_alloc(p, bytes, s);
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return scratch_pool_alloc(p, bytes, s);
+  const size_t want = (std::max<size_t>(bytes, 1) + 4095) & ~(size_t)4095;
+  {
+    std::lock_guard<std::mutex> lk(g_scratch_cache.mu);
+    auto it = g_scratch_cache.idle.find({dev, s});
+    if (it != g_scratch_cache.idle.end()) {
+      auto &list = it->second;
+      size_t best = list.size();
+      for (size_t k = 0; k < list.size(); k++)      // the smallest block that fits, and not one far too large
+        if (list[k].bytes >= want && list[k].bytes <= 4 * want + ((size_t)1 << 20) && (best == list.size() || list[k].bytes < list[best].bytes))
+          best = k;
+      if (best != list.size()) {
+        *p = list[best].p;
+        g_scratch_cache.idle_bytes -= list[best].bytes;
+        list.erase(list.begin() + (ptrdiff_t)best);
+        return hipSuccess;
+      }
+    }
+  }
+  const hipError_t e = scratch_pool_alloc(p, want, s);
+  if (e == hipSuccess) {
+    std::lock_guard<std::mutex> lk(g_scratch_cache.mu);
+    g_scratch_cache.owned[*p] = want;
+  }
+  return e;
+}
+// The end of a scratch block's use on `s`, the stream it was allocated on: everything that reads or writes it is queued.
+inline hipError_t scratch_free_async(void *p, hipStream_t s) {
+  if (p == nullptr) return hipSuccess;
+  {
+    std::lock_guard<std::mutex> lk(g_scratch_cache.mu);
+    auto it = g_scratch_cache.owned.find(p);
+    if (it != g_scratch_cache.owned.end()) {
+      int dev = 0;
+      const size_t bytes = it->second;
+      if (!scratch_capturing(s) && hipGetDevice(&dev) == hipSuccess && g_scratch_cache.idle_bytes + bytes <= kScratchIdleMax) {
+        g_scratch_cache.idle[{dev, s}].push_back({p, bytes});
+        g_scratch_cache.idle_bytes += bytes;
+        return hipSuccess;
+      }
+      g_scratch_cache.owned.erase(it);
+    }
+  }
+  return hipFreeAsync(p, s);
+}
+inline hipError_t scratch_pool_alloc(void **p, size_t bytes, hipStream_t s) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || (g_scratch_pools.failed.load(std::memory_order_relaxed) >> dev & 1ull))
     return hipMallocAsync(p, bytes, s);
@@ -52,6 +135,16 @@ inline hipError_t scratch_alloc_async(void **p, size_t bytes, hipStream_t s) {
 }
 // laser_hip_finalize: the pools go (every device is idle by then; what they kept returns to the driver)
 inline void scratch_pools_trim() {
+  {
+    std::lock_guard<std::mutex> lk(g_scratch_cache.mu);
+    for (auto &kv : g_scratch_cache.idle)
+      for (const ScratchCache::Block &b : kv.second) {
+        (void)hipFree(b.p);
+        g_scratch_cache.owned.erase(b.p);
+      }
+    g_scratch_cache.idle.clear();
+    g_scratch_cache.idle_bytes = 0;
+  }
   for (int dev = 0; dev < 64; dev++) {
     hipMemPool_t pool = g_scratch_pools.pool[dev].exchange(nullptr, std::memory_order_acq_rel);
     if (pool != nullptr) (void)hipMemPoolDestroy(pool);

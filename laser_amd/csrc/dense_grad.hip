@@ -246,7 +246,7 @@ hipError_t launch_bias_grad_f32(float *db, int64_t db_stride, float *dz, int64_t
     e = n % 4 == 0 ? launch_instance<true>(LASER_HIP_ACT_NONE, b, grid, s) : launch_instance<false>(LASER_HIP_ACT_NONE, b, grid, s);
   }
   if (part != nullptr) {
-    const hipError_t f = hipFreeAsync(part, s);
+    const hipError_t f = scratch_free_async(part, s);
     if (e == hipSuccess) e = f;
   }
   if (e == hipSuccess) g_last_bias_grad_kernel = (int)plan[0];

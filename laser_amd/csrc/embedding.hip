@@ -435,7 +435,7 @@ hipError_t launch_embedding_group_i32(int32_t *order, int32_t *starts, const int
     e = hipGetLastError();
   }
   if (scratch != nullptr) {
-    const hipError_t f = hipFreeAsync(scratch, s);
+    const hipError_t f = scratch_free_async(scratch, s);
     if (e == hipSuccess) e = f;
   }
   if (e == hipSuccess) {
@@ -485,7 +485,7 @@ hipError_t launch_embedding_grad_f32(float *dw, int64_t dws, const float *dy, in
     }
   }
   if (own != nullptr) {
-    const hipError_t f = hipFreeAsync(own, s);
+    const hipError_t f = scratch_free_async(own, s);
     if (e == hipSuccess) e = f;
   }
   if (e == hipSuccess) g_last_embedding_kernel[2] = vec ? 0 : 1;

@@ -444,7 +444,7 @@ hipError_t launch_gemm_asm_packed(GemmArgs<T> a, size_t bytes, bool laser_order,
   if (e != hipSuccess) return e;
   e = pack(a, scratch);
   if (e == hipSuccess) e = launch_gemm_asm_core(a, laser_order, o, s);
-  const hipError_t e2 = hipFreeAsync(scratch, s);
+  const hipError_t e2 = scratch_free_async(scratch, s);
   if (e == hipErrorNotSupported) return e;      // (nothing was launched but the packing passes, which touched only the scratch)
   return e != hipSuccess ? e : e2;
 }
@@ -621,7 +621,7 @@ hipError_t launch_conv_f32_asm(const GemmArgs<float> &a_in, bool laser_order, hi
     if (e != hipSuccess) return e;
     e = launch_pack_pad<float>(packed, a.M, Kp, a.A, a.M, a.K, a.rsA, a.csA, s, 0);
     if (e != hipSuccess) {
-      (void)hipFreeAsync(packed, s);
+      (void)scratch_free_async(packed, s);
       return e == hipErrorInvalidValue ? hipErrorNotSupported : e;
     }
   }
@@ -671,7 +671,7 @@ hipError_t launch_conv_f32_asm(const GemmArgs<float> &a_in, bool laser_order, hi
   }
   e = launch_planned(m, pick, plain, ka, tiles_m, tiles_n, group_m, a.batch, 0, s, o, walk_G);
   if (packed) {
-    const hipError_t e2 = hipFreeAsync(packed, s);
+    const hipError_t e2 = scratch_free_async(packed, s);
     if (e == hipSuccess) e = e2;
   }
   if (e == hipSuccess) g_last_f32_asm = 1 + pick;

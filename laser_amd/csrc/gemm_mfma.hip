@@ -389,7 +389,7 @@ hipError_t launch_conv_implicit_f32(const GemmArgs<float> &args, int cfg, bool l
     // images stack as rows of one (batch*M) x ntail view of the output's tail columns
     if (e == hipSuccess)
       e = launch_combine_slices<float>(a.C + plan.n_cut * a.csC, a.rsC, a.csC, W, (int64_t)a.batch * a.M, ntail, (int)nsl, a.alpha, a.beta, s);
-    const hipError_t e2 = hipFreeAsync(W, s);
+    const hipError_t e2 = scratch_free_async(W, s);
     return e != hipSuccess ? e : e2;
   }
   g_last_conv_tail = 3;

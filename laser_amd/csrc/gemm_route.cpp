@@ -70,7 +70,7 @@ hipError_t gemm_slice_parallel(const GemmArgs<T> &a, int kc, hipStream_t s) {
     e = launch_tiled(c, s);
   }
   if (e == hipSuccess) e = launch_combine_slices<T>(a.C, a.rsC, a.csC, W, a.M, a.N, (int)nsl, a.alpha, a.beta, s);
-  const hipError_t e2 = hipFreeAsync(W, s);
+  const hipError_t e2 = scratch_free_async(W, s);
   return e != hipSuccess ? e : e2;
 }
 
@@ -135,7 +135,7 @@ hipError_t run_gemm_prologue_materialised(const GemmArgs<T> &a, hipStream_t s) {
     b.B = scratch + nA; b.rsB = a.N; b.csB = 1;
   }
   if (e == hipSuccess) e = run_gemm<T>(b, s);
-  const hipError_t e2 = hipFreeAsync(scratch, s);
+  const hipError_t e2 = scratch_free_async(scratch, s);
   return e != hipSuccess ? e : e2;
 }
 
@@ -237,7 +237,7 @@ hipError_t run_gemm_int(const GemmArgs<T> &a, hipStream_t s) {
   e = a.K > t.k_chunk ? int_gemm_k_chunks<T>(a, ws, s, t.first, t.fallback, t.k_chunk) : t.first(a, ws, s);
   if (e == hipErrorNotSupported) e = t.fallback(a, ws, s);
   if (t.narrow && e == hipSuccess) g_last_narrow_mfma = 1;
-  const hipError_t e2 = hipFreeAsync(ws, s);
+  const hipError_t e2 = scratch_free_async(ws, s);
   return e != hipSuccess ? e : e2;
 }
 

@@ -674,7 +674,7 @@ hipError_t launch_layer_norm_param_grads_f32(float *dgamma, int64_t dgs, float *
     if (e == hipSuccess && dgamma) e = launch_bias_grad_f32(dgamma, dgs, nullptr, 0, a.outg, n, nullptr, 0, chunks, n, LASER_HIP_ACT_NONE, s);
     if (e == hipSuccess && dbeta) e = launch_bias_grad_f32(dbeta, dbs, nullptr, 0, a.outb, n, nullptr, 0, chunks, n, LASER_HIP_ACT_NONE, s);
     g_last_bias_grad_kernel = keep;
-    const hipError_t f = hipFreeAsync(part, s);
+    const hipError_t f = scratch_free_async(part, s);
     if (e == hipSuccess) e = f;
   }
   if (e == hipSuccess) g_last_layer_norm_kernel[LH_LAYER_NORM_PARAMS] = (int)plan[0];

@@ -379,7 +379,7 @@ hipError_t launch_grad_norm_f32(float *d_norm, float *d_clip, const float *const
     e = hipGetLastError();
   }
   if (buf) {
-    const hipError_t f = hipFreeAsync(buf, s);
+    const hipError_t f = scratch_free_async(buf, s);
     if (e == hipSuccess) e = f;
   }
   return e;

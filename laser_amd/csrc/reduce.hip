@@ -231,7 +231,7 @@ hipError_t reduce_levels(int64_t n, int e0, int acc_size, void *out, hipStream_t
   e = level0(count[0], buf + off[0]);
   for (int l = 1; l < levels && e == hipSuccess; l++)
     e = partials(buf + off[l - 1], count[l - 1], count[l], l + 1 < levels ? (void *)(buf + off[l]) : out);
-  const hipError_t f = hipFreeAsync(buf, s);
+  const hipError_t f = scratch_free_async(buf, s);
   return e != hipSuccess ? e : f;
 }
 
