@@ -16,6 +16,7 @@
 #include <utility>
 
 #include "laser_hip.h"
+#include "laser_hip_select.h"
 
 namespace laser {
 
@@ -1300,6 +1301,61 @@ inline Tensor<int32_t> cdfSampleAndRemove(const Tensor<float> &weights, Rng &rng
                                                 (int64_t)rng.subseq, (int64_t)rng.offset, rows, n, num, stream));
   rng.advance((uint64_t)(rows * num));
   return idx;
+}
+
+// ---- Row top-k, argmax and top-k sampling (include/laser_hip_select.h, the section of that name) -------------------------------
+//   auto r = laser::topk(x, k, largest);        r.values (bit copies), r.indices: (rows, k), rank 0 first; x: a matrix whose rows
+//                                               are contiguous (or a vector for one row)
+//   laser::argmax(x), laser::argmin(x)          Tensor<int32_t> (rows): topk's index for k = 1 from a single pass
+//   laser::take_rows(src, j)                    out[r, c] = src[r, j[r, c]], -1 where j[r, c] is outside the row
+//   laser::sample_top_k(logits, k, u) / (logits, k, rng, num)   draws among the k largest logits of every row in proportion to
+//                                               their softmax: topk, softmax, cumsum, cdfSample, take_rows
+// The order is one of bit patterns (a positive NaN is the largest element, -0 ranks below +0, identical bits rank by ascending
+// column): every bit and index is a function of the row's bits, k and `largest` alone.  Asynchronous on `stream`.
+struct TopkResult {
+  Tensor<float> values;
+  Tensor<int32_t> indices;
+};
+inline TopkResult topk(const Tensor<float> &x, int64_t k, bool largest = true, void *stream = nullptr) {
+  int64_t rows, n, rs;
+  detail::scan_rows(x, "topk", rows, n, rs);
+  if (k < 1 || k > n || k > LASER_HIP_SELECT_MAX_K) throw Error(LASER_HIP_E_INVALID, "topk: 1 <= k <= min(n, 1024) is needed");
+  TopkResult r{newTensor<float>({rows, k}), newTensor<int32_t>({rows, k})};
+  check(laser_hip_topk_rows_f32_dev(r.values.unsafe_raw_data(), k, r.indices.unsafe_raw_data(), k, x.unsafe_raw_data(), rs, rows, n, k,
+                                    largest ? 1 : 0, stream));
+  return r;
+}
+namespace detail {
+inline Tensor<int32_t> arg_rows(const Tensor<float> &x, const char *what, int largest, void *stream) {
+  int64_t rows, n, rs;
+  scan_rows(x, what, rows, n, rs);
+  Tensor<int32_t> idx = newTensor<int32_t>({rows});
+  check(laser_hip_argmax_rows_f32_dev(idx.unsafe_raw_data(), 1, nullptr, 1, x.unsafe_raw_data(), rs, rows, n, largest, stream));
+  return idx;
+}
+}  // namespace detail
+inline Tensor<int32_t> argmax(const Tensor<float> &x, void *stream = nullptr) { return detail::arg_rows(x, "argmax", 1, stream); }
+inline Tensor<int32_t> argmin(const Tensor<float> &x, void *stream = nullptr) { return detail::arg_rows(x, "argmin", 0, stream); }
+inline Tensor<int32_t> take_rows(const Tensor<int32_t> &src, const Tensor<int32_t> &j, void *stream = nullptr) {
+  int64_t rows, m, ss, jrows, num, js;
+  detail::scan_rows(src, "take_rows", rows, m, ss);
+  if (j.rank() != 2 || src.rank() != 2) throw Error(LASER_HIP_E_INVALID, "take_rows: two matrices are needed");
+  if (j.shape[1] == 0) return newTensor<int32_t>({rows, 0});
+  detail::scan_rows(j, "take_rows", jrows, num, js);
+  if (jrows != rows) throw Error(LASER_HIP_E_INVALID, "take_rows: src and j need the same number of rows");
+  Tensor<int32_t> out = newTensor<int32_t>({rows, num});
+  check(laser_hip_take_rows_i32_dev(out.unsafe_raw_data(), num, src.unsafe_raw_data(), ss, j.unsafe_raw_data(), js, rows, m, num, stream));
+  return out;
+}
+inline Tensor<int32_t> sample_top_k(const Tensor<float> &logits, int64_t k, const Tensor<float> &u, void *stream = nullptr) {
+  if (logits.rank() != 2) throw Error(LASER_HIP_E_INVALID, "sample_top_k: a matrix of logits is needed");
+  const TopkResult r = topk(logits, k, true, stream);
+  return take_rows(r.indices, cdfSample(cumsum(softmax(r.values, stream), stream), u, stream), stream);
+}
+inline Tensor<int32_t> sample_top_k(const Tensor<float> &logits, int64_t k, Rng &rng, int64_t num = 1, void *stream = nullptr) {
+  if (logits.rank() != 2) throw Error(LASER_HIP_E_INVALID, "sample_top_k: a matrix of logits is needed");
+  const TopkResult r = topk(logits, k, true, stream);
+  return take_rows(r.indices, cdfSample(cumsum(softmax(r.values, stream), stream), rng, num, stream), stream);
 }
 
 #undef LASER_DISPATCH

@@ -17,7 +17,8 @@ from .nn import bias_grad, linear_backward, layer_norm, layer_norm_backward  # n
 from .optim import sgd_step, adam_step, grad_norm, adam_bias_correction, SGD, Adam  # noqa: F401
 from .nn import embedding, embedding_group, embedding_backward  # noqa: F401
 from .nn import attention, attention_backward  # noqa: F401
-from .sampling import Sampler, newSampler, multinomial  # noqa: F401
+from .sampling import Sampler, newSampler, multinomial, sample_top_k  # noqa: F401
+from .select import topk, argmax, argmin, take_rows, topk_plan, topk_last_kernel  # noqa: F401
 from .random import Rng, randomTensor, randomNormalTensor  # noqa: F401
 from .scan import cumsum, searchsorted, cdfSample, cdfSampleAndRemove  # noqa: F401
 from .sharded import (shard_plan, set_shard_devices, get_shard_devices, gemm_strided_sharded, matmul_sharded,  # noqa: F401

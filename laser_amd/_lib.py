@@ -28,7 +28,7 @@ _lib = None
 
 
 def lib():
-    """Load the library (once) and declare every prototype of include/laser_hip.h."""
+    """Load the library (once) and declare every prototype of include/laser_hip.h and include/laser_hip_select.h."""
     global _lib
     if _lib is not None:
         return _lib
@@ -193,6 +193,12 @@ def lib():
     L.laser_hip_random_normal_f32_dev.argtypes = [vp, i64, C.c_float, C.c_float, u64, u64, u64, vp]
     for sfx, ct in _CT.items():
         getattr(L, f"laser_hip_random_uniform_{sfx}_dev").argtypes = [vp, i64, ct, ct, u64, u64, u64, vp]
+    # include/laser_hip_select.h
+    L.laser_hip_topk_rows_f32_dev.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, i64, ci, vp]
+    L.laser_hip_argmax_rows_f32_dev.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, ci, vp]
+    L.laser_hip_take_rows_i32_dev.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, i64, vp]
+    L.laser_hip_topk_plan.argtypes = [i64, i64, i64, ci, pi]
+    L.laser_hip_topk_last_kernel.argtypes = []
     L.laser_hip_cblas_sgemm.argtypes = [ci, ci, ci, i64, i64, i64, C.c_float, vp, i64, vp, i64, C.c_float, vp, i64]
     L.laser_hip_cblas_dgemm.argtypes = [ci, ci, ci, i64, i64, i64, C.c_double, vp, i64, vp, i64, C.c_double, vp, i64]
     _lib = L
@@ -206,6 +212,12 @@ def check(rc):
 
 def ctype_of(sfx):
     return C.c_int32 if sfx in _NARROW else _CT[sfx]
+
+
+# Every symbol include/laser_hip_select.h declares.
+def select_symbols():
+    return ["laser_hip_topk_rows_f32_dev", "laser_hip_argmax_rows_f32_dev", "laser_hip_take_rows_i32_dev", "laser_hip_topk_plan",
+            "laser_hip_topk_last_kernel"]
 
 
 # Every symbol include/laser_hip.h declares (tests check the .so exports each of them).

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "../../include/laser_hip_select.h"
 #include "normal_core.h"
 #include "philox_core.h"
 #include "random_plan.h"
@@ -31,6 +32,7 @@
 #include "embedding_plan.h"
 #include "optim_plan.h"
 #include "layer_norm_plan.h"
+#include "select_plan.h"
 #include "attention_plan.h"
 #include "softmax_axis_plan.h"
 #include "softmax_rows_plan.h"
@@ -1625,6 +1627,87 @@ int laser_hip_layer_norm_plan(int64_t rows, int64_t n, int vec, int what, int64_
   return LASER_HIP_OK;
 }
 int laser_hip_layer_norm_last_kernel(int what) { return what >= 0 && what < 3 ? (int)g_last_layer_norm_kernel[what] : -1; }
+// ---- row top-k, argmax and the row gather (select.hip, select_plan.h; include/laser_hip_select.h) ----------------------------------
+namespace {
+// [p, p + bytes) and [q, q + qbytes) share a byte
+bool select_overlap(const void *p, long long bytes, const void *q, long long qbytes) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return p && q && bytes > 0 && qbytes > 0 && a < b + (uintptr_t)qbytes && b < a + (uintptr_t)bytes;
+}
+// bytes from the base of a (rows, len) operand of 4-byte elements to its end (rows >= 1)
+long long select_span(int64_t rows, int64_t stride, int64_t len) { return ((rows - 1) * (rows > 1 ? stride : 0) + len) * 4; }
+int select_sizes(const char *fn, int64_t rows, int64_t n) {
+  if (rows < 0 || rows > LASER_HIP_SELECT_MAX_ROWS)
+    return fail(LASER_HIP_E_INVALID, "%s: rows %lld (0 <= rows <= 2^26 is needed)", fn, (long long)rows);
+  if (n < 1 || n > LASER_HIP_SELECT_MAX_N) return fail(LASER_HIP_E_INVALID, "%s: row length %lld (1 <= n <= 2^24 is needed)", fn, (long long)n);
+  return LASER_HIP_OK;
+}
+}  // namespace
+int laser_hip_topk_rows_f32_dev(float *d_vals, int64_t vals_row_stride, int32_t *d_idx, int64_t idx_row_stride, const float *d_src,
+                                int64_t src_row_stride, int64_t rows, int64_t n, int64_t k, int largest, void *stream) {
+  if (int rc = select_sizes("topk", rows, n)) return rc;
+  if (k < 1 || k > n || k > LASER_HIP_SELECT_MAX_K)
+    return fail(LASER_HIP_E_INVALID, "topk: k %lld (1 <= k <= min(n, 1024) is needed; n %lld)", (long long)k, (long long)n);
+  if (largest != 0 && largest != 1) return fail(LASER_HIP_E_INVALID, "topk: largest %d (0 or 1)", largest);
+  if (rows == 0) return LASER_HIP_OK;
+  if (!d_vals && !d_idx) return fail(LASER_HIP_E_INVALID, "topk: neither values nor indices are asked for");
+  if (!d_src) return fail(LASER_HIP_E_INVALID, "topk: null source");
+  if (rows > 1 && (src_row_stride < n || (d_vals && vals_row_stride < k) || (d_idx && idx_row_stride < k)))
+    return fail(LASER_HIP_E_INVALID, "topk: row strides %lld (source, >= n %lld) / %lld (values) / %lld (indices, >= k %lld)",
+                (long long)src_row_stride, (long long)n, (long long)vals_row_stride, (long long)idx_row_stride, (long long)k);
+  const long long src_bytes = select_span(rows, src_row_stride, n);
+  if (select_overlap(d_vals, select_span(rows, vals_row_stride, k), d_src, src_bytes) ||
+      select_overlap(d_idx, select_span(rows, idx_row_stride, k), d_src, src_bytes))
+    return fail(LASER_HIP_E_INVALID, "topk: an output overlaps the source (no overlap is allowed)");
+  if (int rc = ensure_init()) return rc;
+  HIP_TRY(launch_topk_rows_f32(d_vals, vals_row_stride, d_idx, idx_row_stride, d_src, src_row_stride, rows, n, k, largest,
+                               (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_argmax_rows_f32_dev(int32_t *d_idx, int64_t idx_stride, float *d_val, int64_t val_stride, const float *d_src,
+                                  int64_t src_row_stride, int64_t rows, int64_t n, int largest, void *stream) {
+  if (int rc = select_sizes("argmax", rows, n)) return rc;
+  if (largest != 0 && largest != 1) return fail(LASER_HIP_E_INVALID, "argmax: largest %d (0 or 1)", largest);
+  if (rows == 0) return LASER_HIP_OK;
+  if (!d_idx || !d_src) return fail(LASER_HIP_E_INVALID, "argmax: null buffer");
+  if (rows > 1 && (src_row_stride < n || idx_stride < 1 || (d_val && val_stride < 1)))
+    return fail(LASER_HIP_E_INVALID, "argmax: strides %lld (source, >= n %lld) / %lld (indices) / %lld (values, >= 1)",
+                (long long)src_row_stride, (long long)n, (long long)idx_stride, (long long)val_stride);
+  const long long src_bytes = select_span(rows, src_row_stride, n);
+  if (select_overlap(d_idx, select_span(rows, idx_stride, 1), d_src, src_bytes) ||
+      select_overlap(d_val, select_span(rows, val_stride, 1), d_src, src_bytes))
+    return fail(LASER_HIP_E_INVALID, "argmax: an output overlaps the source (no overlap is allowed)");
+  if (int rc = ensure_init()) return rc;
+  HIP_TRY(launch_argmax_rows_f32(d_idx, idx_stride, d_val, val_stride, d_src, src_row_stride, rows, n, largest, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_take_rows_i32_dev(int32_t *d_out, int64_t out_row_stride, const int32_t *d_src, int64_t src_row_stride,
+                                const int32_t *d_j, int64_t j_row_stride, int64_t rows, int64_t m, int64_t num, void *stream) {
+  if (int rc = select_sizes("take_rows", rows, m)) return rc;
+  if (num < 0 || num > LASER_HIP_SELECT_MAX_N) return fail(LASER_HIP_E_INVALID, "take_rows: num %lld (0 <= num <= 2^24 is needed)", (long long)num);
+  if (rows == 0 || num == 0) return LASER_HIP_OK;
+  if (!d_out || !d_src || !d_j) return fail(LASER_HIP_E_INVALID, "take_rows: null buffer");
+  if (rows > 1 && (src_row_stride < m || out_row_stride < num || j_row_stride < num))
+    return fail(LASER_HIP_E_INVALID, "take_rows: row strides %lld (source, >= m %lld) / %lld (out) / %lld (j, >= num %lld)",
+                (long long)src_row_stride, (long long)m, (long long)out_row_stride, (long long)j_row_stride, (long long)num);
+  const long long out_bytes = select_span(rows, out_row_stride, num);
+  if (select_overlap(d_out, out_bytes, d_src, select_span(rows, src_row_stride, m)) ||
+      select_overlap(d_out, out_bytes, d_j, select_span(rows, j_row_stride, num)))
+    return fail(LASER_HIP_E_INVALID, "take_rows: out overlaps src or j (no overlap is allowed)");
+  if (int rc = ensure_init()) return rc;
+  HIP_TRY(launch_take_rows_i32(d_out, out_row_stride, d_src, src_row_stride, d_j, j_row_stride, rows, m, num, (hipStream_t)stream));
+  return LASER_HIP_OK;
+}
+int laser_hip_topk_plan(int64_t rows, int64_t n, int64_t k, int vec, int64_t *out3) {
+  if (!out3) return fail(LASER_HIP_E_INVALID, "topk_plan: null out3");
+  long long p[3];
+  if (lh_topk_plan(rows, n, k, vec, p) != 0)
+    return fail(LASER_HIP_E_INVALID, "topk_plan: rows %lld, n %lld, k %lld outside 0..2^26, 1..2^24, 1..min(n, 1024)", (long long)rows,
+                (long long)n, (long long)k);
+  for (int i = 0; i < 3; i++) out3[i] = p[i];
+  return LASER_HIP_OK;
+}
+int laser_hip_topk_last_kernel(void) { return g_last_topk_kernel; }
 // ---- the softmax gradient from the output (softmax_grad.hip; lh_softmax_grad_rows_plan in softmax_rows_plan.h) --------------------
 int laser_hip_softmax_grad_rows_f32_dev(float *dx, int64_t dx_row_stride, const float *dy, int64_t dy_row_stride, const float *y,
                                         int64_t y_row_stride, int64_t rows, int64_t n, void *stream) {

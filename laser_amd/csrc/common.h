@@ -385,6 +385,16 @@ hipError_t launch_embedding_grad_f32(float *dw, int64_t dw_row_stride, const flo
                                      const int32_t *order, const int32_t *starts, int64_t tokens, int64_t vocab, int64_t dim,
                                      hipStream_t s);
 extern std::atomic<int> g_last_embedding_kernel[4];
+// row selection (select.hip; select_plan.h is the launch plan; include/laser_hip_select.h): the k first elements of every row in
+// the key order with their columns (vals or idx may be null), the first element alone in one pass (val may be null), and the
+// row gather out[r, c] = src[r, j[r, c]].  g_last_topk_kernel: the plan's code of the last top-k launch, + 8 for an argmax launch
+hipError_t launch_topk_rows_f32(float *vals, int64_t vals_row_stride, int32_t *idx, int64_t idx_row_stride, const float *src,
+                                int64_t src_row_stride, int64_t rows, int64_t n, int64_t k, int largest, hipStream_t s);
+hipError_t launch_argmax_rows_f32(int32_t *idx, int64_t idx_stride, float *val, int64_t val_stride, const float *src,
+                                  int64_t src_row_stride, int64_t rows, int64_t n, int largest, hipStream_t s);
+hipError_t launch_take_rows_i32(int32_t *out, int64_t out_row_stride, const int32_t *src, int64_t src_row_stride, const int32_t *j,
+                                int64_t j_row_stride, int64_t rows, int64_t m, int64_t num, hipStream_t s);
+extern std::atomic<int> g_last_topk_kernel;
 // the optimizer steps over a list of tensors and the global gradient norm (optim.hip; optim_core.h is the arithmetic,
 // optim_plan.h the launch plan): the pointer lists are host arrays of device pointers, m may be null for SGD, d_clip may be null
 hipError_t launch_sgd_step_f32(float *const *w, const float *const *g, float *const *m, const int64_t *lens, int count, float lr, float mu,

@@ -6,6 +6,7 @@ include/laser_hip.h "F+tree weighted sampler") over the rows of a float32 matrix
     s.sampleAndRemove(u=None, num=1, rng=None) num draws per row without replacement (mutates the trees; -1 once a row is empty)
     s.update(elem, weight)                     one (elem, weight) per row; elem = -1 leaves that row alone
     laser_amd.multinomial(probs, num_samples=1, replacement=False, u=None, rng=None, method="ftree")   build and draw in one call
+    laser_amd.sample_top_k(logits, k, num_samples=1, u=None, rng=None)     draws among the k largest logits of every row
 
 `weights` is a laser_amd.Tensor or a torch CUDA tensor whose rows are contiguous; the weights need not sum to 1.  The uniform
 numbers come from one of three places.  `u` is a float32 array of shape (rows, num) with values in [0, 1) -- a device tensor,
@@ -171,3 +172,21 @@ def multinomial(probs, num_samples=1, replacement=False, u=None, rng=None, metho
         raise ValueError(f"method = {method!r} (\"ftree\" or \"cdf\")")
     s = newSampler(probs)
     return s.sample(u, num_samples, rng) if replacement else s.sampleAndRemove(u, num_samples, rng)
+
+
+def sample_top_k(logits, k, num_samples=1, u=None, rng=None):
+    """num_samples column indices per row of the 2-D float32 `logits`, drawn among the row's k largest in proportion to their
+    softmax: int32 Tensor (rows, num_samples).  A composition of calls with defined bits -- topk (laser_amd/select.py), softmax
+    of the k values, cumsum, the inverse-CDF draw cdfSample (laser_amd/scan.py) with `u` or `rng` as Sampler.sample takes
+    them, then take_rows on topk's indices -- so the ids are a function of the logits and the uniform numbers alone.  k = 1
+    is argmax.  A row whose k largest hold a NaN or +Inf has a NaN softmax and draws -1."""
+    from . import scan, select
+    from .simd_math import softmax
+    if u is not None and rng is not None:
+        raise ValueError("give the uniform numbers `u` or the generator `rng`, not both")
+    v = _View("logits", logits)
+    if v.rank != 2:
+        raise ValueError(f"sample_top_k: logits has rank {v.rank} (a matrix is needed)")
+    vals, idx = select.topk(logits, k)
+    pos = scan.cdfSample(scan.cumsum(softmax(vals)), u, num_samples, rng)
+    return select.take_rows(idx, pos)
